@@ -8,10 +8,15 @@ exchange (one flat RCCL all-reduce bucket, N > 1) and an SGD update of the weigh
 step sizes.  Inputs / grads are synthetic tensors of the layer shapes (no dataset);
 weights are kaiming-normal (resnet.py:43-45).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line (metric / value / roofline / cpu_baseline ...).
+A plain run sets up, warms up, times the K steps and has rank 0 print ONE JSON line (metric /
+value / ms_per_step / config ...).  ``--dump-outputs DIR`` also writes what the last timed step
+computed as ``DIR/<name>.npy`` (dump_outputs).  ``--full`` adds everything else to the line, each
+from runs of its own after the timed steps: per-kernel and per-layer times, the forward-only rate,
+the dominant kernel family's roofline, measured peaks, the other BASELINE configs and the CPU
+baseline (roofline / fwd_only / extra_configs / cpu_baseline ...).
 """
 from __future__ import annotations
 
@@ -88,9 +93,12 @@ class Trainer:
     """fwd+bwd over the CiM layers, flat-bucket gradient all-reduce, SGD (examples/__init__.py:184-188:
     alpha_* excluded from weight decay)."""
 
-    def __init__(self, layers, world, segments=None):
+    def __init__(self, layers, world, segments=None, keep_outputs=False):
         from cim_quantization_amd.dist import GradBucket
         self.layers, self.world = layers, world
+        # keep_outputs (--dump-outputs): each layer's forward output of the latest step stays alive
+        # (in a captured step: the graph's own output tensors, rewritten by every replay)
+        self.kept = [None] * len(layers) if keep_outputs else None
         # the step in segments of consecutive layers (world > 1: three): at the end of a segment its
         # layers' parameter-gradient epilogues are flushed and their slice of the bucket goes out
         # (GradBucket.exchange_segment) while the next segment computes; one segment at world 1
@@ -129,8 +137,14 @@ class Trainer:
             prepare_weights(self.layers)
         a, b = self.segments[k]
         with chained_epilogues():
-            for m, x, gy in zip(self.layers[a:b], xs[a:b], gs[a:b]):
-                m(x).backward(gy)
+            for i, (m, x, gy) in enumerate(zip(self.layers[a:b], xs[a:b], gs[a:b]), a):
+                if self.kept is None:
+                    m(x).backward(gy)
+                else:
+                    y = m(x)
+                    y.backward(gy)
+                    self.kept[i] = y.detach()  # the values only: not the autograd node and its ctx buffers
+                    del y
         self.bucket.join()  # the parameter-gradient epilogues are part of the step
 
     def compute(self, xs, gs, exchange=False):
@@ -372,6 +386,36 @@ def layer_breakdown(trainer, xs, gs, dev):
     return {n: round(a.elapsed_time(b), 4) for n, a, b in res}
 
 
+DUMP_SAMPLE = 1 << 19  # elements kept of one layer's output: 19 x 2 MB, with the parameters under 45 MB in all
+
+
+def snapshot_outputs(trainer):
+    """What the latest step of ``trainer`` (built with keep_outputs) left its caller, as float32 numpy
+    arrays by name: every parameter after the update (``<layer>.<parameter>``), the optimizer's momentum
+    buffer (``momentum``, flat, the bucket's layout) and every layer's forward output
+    (``<layer>.out``; of an output above DUMP_SAMPLE elements a fixed sample, the same flat indices in
+    every run: numpy's default_rng seeded with the layer's index).  Read before any further step."""
+    import numpy as np
+    arrays = {}
+    for i, (spec, m) in enumerate(zip(RESNET20, trainer.layers)):
+        for pn, p in m.named_parameters():
+            arrays[f"{spec[0]}.{pn}"] = p.detach().cpu().numpy().astype(np.float32)
+        y = trainer.kept[i].reshape(-1)
+        if y.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(i).integers(0, y.numel(), DUMP_SAMPLE))
+            y = y[torch.from_numpy(idx).to(y.device)]
+        arrays[f"{spec[0]}.out"] = y.cpu().numpy().astype(np.float32)
+    arrays["momentum"] = trainer.opt.buf.detach().cpu().numpy().astype(np.float32)
+    return arrays
+
+
+def dump_outputs(arrays, path):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def cpu_baseline(batch_cpu: int, threads: int):
     """The op-faithful torch-CPU port of the reference's Function (oracle/cim_torch_port.py: the
     lsq.py:92-386 op sequence, bit-identical to the reference and 0.95-0.98x its time in the
@@ -561,10 +605,17 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256, help="per-GPU batch")
-    ap.add_argument("--cpu-batch", type=int, default=256)
-    ap.add_argument("--no-cfg5", action="store_true", help="skip the BASELINE cfg5 (QuantLinear) extra line")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-peaks", action="store_true", help="skip the measured HBM-copy / bf16-GEMM peaks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (snapshot_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure per-kernel / per-layer times, the forward-only rate, the "
+                         "roofline, peaks, the other BASELINE configs and the CPU baseline")
+    ap.add_argument("--cpu-batch", type=int, default=256, help="with --full: batch of the CPU baseline")
+    ap.add_argument("--no-cfg5", action="store_true",
+                    help="with --full: skip the other BASELINE configs (cfg5 QuantLinear, cfg1, cfg4)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-peaks", action="store_true",
+                    help="with --full: skip the measured HBM-copy / bf16-GEMM peaks")
     ap.add_argument("--no-graph", action="store_true", help="launch every kernel from the host each step")
     args = ap.parse_args()
 
@@ -584,46 +635,88 @@ def main():
 
     torch.cuda.reset_peak_memory_stats(dev)
     layers, xs, gs = build(dev, args.batch, seed=1234, data_seed=1235 + 1000 * rank)
-    tr = Trainer(layers, world)
+    tr = Trainer(layers, world, keep_outputs=args.dump_outputs is not None)
     for _ in range(max(1, args.warmup)):  # the first step runs the LSQ / alpha_cim init (lsq.py:532-563)
         tr.step(xs, gs)
     torch.cuda.synchronize(dev)
-
-    # per-role kernel ms of one untimed step (all variants), and the dominant kernel family
-    per_kernel = {}
-    for kname in ("fwd", "bwd_gx", "bwd_gw", "prep_act") + tuple(FAMILIES):
-        with _lib.KernelTimer(kname) as kt:
-            tr.step(xs, gs)
-        per_kernel[kname] = kt.total_ms
-    dominant = max(FAMILIES, key=per_kernel.get)
 
     graph = not args.no_graph
     if graph:
         tr.flat.zero_()
         tr.capture(xs, gs)
-        elapsed = timed(tr, xs, gs, args.steps, dev, world, True)
+    elapsed = timed(tr, xs, gs, args.steps, dev, world, graph)
+    if args.dump_outputs is not None:
+        arrays = snapshot_outputs(tr)  # the last timed step's, before anything else runs
+        if rank == 0:
+            dump_outputs(arrays, args.dump_outputs)
+        del arrays
+
+    if args.full:
+        # per-role kernel ms of one untimed step (all variants), and the dominant kernel family
+        per_kernel = {}
+        for kname in ("fwd", "bwd_gx", "bwd_gw", "prep_act") + tuple(FAMILIES):
+            with _lib.KernelTimer(kname) as kt:
+                tr.step(xs, gs)
+            per_kernel[kname] = kt.total_ms
+        dominant = max(FAMILIES, key=per_kernel.get)
         # HIP events recorded inside a graph cannot be timed on ROCm 7: the dominant family's
-        # launches are timed over the same number of host-launched steps right after (same
-        # inputs, same kernels; only the launch path differs)
+        # launches are timed over the same number of host-launched steps after the timed ones
+        # (same inputs, same kernels; only the launch path differs)
         with _lib.KernelTimer(dominant, max_launches=len(RESNET20) * args.steps + 8) as kt:
             for _ in range(args.steps):
                 tr.step(xs, gs)
             torch.cuda.synchronize(dev)
+        fwd_elapsed = timed_forward(tr, xs, args.steps, dev, world, graph)
     else:
-        with _lib.KernelTimer(dominant, max_launches=len(RESNET20) * args.steps + 8) as kt:
-            elapsed = timed(tr, xs, gs, args.steps, dev, world, False)
-    fwd_elapsed = timed_forward(tr, xs, args.steps, dev, world, graph)
+        kt = dominant = per_kernel = None
+        fwd_elapsed = 0.0
     t = torch.tensor([elapsed, fwd_elapsed], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed, fwd_elapsed = t.tolist()
     # device memory of the whole training step (inputs, parameters, bucket, ctx / workspaces, the graph's pool)
     peak_mb = torch.cuda.max_memory_allocated(dev) / 2 ** 20
-    breakdown = layer_breakdown(tr, xs, gs, dev)
 
     ms_per_step = elapsed / args.steps * 1e3
     macs_step = macs_per_sample() * args.batch * world
     value = macs_step / (elapsed / args.steps)
+    result = {
+        "metric": "quantized-MAC/s + fwd+bwd ms per ResNet-20 w3a3 CiM layer, batch 256",
+        "value": value,
+        "unit": "MAC/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "ms_per_layer_fwd_bwd": ms_per_step / len(RESNET20),
+        "value_semantics": "logical MAC (B*P*O*K, flops_counter.py:314-318) of the 19 convs per fwd+bwd+SGD "
+                           "step / step time; the forward-only rate SURVEY 8(d) defines is fwd_only.value (--full)",
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "i8+f32",
+        "data": "synthetic (random-init weights, randn / relu(randn) activations of the layer shapes)",
+        "config": {"workload": "resnet20_w3a3_all_19_cim_convs_fwd_bwd_sgd", "global_batch": args.batch * world,
+                   "per_gpu_batch": args.batch, "xbar": XBAR, "adc_bits": ADC, "first_layer": "w8a8",
+                   "parallelism": f"dp{world}", "grad_bucket_mb": round(tr.bucket_mb, 3), "exchange_segments": len(tr.segments),
+                   "launch": "hip_graph" if graph else "eager", "recompute_psum": RECOMPUTE},
+        "peak_mem_mb": round(peak_mb, 1),
+    }
+    if args.full:
+        result.update(full_report(tr, xs, gs, dev, args, world, rank, kt, dominant, per_kernel, ms_per_step,
+                                  macs_step, fwd_elapsed))
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_report(tr, xs, gs, dev, args, world, rank, kt, dominant, per_kernel, ms_per_step, macs_step, fwd_elapsed):
+    """--full: what the line carries beyond the headline step time, from the measurements main() took
+    after the timed steps and further runs of its own."""
+    from cim_quantization_amd import _lib
+    result = {}
+    breakdown = layer_breakdown(tr, xs, gs, dev)
     roof = family_roofline(kt, dominant, args.steps)
     nl = max(kt.launches, 1)
     traffic, valu, pmc_source = measured_pmc(dominant)
@@ -636,35 +729,15 @@ def main():
                         "frac": t_valu / (kt.total_ms / nl * 1e-3), "peak_lane_ops_per_s": PEAK_VALU_LANE_OPS}
     else:
         roof["valu"] = None
-    result = {
-        "metric": "quantized-MAC/s + fwd+bwd ms per ResNet-20 w3a3 CiM layer, batch 256",
-        "value": value,
-        "unit": "MAC/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": ms_per_step,
-        "ms_per_layer_fwd_bwd": ms_per_step / len(RESNET20),
-        "value_semantics": "logical MAC (B*P*O*K, flops_counter.py:314-318) of the 19 convs per fwd+bwd+SGD "
-                           "step / step time; the forward-only rate SURVEY 8(d) defines is fwd_only.value",
+    result.update({
         "fwd_only": {"value": macs_step / (fwd_elapsed / args.steps), "unit": "MAC/s",
                      "ms_per_forward": fwd_elapsed / args.steps * 1e3},
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "i8+f32",
-        "data": "synthetic (random-init weights, randn / relu(randn) activations of the layer shapes)",
-        "config": {"workload": "resnet20_w3a3_all_19_cim_convs_fwd_bwd_sgd", "global_batch": args.batch * world,
-                   "per_gpu_batch": args.batch, "xbar": XBAR, "adc_bits": ADC, "first_layer": "w8a8",
-                   "parallelism": f"dp{world}", "grad_bucket_mb": round(tr.bucket_mb, 3), "exchange_segments": len(tr.segments),
-                   "launch": "hip_graph" if graph else "eager", "recompute_psum": RECOMPUTE},
         "roofline": dict(roof, kernel=_lib.KERNEL_SYMBOLS[_lib.KERNEL_IDS[dominant]] + " (every instantiation the "
                          "19 layers launch)", avg_launch_us=kt.total_ms / nl * 1e3, pmc_source=pmc_source),
-        "peak_mem_mb": round(peak_mb, 1),
         "kernel_ms_per_step": {k: round(v, 4) for k, v in per_kernel.items()},
         "layer_fwd_bwd_ms": breakdown,
         "rates": step_context(args.batch, world, ms_per_step, fwd_elapsed / args.steps * 1e3),
-    }
+    })
     if world == 1 and not args.no_peaks:
         result["peaks_measured"] = measured_peaks(dev)
     if world == 1 and not args.no_cfg5:
@@ -685,10 +758,7 @@ def main():
         result["extra_configs"] = ex
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args.cpu_batch, min(16, os.cpu_count() or 1))
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    return result
 
 
 if __name__ == "__main__":

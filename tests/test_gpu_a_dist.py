@@ -201,7 +201,7 @@ def test_bench_world2_branch_gloo(gpu_present):
     env = dict(os.environ, CIMQ_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps",
-           "2", "--warmup", "1", "--batch", "16", "--no-cfg5", "--no-cpu-baseline"]
+           "2", "--warmup", "1", "--batch", "16", "--full", "--no-cfg5", "--no-cpu-baseline"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]

@@ -13,7 +13,7 @@ else
 fi
 tail -3 $O/gpu_tests.log
 timeout -k 10 300 python -c "import __graft_entry__ as e; e.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
-timeout -k 10 300 python bench.py --no-cpu-baseline --no-cfg5 --no-peaks > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-cfg5 --no-peaks > $O/bench.json 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o p -- python bench.py --steps 10 --no-cpu-baseline --no-cfg5 --no-peaks > $O/bench_under_rocprof.json 2> $O/rocprof.err || exit 1
 python tools/step_breakdown.py $O/kt/p_kernel_trace.csv > $O/step_breakdown.txt
 rm -f $O/kt/p_kernel_trace.csv
