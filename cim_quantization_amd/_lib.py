@@ -13,7 +13,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CIMQ_LIB_PATH") or os.path.join(_HERE, "libcimq.so")
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 CIMQ_EINVAL = 1  # include/cimq.h error codes
 CIMQ_EUNSUPPORTED = 2
@@ -21,8 +21,10 @@ CIMQ_EHIP = 3
 CIMQ_INPUT_XQ = 0
 CIMQ_INPUT_RAW_LSQ = 1
 # cimq_module_route codes (include/cimq.h CIMQ_ROUTE_*)
-ROUTE_NAMES = {0: "general", 1: "v3", 2: "fwd5", 3: "v7", 4: "fused", 5: "c1", 6: "gx5", 7: "gw5", 8: "dense", 9: "r6"}
+ROUTE_NAMES = {0: "general", 1: "v3", 2: "fwd5", 3: "v7", 4: "fused", 5: "c1", 6: "gx5", 7: "gw5", 8: "dense", 9: "r6",
+               10: "none"}
 CIMQ_ROUTE_R6 = 9
+CIMQ_ROUTE_NONE = 10  # route[1] / route[2] under CIMQ_OPT_INFERENCE (ABI 15)
 CIMQ_LSQ_ACCUMULATE_GRADS = 1
 CIMQ_LSQ_SKIP_TAIL = 2
 CIMQ_LSQ_DEFER_GW = 4
@@ -34,6 +36,7 @@ CIMQ_ADC_SHIFT_SIGN = 3
 CIMQ_ADC_F_PS_INT8 = 0x100
 CIMQ_ADC_F_SHIFT_RANGE = 0x200
 CIMQ_OPT_RECOMPUTE = 1  # cimq_conv_desc.options (ABI 14)
+CIMQ_OPT_INFERENCE = 4  # forward only: nothing written that a backward would read (ABI 15; bit 2 is refused)
 
 # every symbol include/cimq.h declares
 EXPORTED_SYMBOLS = (

@@ -19,7 +19,8 @@ import torch.nn.functional as F
 
 from ..functional import (alpha_cim_init, cim_conv2d_lsq, cim_conv2d_lsq_shift, cim_module_conv,  # noqa: F401
                           cim_module_shift_conv, get_adcless_cim_output, get_analog_partial_sums_autograd_ver2,
-                          get_cim_output_signed, lsq_quantize, module_shift_supported, qconv2d)
+                          get_cim_output_signed, inference_call, inference_weights, lsq_quantize,
+                          module_shift_supported, qconv2d)
 from ._quan_base import (_ActQ, _Conv2dQ, _Conv2dQCiM, _LinearQ, Qmodes, grad_scale,  # noqa: F401
                          round_pass)
 
@@ -47,7 +48,16 @@ class Conv2dLSQCiM(_Conv2dQCiM):
     reference): a learnable per-(tile, w-slice, a-slice, channel) shift ``beta_cim`` next to
     ``alpha_cim``, and the ADC of test/test_backward_cimlayer_scale_shift.py on the rescaled
     partial sum u -- adcbits 1.5: clamp(round((u-beta)/alpha_q), -1, 1)*alpha_q + beta (ver2);
-    adcbits 1: sign((u-beta)/alpha_q)*alpha_q + beta (adcless).  beta starts at 0."""
+    adcbits 1: sign((u-beta)/alpha_q)*alpha_q + beta (adcless).  beta starts at 0.
+
+    Evaluation: a forward under ``torch.no_grad()`` (or one no input of which requires a gradient) runs
+    the library's forward-only mode -- the same output bit for bit, no backward state, nothing saved.
+    On the fused library-ADC path the layer then keeps the weight side it prepared (``_inf_prep``) and
+    reuses it while the input shape and the parameters' versions and addresses are unchanged, so a whole
+    evaluation quantises the weights once per input shape.  ``train(True)`` and ``load_state_dict`` drop
+    it, a call made with grad enabled never reads it, and stochastic-ADC layers keep none.  An edit
+    through ``p.data`` bumps no version counter (functional._versions): after one, call ``train()`` /
+    ``eval()`` again or torch.autograd.graph.increment_version(p) before the next evaluation."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1,
                  groups=1, bias=True, nbits_w=8, nbits_a=8, nbits_alpha=8, wbitslice=1, abitslice=1,
@@ -74,6 +84,7 @@ class Conv2dLSQCiM(_Conv2dQCiM):
         # recompute the partial sums in the backward -- slower on MI355X, so off by default
         self.recompute_psum = False
         self._wprep = None        # functional.prepare_weights: the next forward's weight side, computed ahead
+        self._inf_prep = None     # functional.inference_weights: the weight side the no-grad forwards share
         self._last_x_shape = None
 
     def _fused_ready(self):
@@ -95,7 +106,13 @@ class Conv2dLSQCiM(_Conv2dQCiM):
 
     def _load_from_state_dict(self, *args, **kwargs):
         self._state_cache = None
+        self._inf_prep = None
         return super()._load_from_state_dict(*args, **kwargs)
+
+    def train(self, mode=True):
+        if mode:
+            self._inf_prep = None
+        return super().train(mode)
 
     def _init_flags(self):
         key = (self.init_state._version, self.init_state_cim._version)
@@ -132,6 +149,10 @@ class Conv2dLSQCiM(_Conv2dQCiM):
             # weight side possibly prepared ahead by prepare_weights; taken once)
             wprep, self._wprep = self._wprep, None
             self._last_x_shape = tuple(x.shape)
+            if (not torch.is_grad_enabled() and not self.stochastic_quant and x.is_cuda and
+                    inference_call(x, self.weight, self.alpha_act, self.alpha_weight, self.alpha_cim)):
+                # evaluation: the forward-only weight side, made once and kept while it matches
+                wprep = self._inf_prep = inference_weights(self, x.shape, self._inf_prep)
             out = cim_module_conv(x, self.weight, self.alpha_act, self.alpha_weight, self.alpha_cim,
                                   self.binary_mask, self.signed_act, self.stride, self.padding, self.dilation,
                                   self.nbits_a, self.abitslice, self.nbits_w, self.wbitslice, self.adcbits,

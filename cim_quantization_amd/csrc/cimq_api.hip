@@ -9,18 +9,29 @@ using namespace cimq;
 
 namespace {
 
+// the entry points with no forward-only form refuse CIMQ_OPT_INFERENCE before they look at any other argument
+int refuse_inference(const cimq_conv_desc* d, const char* who) {
+  if (d && (d->options & CIMQ_OPT_INFERENCE))
+    return fail(CIMQ_EINVAL, "%s: CIMQ_OPT_INFERENCE descriptors are forward only (cimq_forward, cimq_module_forward, "
+                             "cimq_module_shift_forward, cimq_module_prepare)", who);
+  return CIMQ_OK;
+}
+
 int prep_all(const Geo& g, const float* x, const float* w_q, const float* sa, const float* sw,
              const float* alpha_q, const int8_t* bmask, const float* signed_act, uint8_t* ctx,
              hipStream_t s, bool need_params, bool need_wgx, const float* beta = nullptr) {
   CtxLayout L = ctx_layout(g);
   const int blk = 256;
-  {
+  if (!inf_actq(g)) {  // (there the forward's row staging quantises, and the ctx has no slice words)
     // one 4-element item per thread up to 8192 blocks (fewer, fatter blocks measured slower)
     int grid = cdiv(g.Nin, 4 * blk);
     if (grid > act_blocks()) grid = act_blocks();
     const int slot = prof_begin(KID_PREP_ACT, g, s);
-    hipLaunchKernelGGL(prep_act_kernel, dim3(grid), dim3(blk), 0, s, g, x, sa, signed_act,
-                       ctx + L.xcode, ctx + L.xhat);
+    if (g.inference)  // forward only: the forward slice words alone (the ctx has no backward words)
+      hipLaunchKernelGGL(prep_act_fwd_kernel, dim3(grid), dim3(blk), 0, s, g, x, sa, signed_act, ctx + L.xcode);
+    else
+      hipLaunchKernelGGL(prep_act_kernel, dim3(grid), dim3(blk), 0, s, g, x, sa, signed_act,
+                         ctx + L.xcode, ctx + L.xhat);
     prof_end(slot, s);
     CIMQ_TRY(check_hip("prep_act"));
   }
@@ -163,7 +174,7 @@ int cimq_query_sizes(const cimq_conv_desc* d, cimq_sizes* out) {
   out->wprep_bytes = ctx_layout(g).wbytes;
   WsLayout W = ws_layout(g);
   out->fwd_workspace_bytes = W.total;
-  out->bwd_workspace_bytes = W.total;
+  out->bwd_workspace_bytes = g.inference ? 0 : W.total;  // (forward only: there is no backward)
   Geo gm = g;
   gm.onchw = 1;  // the module entry points' layout: no state words where their backward recomputes
   out->module_ctx_bytes = ctx_layout(gm).total;
@@ -184,13 +195,17 @@ int cimq_forward(const cimq_conv_desc* d, const float* x, const float* w_q, cons
   (void)ws;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   uint8_t* c = reinterpret_cast<uint8_t*>(ctx);
-  CIMQ_TRY(prep_all(g, x, w_q, sa, sw, alpha_q, binary_mask, signed_act, c, s, true, true));
-  return launch_fwd_any(g, c, sw, sa, out, nullptr, nullptr, s);
+  // forward only (CIMQ_OPT_INFERENCE): no backward weight operands; the activation quantiser in the forward's
+  // row staging where that applies (inf_actq: the same words, bit for bit, without the pass over x)
+  CIMQ_TRY(prep_all(g, x, w_q, sa, sw, alpha_q, binary_mask, signed_act, c, s, true, !g.inference));
+  const ActQ aq{x, signed_act};
+  return launch_fwd_any(g, c, sw, sa, out, nullptr, nullptr, s, inf_actq(g) ? &aq : nullptr);
 }
 
 int cimq_shift_forward(const cimq_conv_desc* d, const float* x, const float* w_q, const float* sa,
                        const float* sw, const float* alpha, const float* beta, const int8_t* binary_mask,
                        const float* signed_act, float* out, void* ctx, void* ws, void* stream) {
+  CIMQ_TRY(refuse_inference(d, "cimq_shift_forward"));
   Geo g;
   CIMQ_TRY(make_geo(d, &g));
   if (g.variant != VAR_SHIFT_ROUND && g.variant != VAR_SHIFT_SIGN)
@@ -208,6 +223,7 @@ int cimq_shift_backward(const cimq_conv_desc* d, const float* grad_out, const fl
                         const float* sw, const float* alpha, const float* beta, const int8_t* binary_mask,
                         const float* signed_act, const void* ctx, float* grad_x, float* grad_w,
                         float* grad_alpha, float* grad_beta, float* grad_sa, void* ws, void* stream) {
+  CIMQ_TRY(refuse_inference(d, "cimq_shift_backward"));
   Geo g;
   CIMQ_TRY(make_geo(d, &g));
   (void)alpha; (void)beta;
@@ -270,6 +286,7 @@ int cimq_debug_partial_sums(const cimq_conv_desc* d, const float* x, const float
                             const float* sw, const float* alpha_q, const int8_t* binary_mask,
                             const float* signed_act, float* out, int32_t* ps_out, float* adc_out, void* ctx,
                             void* stream) {
+  CIMQ_TRY(refuse_inference(d, "cimq_debug_partial_sums"));
   Geo g;
   CIMQ_TRY(make_geo(d, &g));
   if (!x || !w_q || !sa || !sw || !binary_mask || !signed_act || !out || !ps_out || !adc_out || !ctx)
@@ -284,6 +301,7 @@ int cimq_debug_partial_sums(const cimq_conv_desc* d, const float* x, const float
 
 int cimq_debug_state_codes(const cimq_conv_desc* d, const void* ctx, int8_t* code_out, uint8_t* pass_out,
                            void* stream) {
+  CIMQ_TRY(refuse_inference(d, "cimq_debug_state_codes"));
   Geo g;
   CIMQ_TRY(make_geo(d, &g));
   if (!ctx || !code_out || !pass_out) return fail(CIMQ_EINVAL, "null pointer argument");
@@ -299,6 +317,7 @@ int cimq_debug_state_codes(const cimq_conv_desc* d, const void* ctx, int8_t* cod
 
 int cimq_debug_recompute_codes(const cimq_conv_desc* d, const float* x, const float* signed_act, const void* ctx,
                                void* st_scratch, int8_t* code_out, uint8_t* pass_out, void* stream) {
+  CIMQ_TRY(refuse_inference(d, "cimq_debug_recompute_codes"));
   Geo g;
   CIMQ_TRY(make_geo(d, &g));
   if (!x || !signed_act || !ctx || !st_scratch || !code_out || !pass_out) return fail(CIMQ_EINVAL, "null pointer argument");
@@ -319,6 +338,7 @@ int cimq_backward(const cimq_conv_desc* d, const float* grad_out, const float* x
                   const float* sw, const float* alpha_q, const int8_t* binary_mask,
                   const float* signed_act, const void* ctx, float* grad_x, float* grad_w,
                   float* grad_alpha, float* grad_sa, void* ws, void* stream) {
+  CIMQ_TRY(refuse_inference(d, "cimq_backward"));
   Geo g;
   CIMQ_TRY(make_geo(d, &g));
   (void)alpha_q; (void)binary_mask;
@@ -570,6 +590,10 @@ static ModulePrep module_prep_args(const Geo& g, const float* x, const float* we
   a.wx6 = reinterpret_cast<v4i*>(wr + L.wx6);
   a.nwx6 = (int)(r6_frag_bytes(g) / 16);  // cim_bwd_r6_kernel's gx operand
   a.npp = g.T * g.nba * g.nbw * g.Opad + g.nbw * g.nba;
+  if (g.inference) {  // forward only: no backward words, none of the backward-only weight roles
+    a.xcb = nullptr;
+    a.nwg = a.nwc = a.nwx5 = a.nwx6 = 0;
+  }
   *nwblk = std::max(1, std::min(cdiv(a.nwf + a.nwg + a.nwc + a.nw5 + a.nwx5 + a.nwx6 + a.npp, 256), 1024));
   return a;
 }
@@ -629,7 +653,10 @@ static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
       aw.amm = part;
       aw.namm = 64;
     }
-    hipLaunchKernelGGL(prep_module_kernel, dim3(a.nact_blocks + nwblk), dim3(256), 0, s, g, la, aw);
+    if (g.inference)
+      hipLaunchKernelGGL(prep_module_fwd_kernel, dim3(a.nact_blocks + nwblk), dim3(256), 0, s, g, la, aw);
+    else
+      hipLaunchKernelGGL(prep_module_kernel, dim3(a.nact_blocks + nwblk), dim3(256), 0, s, g, la, aw);
     prof_end(slot, s);
     CIMQ_TRY(check_hip("prep_module"));
     }
@@ -686,6 +713,10 @@ int cimq_module_route(const cimq_conv_desc* d, int* route) {
   } else if (dense_plan(g)) {
     route[0] = CIMQ_ROUTE_DENSE;
   }
+  if (g.inference) {  // forward only: there is no backward
+    route[1] = route[2] = CIMQ_ROUTE_NONE;
+    return CIMQ_OK;
+  }
   // backward (dispatch_bwd_any)
   if (v7_bwd(g)) {
     if (r6_bwd(g)) {
@@ -726,6 +757,7 @@ static int module_backward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q,
                                 const float* signed_act, const void* ctx, float* grad_x, float* grad_weight,
                                 float* grad_alpha_act, float* grad_alpha_weight, float* grad_alpha_cim, void* ws,
                                 Pending* pend, void* stream) {
+  CIMQ_TRY(refuse_inference(d, "cimq_module_backward"));
   Geo g;
   LsqArgs la;
   CIMQ_TRY(module_geo(d, q, &g, &la));
@@ -811,6 +843,7 @@ int cimq_module_backward_chain(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
                                const float* signed_act, const void* ctx, float* grad_x, float* grad_weight,
                                float* grad_alpha_act, float* grad_alpha_weight, float* grad_alpha_cim, void* ws,
                                cimq_pending* pending, void* stream) {
+  CIMQ_TRY(refuse_inference(d, "cimq_module_backward_chain"));
   if (!pending) return fail(CIMQ_EINVAL, "null cimq_pending");
   Pending* pd = reinterpret_cast<Pending*>(pending);
   if (pd->magic != 0 && pd->magic != kPendingMagic) return fail(CIMQ_EINVAL, "cimq_pending not initialised (zero it)");
@@ -836,6 +869,7 @@ int cimq_pending_flush(cimq_pending* pending, void* stream) {
 int cimq_module_backward_tail(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* weight,
                               const float* alpha_cim, const void* ctx, float* grad_weight, float* grad_alpha_act,
                               float* grad_alpha_weight, float* grad_alpha_cim, void* ws, void* stream) {
+  CIMQ_TRY(refuse_inference(d, "cimq_module_backward_tail"));
   Geo g;
   LsqArgs la;
   CIMQ_TRY(module_geo(d, q, &g, &la));
@@ -854,6 +888,7 @@ int cimq_module_backward_params(const cimq_conv_desc* d, const cimq_lsq_desc* q,
                                 const float* weight, const float* alpha_cim, const void* ctx, float* grad_weight,
                                 float* grad_alpha_act, float* grad_alpha_weight, float* grad_alpha_cim, void* ws,
                                 void* stream) {
+  CIMQ_TRY(refuse_inference(d, "cimq_module_backward_params"));
   Geo g;
   LsqArgs la;
   CIMQ_TRY(module_geo(d, q, &g, &la));
@@ -884,6 +919,7 @@ int cimq_module_shift_backward(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
                                const int8_t* binary_mask, const float* signed_act, const void* ctx, float* grad_x,
                                float* grad_weight, float* grad_alpha_act, float* grad_alpha_weight,
                                float* grad_alpha_cim, float* grad_beta_cim, void* ws, void* stream) {
+  CIMQ_TRY(refuse_inference(d, "cimq_module_shift_backward"));
   Geo g;
   LsqArgs la;
   CIMQ_TRY(module_geo(d, q, &g, &la, true));
@@ -957,6 +993,7 @@ int cimq_module_prepare(int n, const cimq_prepare_item* items, void* stream) {
 int cimq_alpha_init(const cimq_conv_desc* d, const float* x, const float* w_q, const float* sa,
                     const float* sw, const int8_t* binary_mask, const float* signed_act,
                     float* alpha_init, void* ctx, void* ws, void* stream) {
+  CIMQ_TRY(refuse_inference(d, "cimq_alpha_init"));
   Geo g;
   CIMQ_TRY(make_geo(d, &g));
   if (!x || !w_q || !sa || !sw || !binary_mask || !signed_act || !alpha_init || !ctx || !ws)

@@ -41,10 +41,14 @@ struct Geo {
   int onchw;               // out / grad_out layout: 0 = [B, P, O] (the Function's), 1 = NCHW (the module's)
   int variant;             // AdcVariant; anything but VAR_LIBRARY runs the literal (general) kernels
   int ps_int8;             // partial sums pass an int8 buffer before the ADC (scale_shift.py:401)
-  int recompute;           // cimq_conv_desc.options & CIMQ_OPT_RECOMPUTE: the module backward recomputes partial sums
+  // host side, cimq_conv_desc.options (two halves of what was one int, so that the struct every kernel takes by
+  // value keeps its size and its offsets): CIMQ_OPT_RECOMPUTE -- the module backward recomputes partial sums --
+  // and CIMQ_OPT_INFERENCE -- forward only, nothing written that a backward would read
+  short recompute, inference;
   uint32_t seed_lo, seed_hi;  // VAR_STOCHASTIC: Philox key
   const unsigned char* wbase;  // host side: the weight-side ctx regions (cimq_lsq_desc.wprep); null: inside ctx
 };
+static_assert(sizeof(Geo) == 200, "Geo is every kernel's first argument: keep its size and offsets");
 
 // Per-(tile i, a-slice j, w-slice k, out-channel o) ADC / STE parameters, SoA.
 // index: ((i*nba + j)*nbw + k)*Opad + o

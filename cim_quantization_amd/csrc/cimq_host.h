@@ -148,7 +148,11 @@ inline int make_geo(const cimq_conv_desc* d, Geo* out) {
   g.ps_int8 = (d->adc_variant & CIMQ_ADC_F_PS_INT8) ? 1 : 0;
   g.seed_lo = d->seed_lo;
   g.seed_hi = d->seed_hi;
-  if (d->options & ~CIMQ_OPT_RECOMPUTE) return fail(CIMQ_EINVAL, "unknown options 0x%x", d->options);
+  if (d->options & ~(CIMQ_OPT_RECOMPUTE | CIMQ_OPT_INFERENCE))
+    return fail(CIMQ_EINVAL, "unknown options 0x%x", d->options);
+  g.inference = (d->options & CIMQ_OPT_INFERENCE) ? 1 : 0;
+  // (with CIMQ_OPT_INFERENCE the recompute bit changes nothing that runs: it only keeps the weight-side
+  // layout, and so wprep_bytes, what it is without the inference bit)
   g.recompute = (d->options & CIMQ_OPT_RECOMPUTE) ? 1 : 0;
   switch (g.variant) {
     case VAR_LIBRARY: break;
@@ -194,6 +198,12 @@ inline size_t f5_frag_bytes(const Geo& g);  // after f5_plan
 inline size_t x5_frag_bytes(const Geo& g);  // after x5_plan
 inline size_t r6_frag_bytes(const Geo& g);  // after r6_plan
 inline bool r6_bwd(const Geo& g);           // after r6_plan
+inline bool fwd_actq_ok(const Geo& g);      // after v7_plan
+
+// A forward-only call (CIMQ_OPT_INFERENCE) whose forward kernel quantises the activation in its own row staging
+// (stage_rows_q / cim_fwd5_kernel): no prologue pass over x, no slice words in the ctx.  The module entry points'
+// fwd_actq_ok layers, and the same shapes through cimq_forward (cim_fwd_v3_kernel with [B, P, O] output).
+inline bool inf_actq(const Geo& g) { return g.inference && fwd_actq_ok(g); }
 
 inline CtxLayout ctx_layout_compute(const Geo& g) {
   CtxLayout L;
@@ -217,7 +227,13 @@ inline CtxLayout ctx_layout_compute(const Geo& g) {
   L.flags = o; o = align256(o + 16);
   L.lsq_scal = o; o = align256(o + 16 * 4);
   L.wbytes = o;
-  L.xcode = o; o = align256(o + (size_t)g.Nin * g.NBP);  // forward slice bytes
+  L.xcode = o; o = align256(o + (inf_actq(g) ? (size_t)0 : (size_t)g.Nin * g.NBP));  // forward slice bytes
+  if (g.inference) {
+    // forward only (CIMQ_OPT_INFERENCE): the ctx ends here -- no backward slice words, no code table, no state;
+    // their offsets point at the end and nothing is written through them
+    L.xhat = L.alut = L.st = L.total = o;
+    return L;
+  }
   L.xhat = o; o = align256(o + (size_t)g.Nin * g.NBP);   // backward (int8 ctx) slice bytes
   L.alut = o; o = align256(o + (size_t)4 * 301);         // ctx codes: code -> ctx word (ctx_codes), format word 300
   // per-partial-sum state words written by the fast forward (cimq_kernels_v3.hip: StWord)
@@ -956,7 +972,7 @@ inline PlanR6 r6_plan(const Geo& g) { return memo_geo<PlanR6, r6_plan_compute>(g
 inline size_t r6_frag_bytes(const Geo& g) { return r6_plan(g).ok ? (size_t)kR6WxItems * 16 : 0; }
 // decided at launch: the module entry points (g.onchw) run cim_fwd5_kernel, whose operand the recompute needs; the
 // Function path's forward writes state words and keeps the state-word backward
-inline bool r6_bwd(const Geo& g) { return g.onchw && r6_plan(g).ok; }
+inline bool r6_bwd(const Geo& g) { return g.onchw && !g.inference && r6_plan(g).ok; }
 
 // The module path's ctx as ONE activation-code byte per element (instead of the 4-byte backward word):
 // where the forward is cim_fwd5_kernel (which quantises the activation itself) and the layer's grad_w
@@ -994,6 +1010,16 @@ inline WsLayout ws_layout_compute(const Geo& g) {
   // (sizes for either backward of a layer: the module path's recompute backward has one chunk per image)
   const size_t nch = (size_t)std::max({W.nchunks, W.nchunks_bwd, r6_plan(g).ok ? g.B : 0});
   size_t o = 0;
+  if (g.inference) {
+    // forward only (CIMQ_OPT_INFERENCE): the prologue's alpha_cim max / min partials (lsq_part), and the
+    // general kernels' [B, P, O] staging copy of out where the module forward runs them; no backward slabs
+    W.gw_slab = W.ga_slab = W.gb_slab = W.ss_slab = W.qtab = 0;
+    W.lsq_part = o; o = align256(o + sizeof(float) * std::max(kLsqParts, g.B * g.H));
+    W.gaq = W.gapart = W.wpart = o;
+    W.bpo = o; o = align256(o + ((v3_plan(g).ok || dense_plan(g)) ? (size_t)0 : sizeof(float) * (size_t)g.M * g.O));
+    W.gxu = W.total = o;
+    return W;
+  }
   W.gw_slab = o; o = align256(o + sizeof(float) * nch * g.T * g.FBT * 16 * g.Opad);
   W.ga_slab = o; o = align256(o + sizeof(float) * nch * g.T * g.nbw * g.nba * g.Opad);
   W.gb_slab = o; o = align256(o + (g.variant == VAR_SHIFT_ROUND || g.variant == VAR_SHIFT_SIGN

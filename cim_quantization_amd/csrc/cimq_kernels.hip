@@ -42,6 +42,9 @@ __device__ inline void pack_word(int8_t (&v)[8], int nbp, uint8_t* dst, long lon
   }
 }
 
+// WB (here and in the helpers below): also write the backward (ctx) words to xcb; false for the forward-only
+// prologues (CIMQ_OPT_INFERENCE), whose ctx has no such region
+template <bool WB = true>
 __device__ inline void act_item(const Geo& g, const float* __restrict__ x, float sa, bool sgn,
                                 uint8_t* __restrict__ xcf, uint8_t* __restrict__ xcb, long long idx) {
   float v = x[idx];
@@ -69,7 +72,7 @@ __device__ inline void act_item(const Geo& g, const float* __restrict__ x, float
     bw[j] = (j < g.nba) ? (int8_t)clamp_i8(sb) : (int8_t)0;
   }
   pack_word(fw, g.NBP, xcf, idx);
-  pack_word(bw, g.NBP, xcb, idx);
+  if constexpr (WB) pack_word(bw, g.NBP, xcb, idx);
 }
 
 // Slice words of one element, NBP-specialised.  When x_int is an exact integer (the common
@@ -184,7 +187,7 @@ __device__ inline void act_words_lut(const Geo& g, float v, float sa, bool sgn, 
 }
 
 // four consecutive elements (idx4 = 4 * t): one 16-B load, 16-B (NBP 4) or 2 x 16-B stores
-template <int NBP, int NBA_C = 0>
+template <int NBP, int NBA_C = 0, bool WB = true>
 __device__ inline void act_item4(const Geo& g, const float* __restrict__ x, float sa, bool sgn,
                                  uint8_t* __restrict__ xcf, uint8_t* __restrict__ xcb, long long t,
                                  const uint32_t* lut = nullptr) {
@@ -200,28 +203,31 @@ __device__ inline void act_item4(const Geo& g, const float* __restrict__ x, floa
   }
   if (NBP == 4) {
     reinterpret_cast<uint4*>(xcf)[t] = make_uint4(f[0][0], f[1][0], f[2][0], f[3][0]);
-    reinterpret_cast<uint4*>(xcb)[t] = make_uint4(b[0][0], b[1][0], b[2][0], b[3][0]);
+    if constexpr (WB) reinterpret_cast<uint4*>(xcb)[t] = make_uint4(b[0][0], b[1][0], b[2][0], b[3][0]);
   } else {
     reinterpret_cast<uint4*>(xcf)[2 * t] = make_uint4(f[0][0], f[0][NBP / 4 - 1], f[1][0], f[1][NBP / 4 - 1]);
     reinterpret_cast<uint4*>(xcf)[2 * t + 1] = make_uint4(f[2][0], f[2][NBP / 4 - 1], f[3][0], f[3][NBP / 4 - 1]);
-    reinterpret_cast<uint4*>(xcb)[2 * t] = make_uint4(b[0][0], b[0][NBP / 4 - 1], b[1][0], b[1][NBP / 4 - 1]);
-    reinterpret_cast<uint4*>(xcb)[2 * t + 1] = make_uint4(b[2][0], b[2][NBP / 4 - 1], b[3][0], b[3][NBP / 4 - 1]);
+    if constexpr (WB) {
+      reinterpret_cast<uint4*>(xcb)[2 * t] = make_uint4(b[0][0], b[0][NBP / 4 - 1], b[1][0], b[1][NBP / 4 - 1]);
+      reinterpret_cast<uint4*>(xcb)[2 * t + 1] = make_uint4(b[2][0], b[2][NBP / 4 - 1], b[3][0], b[3][NBP / 4 - 1]);
+    }
   }
 }
 
 // all elements of x: vectorised when Nin % 4 == 0 (W % 4 == 0), element-wise otherwise
-template <int NBP, int NBA_C>
+template <int NBP, int NBA_C, bool WB = true>
 __device__ inline void act_range_sel(const Geo& g, const float* __restrict__ x, float sa, bool sgn,
                                      uint8_t* __restrict__ xcf, uint8_t* __restrict__ xcb, long long first,
                                      long long step, uint32_t* lut) {
   const long long n4 = g.Nin / 4;
   const bool tab = lut && g.input_kind == 1 && g.lsq_qp >= 0.f && g.lsq_qp < (float)kActLutMax;
   if (tab) act_lut_build<NBP, NBA_C>(g, sa, sgn, lut);  // block-uniform condition: every thread syncs
-  for (long long t = first; t < n4; t += step) act_item4<NBP, NBA_C>(g, x, sa, sgn, xcf, xcb, t, tab ? lut : nullptr);
+  for (long long t = first; t < n4; t += step) act_item4<NBP, NBA_C, WB>(g, x, sa, sgn, xcf, xcb, t, tab ? lut : nullptr);
 }
 
 // lut: LDS for the RAW_LSQ word table (kActLutMax * NBP / 2 words), or null; called by every
 // thread of the block
+template <bool WB = true>
 __device__ inline void act_range(const Geo& g, const float* __restrict__ x, float sa, bool sgn,
                                  uint8_t* __restrict__ xcf, uint8_t* __restrict__ xcb, long long first,
                                  long long step, uint32_t* lut = nullptr) {
@@ -230,19 +236,19 @@ __device__ inline void act_range(const Geo& g, const float* __restrict__ x, floa
     // the 1-bit-slice cases of the CIFAR / QuantLinear configs with compile-time digit loops
     const int sel = g.bsa != 1 ? 0 : g.nba;
     if (sel == 3)
-      act_range_sel<4, 3>(g, x, sa, sgn, xcf, xcb, first, step, lut);
+      act_range_sel<4, 3, WB>(g, x, sa, sgn, xcf, xcb, first, step, lut);
     else if (sel == 2)
-      act_range_sel<4, 2>(g, x, sa, sgn, xcf, xcb, first, step, lut);
+      act_range_sel<4, 2, WB>(g, x, sa, sgn, xcf, xcb, first, step, lut);
     else if (sel == 4)
-      act_range_sel<4, 4>(g, x, sa, sgn, xcf, xcb, first, step, lut);
+      act_range_sel<4, 4, WB>(g, x, sa, sgn, xcf, xcb, first, step, lut);
     else if (sel == 8)
-      act_range_sel<8, 8>(g, x, sa, sgn, xcf, xcb, first, step, lut);
+      act_range_sel<8, 8, WB>(g, x, sa, sgn, xcf, xcb, first, step, lut);
     else if (g.NBP == 4)
-      for (long long t = first; t < n4; t += step) act_item4<4>(g, x, sa, sgn, xcf, xcb, t);
+      for (long long t = first; t < n4; t += step) act_item4<4, 0, WB>(g, x, sa, sgn, xcf, xcb, t);
     else
-      for (long long t = first; t < n4; t += step) act_item4<8>(g, x, sa, sgn, xcf, xcb, t);
+      for (long long t = first; t < n4; t += step) act_item4<8, 0, WB>(g, x, sa, sgn, xcf, xcb, t);
   } else {
-    for (long long idx = first; idx < g.Nin; idx += step) act_item(g, x, sa, sgn, xcf, xcb, idx);
+    for (long long idx = first; idx < g.Nin; idx += step) act_item<WB>(g, x, sa, sgn, xcf, xcb, idx);
   }
 }
 
@@ -254,6 +260,14 @@ __global__ void prep_act_kernel(Geo g, const float* __restrict__ x, const float*
   const bool sgn = (*signed_p) != 0.f;
   act_range(g, x, sa, sgn, xcf, xcb, (long long)blockIdx.x * blockDim.x + threadIdx.x,
             (long long)gridDim.x * blockDim.x);
+}
+// the forward-only prologue (CIMQ_OPT_INFERENCE): the forward slice words alone
+__global__ void prep_act_fwd_kernel(Geo g, const float* __restrict__ x, const float* __restrict__ sa_p,
+                                    const float* __restrict__ signed_p, uint8_t* __restrict__ xcf) {
+  const float sa = *sa_p;
+  const bool sgn = (*signed_p) != 0.f;
+  act_range<false>(g, x, sa, sgn, xcf, nullptr, (long long)blockIdx.x * blockDim.x + threadIdx.x,
+                   (long long)gridDim.x * blockDim.x);
 }
 #endif
 

@@ -143,6 +143,8 @@ __device__ inline void act_lut_build_q(const Geo& g, float sa, bool sgn, uint32_
   }
   act_lut_build<4, NBA_C>(g, sa, sgn, lut);  // entries 0 .. Qp, then the block barrier
 }
+// WCB false (forward only): no backward words at all, xcb is not read
+template <bool WCB = true>
 __device__ inline void stage_rows_q(const Geo& g, int WP, int RHx, const float* __restrict__ x, float sa,
                                     const uint32_t* lut, int b, int ih_first, uint8_t* patch,
                                     uint8_t* __restrict__ xcb, int own_lo, int own_hi) {
@@ -187,6 +189,7 @@ __device__ inline void stage_rows_q(const Geo& g, int WP, int RHx, const float* 
       const uint2 w2 = act_words_tab(v[u].z, sa, g.lsq_qp, nan_e, lut);
       const uint2 w3 = act_words_tab(v[u].w, sa, g.lsq_qp, nan_e, lut);
       p[0] = w0.x; p[1] = w1.x; p[2] = w2.x; p[3] = w3.x;
+      if constexpr (!WCB) continue;
       if (ihs[u] >= own_lo && ihs[u] < own_hi)
         reinterpret_cast<uint4*>(xcb)[((img + (size_t)cs[u] * g.H + ihs[u]) * g.W >> 2) + qs[u]] =
             make_uint4(w0.y, w1.y, w2.y, w3.y);
@@ -370,9 +373,13 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
                                                          uint8_t* __restrict__ st, const float* __restrict__ xin,
                                                          const float* __restrict__ sgn_p, uint8_t* __restrict__ xcb) {
   // CSTA 9: the w8a8 fast path of CST 8 without the state words (cimq_c1.hip recomputes them)
+  // CSTA 12 / 13 / 18: CST 2 / 3 / 8 forward only (CIMQ_OPT_INFERENCE) -- no state words, none of their bits on
+  // either ADC path, and no backward words through xcb.  (CST 0 writes no state as it is.)  Encoded in CSTA so
+  // that the training instances keep their symbols and their code.
   // xin (module path, NBP 4): the activation quantiser fused into the row staging (stage_rows_q)
-  constexpr int CST = CSTA == 9 ? 8 : CSTA;
-  constexpr bool WST = CSTA != 9;
+  constexpr int CST = CSTA == 9 ? 8 : CSTA >= 10 ? CSTA - 10 : CSTA;
+  constexpr bool WST = CSTA < 9;
+  constexpr bool INF = CSTA >= 10;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int og = blockIdx.y;
   const int NOB = min(OBM, g.OB16);
@@ -535,7 +542,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
       const int own_lo = blockIdx.y == 0 ? oh0 * g.SH : 0;
       const int own_hi = blockIdx.y == 0 ? (p0 + 64 == g.P ? g.H : (oh0 + (64 >> v.lw)) * g.SH) : 0;
       if constexpr (NBP == 4)
-        stage_rows_q(g, v.WP, v.RH, xin, sa_q, alut, b, oh0 * g.SH - g.PH, patch, xcb, own_lo, own_hi);
+        stage_rows_q<!INF>(g, v.WP, v.RH, xin, sa_q, alut, b, oh0 * g.SH - g.PH, patch, xcb, own_lo, own_hi);
     } else {
       stage_rows<NBP>(g, v.WP, v.RH, xcf, b, oh0 * g.SH - g.PH, patch);
     }
@@ -719,6 +726,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
                     float a = hi ? cf : 0.f;
                     a = lo ? -cf : a;
                     acc[ob][r] += a;
+                    if constexpr (INF) continue;  // (forward only: no state bits)
                     const bool pass = (unsigned)(ps[r] - pv.z) <= (unsigned)pv.w;
                     if (PLF) {
                       tq[r][0] |= (pass ? 1u : 0u) << j;
@@ -734,6 +742,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
 #pragma unroll
                   for (int r = 0; r < 4; ++r) {
                     acc[ob][r] += shift_adc_literal(ps[r], sw, sa, al, be, mk);
+                    if constexpr (INF) continue;
                     const uint32_t sb = shift_state_literal(ps[r], sw, sa, al, be, g.thr_hi, g.thr_lo);
                     if (PLF) {
                       tq[r][0] |= (sb & 1u) << j;
@@ -750,6 +759,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
 #pragma unroll
                   for (int r = 0; r < 4; ++r) {
                     acc[ob][r] += adc_literal_sum(ps, g.mode, sw, sa, al, g.qn, g.qp, mk, r);
+                    if constexpr (INF) continue;
                     const bool pass = flag_lit ? (ste_literal(ps[r], g.mode, sw, sa, al, g.thr_hi, g.thr_lo) != 0.f)
                                                : ((unsigned)(ps[r] - pv.z) <= (unsigned)pv.w);
                     const float code =

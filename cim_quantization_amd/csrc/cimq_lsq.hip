@@ -167,6 +167,25 @@ __global__ __launch_bounds__(256) void prep_module_kernel(Geo g, LsqArgs q, Modu
   module_prep_weights(g, q, a, (int)blockIdx.x, nwblk, red);
 }
 
+// prep_module_kernel for a forward-only call (CIMQ_OPT_INFERENCE): the activation blocks write the forward slice
+// words alone (a.xcb is null: the ctx has no backward words), and the host left the backward-only weight roles
+// (nwg, nwc, nwx5, nwx6) empty
+__global__ __launch_bounds__(256) void prep_module_fwd_kernel(Geo g, LsqArgs q, ModulePrep a) {
+  __shared__ float4 red4[16];
+  float* red = reinterpret_cast<float*>(red4);
+  const int nwblk = (int)gridDim.x - a.nact_blocks;
+  if ((int)blockIdx.x >= nwblk) {
+    const float sa = grad_scale_value(a.alpha_act[0], q.gs_a);  // lsq.py:547-548
+    const int ab = (int)blockIdx.x - nwblk;
+    const bool sgn = a.signed_act[0] != 0.f;
+    __shared__ __attribute__((aligned(16))) uint32_t lut[kActLutMax * 4];  // the RAW_LSQ word table (act_range)
+    act_range<false>(g, a.x, sa, sgn, a.xcf, nullptr, (long long)ab * blockDim.x + threadIdx.x,
+                     (long long)a.nact_blocks * blockDim.x, lut);
+    return;
+  }
+  module_prep_weights(g, q, a, (int)blockIdx.x, nwblk, red);
+}
+
 // The job of block b in a packed launch: the number of job starts blk0[1 .. n-1] at or below b, counted
 // over the whole (fixed-size) table -- independent scalar loads of the kernel arguments and a compare
 // chain, instead of a search loop whose every step waits on the previous step's argument load

@@ -52,6 +52,23 @@ __device__ inline void adc_ps(int ps, int4 pv, float cf, float& acc, uint32_t& s
       : [ps] "v"(ps), [t] "v"(t), [thi] "v"(pv.x), [tlo] "v"(pv.y), [span] "v"(pv.w), [cf] "v"(cf));
 }
 
+// adc_ps without the state bits (the forward-only instances, CIMQ_OPT_INFERENCE): the same two compares, two
+// selects and one add, so acc is bit-identical.  As in adc_ps the first read of the MFMA result is compiler code
+// (the subtraction, an input the asm does not use), so the hazard recognizer pads it; and as there the masks
+// live in SGPRs only inside the block (the plain expression spills in the w4a4 instances).
+__device__ inline void adc_ps_out(int ps, int4 pv, float cf, float& acc) {
+  const int t = (int)((unsigned)ps - (unsigned)pv.z);
+  uint64_t mh, ml;
+  float a;
+  asm("v_cmp_ge_i32_e64 %[mh], %[ps], %[thi]\n\t"
+      "v_cmp_le_i32_e64 %[ml], %[ps], %[tlo]\n\t"
+      "v_cndmask_b32_e64 %[a], 0, %[cf], %[mh]\n\t"
+      "v_cndmask_b32_e64 %[a], %[a], -%[cf], %[ml]\n\t"
+      "v_add_f32_e32 %[acc], %[acc], %[a]"
+      : [mh] "=&s"(mh), [ml] "=&s"(ml), [a] "=&v"(a), [acc] "+v"(acc)
+      : [ps] "v"(ps), [t] "v"(t), [thi] "v"(pv.x), [tlo] "v"(pv.y), [cf] "v"(cf));
+}
+
 // bit b of a 16-bit plane -> bit 2b
 __device__ inline uint32_t spread16(uint32_t x) {
   x &= 0xFFFFu;
@@ -64,7 +81,8 @@ __device__ inline uint32_t spread16(uint32_t x) {
 // ---------------------------------------------------------------------------------------------
 // forward: block = 64 rows x 64 channels, wave w = rows 16w..16w+15 x four 16-channel blocks (in turn)
 // ---------------------------------------------------------------------------------------------
-template <int NBW, int NBA, int KS, bool LIT>
+// WST false (the forward-only instances): no state planes, none of their bits
+template <int NBW, int NBA, int KS, bool LIT, bool WST = true>
 __device__ inline void dense_fwd_body(const Geo& g, const uint8_t* __restrict__ xcf, const v4i* __restrict__ wfrag,
                                       const Params& pp, float sw, float sa, float* __restrict__ out,
                                       uint2* __restrict__ st, int4* prm, float* cfl, float4* accs, int m0,
@@ -153,7 +171,8 @@ __device__ inline void dense_fwd_body(const Geo& g, const uint8_t* __restrict__ 
 #ifdef CIMQ_EXP_DENSE_NOADC  // attribution builds only (tools/kernel_experiment.py): wrong results
               acc[r] += (float)ps[j][r] * cf + (float)pv.x;
 #else
-              adc_ps(ps[j][r], pv, cf, acc[r], sp[r], sz[r], sn[r]);
+              if constexpr (WST) adc_ps(ps[j][r], pv, cf, acc[r], sp[r], sz[r], sn[r]);
+              else adc_ps_out(ps[j][r], pv, cf, acc[r]);
 #endif
           } else {
             // degenerate alpha / scales: the literal ADC per partial sum (as cim_fwd_v3_kernel)
@@ -163,6 +182,7 @@ __device__ inline void dense_fwd_body(const Geo& g, const uint8_t* __restrict__ 
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               acc[r] += adc_literal_sum(ps[j], g.mode, sw, sa, al, g.qn, g.qp, mk, r);
+              if constexpr (!WST) continue;
               const bool pass = ste_literal(ps[j][r], g.mode, sw, sa, al, g.thr_hi, g.thr_lo) != 0.f;
               const float code = code_literal(ps[j][r], g.mode, sw, sa, al, g.qn, g.qp, g.thr_hi, g.thr_lo);
               sp[r] = (sp[r] << 1) | (pass ? 1u : 0u);
@@ -176,6 +196,7 @@ __device__ inline void dense_fwd_body(const Geo& g, const uint8_t* __restrict__ 
       const int o = og * 64 + ob * 16 + r16;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
+        if constexpr (!WST) continue;
         const size_t m = (size_t)m0 + wave * 16 + 4 * g4 + r;
         // code fields: lo -> 11, hi -> 01 (lo wins, as the ADC's second select)
         const uint32_t code = spread16(sz[r] | sn[r]) | (spread16(sn[r]) << 1);
@@ -197,15 +218,20 @@ __device__ inline void dense_fwd_body(const Geo& g, const uint8_t* __restrict__ 
 
 // The threshold path: one 64 x 64 tile per block.  Exits at once when the prologue set the
 // literal-ADC flag (dense_fwd_lit_kernel then does the work).
-template <int NBW, int NBA, int KS>
+// KSA (the three forward kernels): the K-steps per tile KS = KSA & 3; KSA >= 4 is the forward-only instance
+// (CIMQ_OPT_INFERENCE: no state planes through st) -- encoded there so that the training instances keep their
+// symbols and their code
+template <int NBW, int NBA, int KSA>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void dense_fwd_kernel(
     Geo g, const uint8_t* __restrict__ xcf, const v4i* __restrict__ wfrag, Params pp, const float* __restrict__ sw_p,
     const float* __restrict__ sa_p, float* __restrict__ out, uint2* __restrict__ st) {
+  constexpr int KS = KSA & 3;
+  constexpr bool WST = KSA < 4;
   __shared__ int4 prm[NBW * NBA * 64];  // this tile's ADC / STE thresholds, [j][k][64 channels]
   __shared__ float cfl[NBW * NBA * 64];
   __shared__ float4 accs[4 * 4 * 64];
   if (__builtin_amdgcn_readfirstlane(pp.flags[0]) != 0) return;
-  dense_fwd_body<NBW, NBA, KS, false>(g, xcf, wfrag, pp, 0.f, 0.f, out, st, prm, cfl, accs, blockIdx.x * 64,
+  dense_fwd_body<NBW, NBA, KS, false, WST>(g, xcf, wfrag, pp, 0.f, 0.f, out, st, prm, cfl, accs, blockIdx.x * 64,
                                       blockIdx.y);
 }
 
@@ -215,10 +241,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void d
 // forward).  The weight fragments go in two halves (output blocks 0-1, then 2-3) so a block stays under
 // 80 KB of LDS: two blocks per CU.  Per partial sum the ADC / state bits are adc_ps, in the same order:
 // out and the state words are bit-identical to dense_fwd_kernel's.
-template <int NBW, int NBA, int KS>
+template <int NBW, int NBA, int KSA>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void dense_fwd8_kernel(
     Geo g, const uint8_t* __restrict__ xcf, const v4i* __restrict__ wfrag, Params pp, float* __restrict__ out,
     uint2* __restrict__ st) {
+  constexpr int KS = KSA & 3;
+  constexpr bool WST = KSA < 4;
   constexpr int NKJ = NBW * NBA;
   constexpr int NWH = KS * NBW * 2 * 64;  // v4i of one half's weight fragments
   __shared__ int4 prm[NKJ * 64];          // [j][k][64 channels]: thi, tlo, mlo, span
@@ -328,13 +356,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void d
 #ifdef CIMQ_EXP_DENSE_NOADC
             acc[r] += (float)ps[j][r] * cf + (float)pv.x;
 #else
-            adc_ps(ps[j][r], pv, cf, acc[r], sp[r], sz[r], sn[r]);
+            if constexpr (WST) adc_ps(ps[j][r], pv, cf, acc[r], sp[r], sz[r], sn[r]);
+            else adc_ps_out(ps[j][r], pv, cf, acc[r]);
 #endif
         }
       }
       const int o = og * 64 + ob * 16 + r16;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
+        if constexpr (!WST) continue;
         const size_t m = (size_t)m0 + wave * 16 + 4 * g4 + r;
         const uint32_t code = spread16(sz[r] | sn[r]) | (spread16(sn[r]) << 1);
 #ifndef CIMQ_EXP_DENSE_NOSTORE
@@ -355,18 +385,20 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void d
 
 // Degenerate alpha_q / scales (flag set): the literal ADC per partial sum, a few blocks looping
 // over the tiles (its out-of-line calls kept out of the threshold kernel's register budget).
-template <int NBW, int NBA, int KS>
+template <int NBW, int NBA, int KSA>
 __global__ __launch_bounds__(256) void dense_fwd_lit_kernel(Geo g, const uint8_t* __restrict__ xcf,
                                                             const v4i* __restrict__ wfrag, Params pp,
                                                             const float* __restrict__ sw_p,
                                                             const float* __restrict__ sa_p, float* __restrict__ out,
                                                             uint2* __restrict__ st) {
+  constexpr int KS = KSA & 3;
+  constexpr bool WST = KSA < 4;
   __shared__ float4 accs[4 * 4 * 64];
   if (__builtin_amdgcn_readfirstlane(pp.flags[0]) == 0) return;
   const float sw = *sw_p, sa = *sa_p;
   const int nm = g.M / 64, ntile = nm * (g.O / 64);
   for (int t = blockIdx.x; t < ntile; t += gridDim.x)
-    dense_fwd_body<NBW, NBA, KS, true>(g, xcf, wfrag, pp, sw, sa, out, st, nullptr, nullptr, accs, (t % nm) * 64, t / nm);
+    dense_fwd_body<NBW, NBA, KS, true, WST>(g, xcf, wfrag, pp, sw, sa, out, st, nullptr, nullptr, accs, (t % nm) * 64, t / nm);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -686,16 +718,21 @@ __global__ __launch_bounds__(512) void dense_gw_kernel(Geo g, int rows_per_chunk
 template <int NBW, int NBA>
 int launch_dense_fwd_n(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, hipStream_t s) {
   CtxLayout L = ctx_layout(g);
-  auto klit = g.KS == 1 ? dense_fwd_lit_kernel<NBW, NBA, 1> : dense_fwd_lit_kernel<NBW, NBA, 2>;
+  // forward only (CIMQ_OPT_INFERENCE): the instances that write no state planes (KSA = 4 + KS)
+  const bool inf = g.inference != 0;
+  auto klit = g.KS == 1 ? (inf ? dense_fwd_lit_kernel<NBW, NBA, 5> : dense_fwd_lit_kernel<NBW, NBA, 1>)
+                        : (inf ? dense_fwd_lit_kernel<NBW, NBA, 6> : dense_fwd_lit_kernel<NBW, NBA, 2>);
   const uint8_t* wr = wreg(g, ctx);
   uint2* st = reinterpret_cast<uint2*>(ctx + L.st);
   const int slot = prof_begin(KID_FWD, g, s);
   if (tune("DENSE_FWD8", 1)) {  // 128-row blocks, weight side staged once per block (dense_plan: M % 128 == 0)
-    auto kern = g.KS == 1 ? dense_fwd8_kernel<NBW, NBA, 1> : dense_fwd8_kernel<NBW, NBA, 2>;
+    auto kern = g.KS == 1 ? (inf ? dense_fwd8_kernel<NBW, NBA, 5> : dense_fwd8_kernel<NBW, NBA, 1>)
+                          : (inf ? dense_fwd8_kernel<NBW, NBA, 6> : dense_fwd8_kernel<NBW, NBA, 2>);
     hipLaunchKernelGGL(kern, dim3(g.M / 128, g.O / 64), dim3(512), 0, s, g, ctx + L.xcode,
                        reinterpret_cast<const v4i*>(wr + L.wfrag), params_of(g, ctx), out, st);
   } else {
-    auto kern = g.KS == 1 ? dense_fwd_kernel<NBW, NBA, 1> : dense_fwd_kernel<NBW, NBA, 2>;
+    auto kern = g.KS == 1 ? (inf ? dense_fwd_kernel<NBW, NBA, 5> : dense_fwd_kernel<NBW, NBA, 1>)
+                          : (inf ? dense_fwd_kernel<NBW, NBA, 6> : dense_fwd_kernel<NBW, NBA, 2>);
     hipLaunchKernelGGL(kern, dim3(g.M / 64, g.O / 64), dim3(256), 0, s, g, ctx + L.xcode,
                        reinterpret_cast<const v4i*>(wr + L.wfrag), params_of(g, ctx), sw, sa, out, st);
   }

@@ -15,7 +15,19 @@ int launch_fwd_v3(const Geo& g, const Plan3& p, uint8_t* ctx, const float* sw, c
   // CST: compact state words with nbw = nba = CST fixed at compile time (v7_plan's slice pairs)
   void (*kern)(Geo, V3, const uint8_t*, const v4i*, Params, const float*, const float*, float*, uint8_t*,
                const float*, const float*, uint8_t*);
-  if (!cst) {
+  if (cst && g.inference) {
+    // forward only (CIMQ_OPT_INFERENCE): the same instances without the state words, their bits and the
+    // backward words (CSTA 10 + CST); the CST 0 instances below write no state as they are
+    if constexpr (NBP == 8) {
+      kern = c1_plan(g).ok ? cim_fwd_v3_kernel<8, KS, 9, 1> : cim_fwd_v3_kernel<8, KS, 18, 1>;
+    } else if (g.nbw == 2) {
+      kern = obm == 1 ? cim_fwd_v3_kernel<NBP, KS, 12, 1> : obm == 2 ? cim_fwd_v3_kernel<NBP, KS, 12, 2>
+                                                         : cim_fwd_v3_kernel<NBP, KS, 12, 4>;
+    } else {
+      kern = obm == 1 ? cim_fwd_v3_kernel<NBP, KS, 13, 1> : obm == 2 ? cim_fwd_v3_kernel<NBP, KS, 13, 2>
+                                                         : cim_fwd_v3_kernel<NBP, KS, 13, 4>;
+    }
+  } else if (!cst) {
     kern = obm == 1 ? cim_fwd_v3_kernel<NBP, KS, 0, 1> : obm == 2 ? cim_fwd_v3_kernel<NBP, KS, 0, 2>
                                                        : cim_fwd_v3_kernel<NBP, KS, 0, 4>;
   } else if constexpr (NBP == 8) {
@@ -50,7 +62,8 @@ int launch_fwd(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, flo
   if (p.ok && !DBG) {
     if (aq) {
       const Plan5 p5 = f5_plan(g);
-      if (p5.ok) return launch_fwd5(g, p5, ctx, sw, sa, out, s, aq);
+      // (cim_fwd5_kernel writes NCHW only: a forward-only Function call, [B, P, O], stays on cim_fwd_v3_kernel)
+      if (p5.ok && g.onchw) return launch_fwd5(g, p5, ctx, sw, sa, out, s, aq);
     }
     if (g.KS == 1) return launch_fwd_v3<NBP, 1>(g, p, ctx, sw, sa, out, s, aq);
     return launch_fwd_v3<NBP, 2>(g, p, ctx, sw, sa, out, s, aq);

@@ -12,6 +12,12 @@
                            same 14 positional args, grads for x, w, alpha_cim, beta_cim.
 ``cim_conv2d_lsq_shift``   the scale + shift ADC as a Conv2dLSQCiM option (adc_shift=True).
 
+Inference: a call made under ``torch.no_grad()`` / ``torch.inference_mode()``, or with no tensor
+argument that requires a gradient, runs the library's forward-only mode (CIMQ_OPT_INFERENCE, ABI 15):
+the same ``out`` bit for bit, no backward state written, a ctx of the weight tables only, nothing
+saved.  The choice is made before ``Function.apply`` (inside ``forward`` grad mode is always off and
+``needs_input_grad`` is all True, whatever the caller's mode).
+
 Device-only: CPU tensors raise (there is no CPU fallback in the product path).
 """
 from __future__ import annotations
@@ -23,6 +29,19 @@ import math
 import torch
 
 from . import _lib
+
+
+_INFERENCE = True  # tests switch it off to compare against the training forward under no-grad
+
+
+def inference_call(*args) -> bool:
+    """Whether a call with these arguments can never be differentiated: grad mode is off, or no
+    tensor among them requires a gradient.  Such calls take the forward-only library path."""
+    if not _INFERENCE:
+        return False
+    if not torch.is_grad_enabled():
+        return True
+    return not any(torch.is_tensor(a) and a.requires_grad for a in args)
 
 
 def _require_device(*ts):
@@ -65,10 +84,19 @@ def _geometry(x, w, stride, padding, dilation):
 class get_cim_output_signed(torch.autograd.Function):
     """HIP implementation of ``get_cim_output_signed`` (lsq.py:89-386)."""
 
+    @classmethod
+    def apply(cls, *args):
+        """The Function, or for a call nothing can differentiate (inference_call) the forward-only
+        library call: same output, no autograd node, no saved state."""
+        if inference_call(*args):
+            return cls._call(*args, inference=True)[0]
+        return super().apply(*args)
+
     @staticmethod
-    def forward(ctx, x, w, conv_stride, conv_padding, conv_dilation, act_bits, act_bit_slice,
-                weight_bits, weight_bit_slice, adc_bits, arr, binary_mask, alpha_cim,
-                weight_scaling_factor, act_scaling_factor, stochastic, signed_act):
+    def _call(x, w, conv_stride, conv_padding, conv_dilation, act_bits, act_bit_slice,
+              weight_bits, weight_bit_slice, adc_bits, arr, binary_mask, alpha_cim,
+              weight_scaling_factor, act_scaling_factor, stochastic, signed_act, inference=False):
+        """cimq_forward; returns (out, desc, sizes, bufs, wq).  ``inference``: CIMQ_OPT_INFERENCE."""
         if stochastic:
             assert adc_bits == 1.5  # lsq.py:136-137
         _require_device(x)
@@ -77,7 +105,8 @@ class get_cim_output_signed(torch.autograd.Function):
         desc = _lib.make_desc(B, C, H, W, O, KH, KW, st, pd, arr, weight_bits, act_bits,
                               weight_bit_slice, act_bit_slice, adc_bits, _lib.CIMQ_INPUT_XQ,
                               adc_variant=_lib.CIMQ_ADC_STOCHASTIC if stochastic else _lib.CIMQ_ADC_LIBRARY,
-                              seed=stochastic_seed() if stochastic else 0)
+                              seed=stochastic_seed() if stochastic else 0,
+                              options=_lib.CIMQ_OPT_INFERENCE if inference else 0)
         sizes = _lib.query_sizes(desc)
         xq = x.detach().to(torch.float32).contiguous()
         wq = w.detach().to(torch.float32).contiguous()
@@ -94,8 +123,18 @@ class get_cim_output_signed(torch.autograd.Function):
         _lib.check(lib.cimq_forward(desc, xq.data_ptr(), wq.data_ptr(), sa.data_ptr(), sw.data_ptr(),
                                     None if al is None else al.data_ptr(), bm.data_ptr(), sg.data_ptr(),
                                     out.data_ptr(), cbuf.data_ptr(), None, _stream()), "cimq_forward")
+        return out, desc, sizes, (xq, sa, sw, al, bm, sg, cbuf), wq
+
+    @staticmethod
+    def forward(ctx, x, w, conv_stride, conv_padding, conv_dilation, act_bits, act_bit_slice,
+                weight_bits, weight_bit_slice, adc_bits, arr, binary_mask, alpha_cim,
+                weight_scaling_factor, act_scaling_factor, stochastic, signed_act):
+        out, desc, sizes, bufs, wq = get_cim_output_signed._call(
+            x, w, conv_stride, conv_padding, conv_dilation, act_bits, act_bit_slice, weight_bits, weight_bit_slice,
+            adc_bits, arr, binary_mask, alpha_cim, weight_scaling_factor, act_scaling_factor, stochastic, signed_act)
+        xq = bufs[0]
         ctx.desc, ctx.sizes = desc, sizes
-        ctx.bufs = (xq, sa, sw, al, bm, sg, cbuf)
+        ctx.bufs = bufs
         ctx.save_for_backward(x, w)  # autograd's version check: in-place edits before backward raise
         ctx.wshape, ctx.xshape = wq.shape, xq.shape
         ctx.has_alpha = alpha_cim is not None
@@ -124,8 +163,9 @@ class _CimConv2dLSQ(torch.autograd.Function):
     """Fused LSQ-activation-quantiser + CiM conv (lsq.py:547-549 followed by lsq.py:578)."""
 
     @staticmethod
-    def forward(ctx, x, w_q, sa, sw, alpha_q, binary_mask, signed_act, stride, padding, dilation,
-                nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, stochastic=False):
+    def _call(x, w_q, sa, sw, alpha_q, binary_mask, signed_act, stride, padding, dilation,
+              nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, stochastic=False, inference=False):
+        """cimq_forward on the raw activation; returns (out, desc, sizes, bufs, wq)."""
         _require_device(x)
         dev = x.device
         B, C, H, W, O, KH, KW, st, pd = _geometry(x, w_q, stride, padding, dilation)
@@ -133,7 +173,8 @@ class _CimConv2dLSQ(torch.autograd.Function):
         desc = _lib.make_desc(B, C, H, W, O, KH, KW, st, pd, xbar, nbits_w, nbits_a, wbitslice,
                               abitslice, adcbits, _lib.CIMQ_INPUT_RAW_LSQ, qp_a,
                               _lib.CIMQ_ADC_STOCHASTIC if stochastic else _lib.CIMQ_ADC_LIBRARY,
-                              stochastic_seed() if stochastic else 0)
+                              stochastic_seed() if stochastic else 0,
+                              _lib.CIMQ_OPT_INFERENCE if inference else 0)
         sizes = _lib.query_sizes(desc)
         xc = x.detach().to(torch.float32).contiguous()
         wq = w_q.detach().to(torch.float32).contiguous()
@@ -150,8 +191,16 @@ class _CimConv2dLSQ(torch.autograd.Function):
         _lib.check(lib.cimq_forward(desc, xc.data_ptr(), wq.data_ptr(), sa_.data_ptr(), sw_.data_ptr(),
                                     None if al is None else al.data_ptr(), bm.data_ptr(), sg.data_ptr(),
                                     out.data_ptr(), cbuf.data_ptr(), None, _stream()), "cimq_forward")
+        return out, desc, sizes, (xc, sa_, sw_, al, bm, sg, cbuf), wq
+
+    @staticmethod
+    def forward(ctx, x, w_q, sa, sw, alpha_q, binary_mask, signed_act, stride, padding, dilation,
+                nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, stochastic=False):
+        out, desc, sizes, bufs, wq = _CimConv2dLSQ._call(x, w_q, sa, sw, alpha_q, binary_mask, signed_act, stride,
+                                                         padding, dilation, nbits_a, abitslice, nbits_w, wbitslice,
+                                                         adcbits, xbar, stochastic)
         ctx.desc, ctx.sizes = desc, sizes
-        ctx.bufs = (xc, sa_, sw_, al, bm, sg, cbuf)
+        ctx.bufs = bufs
         ctx.save_for_backward(x, w_q)
         ctx.wshape = wq.shape
         ctx.has_alpha = alpha_q is not None
@@ -180,7 +229,11 @@ class _CimConv2dLSQ(torch.autograd.Function):
 def cim_conv2d_lsq(x, w_q, sa, sw, alpha_q, binary_mask, signed_act, stride, padding, dilation,
                    nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, stochastic=False):
     """out[B, P, O] of the fused act-LSQ + CiM conv; differentiable in x, w_q, sa, alpha_q.
-    ``stochastic``: the stochastic 1.5-bit ADC of lsq.py:205-221 in the forward."""
+    ``stochastic``: the stochastic 1.5-bit ADC of lsq.py:205-221 in the forward.
+    A call nothing can differentiate (inference_call) runs forward only and saves nothing."""
+    if inference_call(x, w_q, sa, sw, alpha_q):
+        return _CimConv2dLSQ._call(x, w_q, sa, sw, alpha_q, binary_mask, signed_act, stride, padding, dilation,
+                                   nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, stochastic, inference=True)[0]
     return _CimConv2dLSQ.apply(x, w_q, sa, sw, alpha_q, binary_mask, signed_act, stride, padding,
                                dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, stochastic)
 
@@ -419,7 +472,7 @@ def _versions(*ts):
 
 
 def _module_descs(x_shape, weight, stride, padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits,
-                  xbar, nbits_alpha, has_alpha, stochastic, recompute=False):
+                  xbar, nbits_alpha, has_alpha, stochastic, recompute=False, inference=False):
     B, C, H, W = x_shape
     O, _, KH, KW = weight.shape
     st = tuple(stride) if isinstance(stride, (tuple, list)) else (stride, stride)
@@ -430,10 +483,60 @@ def _module_descs(x_shape, weight, stride, padding, dilation, nbits_a, abitslice
                           abitslice, adcbits, _lib.CIMQ_INPUT_RAW_LSQ, qp_a,
                           _lib.CIMQ_ADC_STOCHASTIC if stochastic else _lib.CIMQ_ADC_LIBRARY,
                           stochastic_seed() if stochastic else 0,
-                          _lib.CIMQ_OPT_RECOMPUTE if recompute else 0)
+                          (_lib.CIMQ_OPT_RECOMPUTE if recompute else 0) | (_lib.CIMQ_OPT_INFERENCE if inference else 0))
     lsq = _lib.make_lsq_desc(qn_w, qp_w, 1.0 / math.sqrt(B * C * H * W * qp_a),
                              1.0 / math.sqrt(weight.numel() * qp_w), nbits_alpha if has_alpha else 0)
     return desc, lsq
+
+
+def _prepare_descs(m, shape, inference=False):
+    """The descriptor pair a prepared weight side of layer ``m`` is made for (input shape ``shape``)."""
+    return _module_descs(shape, m.weight, m.stride, m.padding, m.dilation, m.nbits_a, m.abitslice,
+                         m.nbits_w, m.wbitslice, m.adcbits, m.xbar, m.nbits_alpha, m.alpha_cim is not None, False,
+                         bool(getattr(m, "recompute_psum", False)), inference)
+
+
+def _prepare_item(m, shape, inference=False):
+    """One layer's cimq_module_prepare item for input shape ``shape``, what it must keep alive until the
+    call, and the WeightPrep the call fills.  ``inference``: for the forward-only descriptor."""
+    has_alpha = m.alpha_cim is not None
+    desc, lsq = _prepare_descs(m, shape, inference)
+    sizes = _lib.query_sizes(desc)
+    dev = m.weight.device
+    buf = torch.empty(max(sizes.wprep_bytes, 1), device=dev, dtype=torch.uint8)
+    bm = m.binary_mask.to(device=dev, dtype=torch.int8).contiguous()
+    ps = (m.weight, m.alpha_act, m.alpha_weight, m.alpha_cim)
+    for t in ps:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise ValueError("prepare_weights: parameters must be contiguous fp32")
+    it = _lib.PrepareItem()
+    it.desc = ctypes.pointer(desc)
+    it.lsq = ctypes.pointer(lsq)
+    it.weight = m.weight.data_ptr()
+    it.alpha_act = m.alpha_act.data_ptr()
+    it.alpha_weight = m.alpha_weight.data_ptr()
+    it.alpha_cim = m.alpha_cim.data_ptr() if has_alpha else None
+    it.binary_mask = bm.data_ptr()
+    it.wprep = buf.data_ptr()
+    return it, (desc, lsq, bm), WeightPrep(buf, _prep_key(desc, lsq, shape), _versions(*ps, m.binary_mask))
+
+
+def inference_weights(m, x_shape, cached=None):
+    """The weight side of a forward-only call of the fused Conv2dLSQCiM ``m`` on input shape ``x_shape``:
+    ``cached`` if that WeightPrep was made for this shape and the parameters as they are now (_prep_key,
+    _versions -- an edit through ``p.data`` bumps no version: drop the cache after one), else a new one from
+    cimq_module_prepare with the forward roles only.  Conv2dLSQCiM keeps it across the batches of an evaluation."""
+    if cached is not None:
+        desc, lsq = _prepare_descs(m, tuple(x_shape), inference=True)
+        if (cached.key == _prep_key(desc, lsq, tuple(x_shape)) and cached.versions ==
+                _versions(m.weight, m.alpha_act, m.alpha_weight, m.alpha_cim, m.binary_mask)):
+            return cached
+    it, keep, wp = _prepare_item(m, tuple(x_shape), inference=True)
+    arr = (_lib.PrepareItem * 1)(it)
+    _lib.check(_lib.load().cimq_module_prepare(1, arr, torch.cuda.current_stream(m.weight.device).cuda_stream),
+               "cimq_module_prepare")
+    del keep
+    return wp
 
 
 def prepare_weights(modules, stream=None):
@@ -449,31 +552,11 @@ def prepare_weights(modules, stream=None):
     for m in modules:
         if not getattr(m, "_fused_ready", None) or not m._fused_ready():
             continue
-        shape = m._last_x_shape
-        has_alpha = m.alpha_cim is not None
-        desc, lsq = _module_descs(shape, m.weight, m.stride, m.padding, m.dilation, m.nbits_a, m.abitslice,
-                                  m.nbits_w, m.wbitslice, m.adcbits, m.xbar, m.nbits_alpha, has_alpha, False,
-                                  bool(getattr(m, "recompute_psum", False)))
-        sizes = _lib.query_sizes(desc)
+        it, kp, wp = _prepare_item(m, m._last_x_shape)
         dev = m.weight.device
-        buf = torch.empty(max(sizes.wprep_bytes, 1), device=dev, dtype=torch.uint8)
-        bm = m.binary_mask.to(device=dev, dtype=torch.int8).contiguous()
-        ps = (m.weight, m.alpha_act, m.alpha_weight, m.alpha_cim)
-        for t in ps:
-            if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
-                raise ValueError("prepare_weights: parameters must be contiguous fp32")
-        it = _lib.PrepareItem()
-        it.desc = ctypes.pointer(desc)
-        it.lsq = ctypes.pointer(lsq)
-        it.weight = m.weight.data_ptr()
-        it.alpha_act = m.alpha_act.data_ptr()
-        it.alpha_weight = m.alpha_weight.data_ptr()
-        it.alpha_cim = m.alpha_cim.data_ptr() if has_alpha else None
-        it.binary_mask = bm.data_ptr()
-        it.wprep = buf.data_ptr()
         items.append(it)
-        keep.append((desc, lsq, bm))
-        taken.append((m, WeightPrep(buf, _prep_key(desc, lsq, shape), _versions(*ps, m.binary_mask))))
+        keep.append(kp)
+        taken.append((m, wp))
     if not items:
         return 0
     arr = (_lib.PrepareItem * len(items))(*items)
@@ -500,20 +583,22 @@ class _CimModuleConv(torch.autograd.Function):
     the bucket joins that stream before it reads the gradients (GradBucket.join)."""
 
     @staticmethod
-    def forward(ctx, x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding,
-                dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha, accumulate=False,
-                stochastic=False, tail_stream=None, wprep=None, recompute=False):
+    def _call(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding, dilation,
+              nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha, stochastic=False, wprep=None,
+              recompute=False, inference=False):
+        """cimq_module_forward; returns (out, desc, lsq, sizes, bufs, wprep_buf).  ``inference``:
+        CIMQ_OPT_INFERENCE (the small ctx and the forward workspace, dropped by the caller)."""
         _require_device(x)
         dev = x.device
         B, C, H, W, O, KH, KW, st, pd = _geometry(x, weight, stride, padding, dilation)
         desc, lsq = _module_descs(tuple(x.shape), weight, st, pd, dilation, nbits_a, abitslice, nbits_w, wbitslice,
-                                  adcbits, xbar, nbits_alpha, alpha_cim is not None, stochastic, recompute)
-        # a prepared weight side (prepare_weights) if it was made for exactly this call
-        ctx.wprep_buf = None
+                                  adcbits, xbar, nbits_alpha, alpha_cim is not None, stochastic, recompute, inference)
+        # a prepared weight side (prepare_weights / inference_weights) if it was made for exactly this call
+        wprep_buf = None
         if (wprep is not None and not stochastic and wprep.key == _prep_key(desc, lsq, x.shape)
                 and wprep.versions == _versions(weight, alpha_act, alpha_weight, alpha_cim, binary_mask)):
             lsq.wprep = wprep.buf.data_ptr()
-            ctx.wprep_buf = wprep.buf
+            wprep_buf = wprep.buf
         sizes = _lib.query_sizes(desc)
         xc = x.detach().to(torch.float32).contiguous()
         wc = weight.detach().to(torch.float32).contiguous()
@@ -533,8 +618,17 @@ class _CimModuleConv(torch.autograd.Function):
                                            None if ac is None else ac.data_ptr(), bm.data_ptr(), sg.data_ptr(),
                                            out.data_ptr(), cbuf.data_ptr(), ws.data_ptr(), _stream()),
                    "cimq_module_forward")
+        return out, desc, lsq, sizes, (xc, wc, aa, aw, ac, bm, sg, cbuf), wprep_buf
+
+    @staticmethod
+    def forward(ctx, x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding,
+                dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha, accumulate=False,
+                stochastic=False, tail_stream=None, wprep=None, recompute=False):
+        out, desc, lsq, sizes, bufs, ctx.wprep_buf = _CimModuleConv._call(
+            x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding, dilation, nbits_a,
+            abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha, stochastic, wprep, recompute)
         ctx.desc, ctx.lsq, ctx.sizes = desc, lsq, sizes
-        ctx.bufs = (xc, wc, aa, aw, ac, bm, sg, cbuf)
+        ctx.bufs = bufs
         ctx.module_path = True  # a cimq_module_forward ctx (debug_state_codes)
         # the backward reads x and the raw parameters again (act-LSQ / weight-LSQ STE); saving
         # them lets autograd's version counters catch an in-place change in between
@@ -634,7 +728,13 @@ def cim_module_conv(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, 
     the three step-size parameters (alpha_act and alpha_weight are 1-element tensors).
     ``accumulate`` / ``tail_stream``: see _CimModuleConv; ``stochastic``: the stochastic 1.5-bit ADC;
     ``wprep``: a WeightPrep from prepare_weights (used only if it matches this call); ``recompute``:
-    CIMQ_OPT_RECOMPUTE (no state words in the ctx where a recompute backward exists; slower)."""
+    CIMQ_OPT_RECOMPUTE (no state words in the ctx where a recompute backward exists; slower).
+    A call nothing can differentiate (inference_call) runs forward only (CIMQ_OPT_INFERENCE): out, the small
+    ctx and the forward workspace are allocated, nothing is saved; ``wprep`` then comes from inference_weights."""
+    if inference_call(x, weight, alpha_act, alpha_weight, alpha_cim):
+        return _CimModuleConv._call(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride,
+                                    padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar,
+                                    nbits_alpha, stochastic, wprep, recompute, inference=True)[0]
     return _CimModuleConv.apply(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride,
                                 padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar,
                                 nbits_alpha, accumulate, stochastic, tail_stream, wprep, recompute)
@@ -670,13 +770,16 @@ class _CimModuleShiftConv(torch.autograd.Function):
     alpha_cim and beta_cim.  NCHW output."""
 
     @staticmethod
-    def forward(ctx, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act, stride,
-                padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, xbar, nbits_alpha):
+    def _call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act, stride,
+              padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, xbar, nbits_alpha, inference=False):
+        """cimq_module_shift_forward; returns (out, desc, lsq, sizes, bufs)."""
         _require_device(x)
         dev = x.device
         B, C, H, W, O, KH, KW, st, pd = _geometry(x, weight, stride, padding, dilation)
         desc, lsq = _shift_module_descs(tuple(x.shape), weight, st, pd, dilation, nbits_a, abitslice, nbits_w,
                                         wbitslice, xbar, nbits_alpha)
+        if inference:
+            desc.options |= _lib.CIMQ_OPT_INFERENCE
         sizes = _lib.query_sizes(desc)
         xc = x.detach().to(torch.float32).contiguous()
         wc = weight.detach().to(torch.float32).contiguous()
@@ -695,8 +798,16 @@ class _CimModuleShiftConv(torch.autograd.Function):
                                                          aw.data_ptr(), ac.data_ptr(), bc.data_ptr(), bm.data_ptr(),
                                                          sg.data_ptr(), out.data_ptr(), cbuf.data_ptr(),
                                                          ws.data_ptr(), _stream()), "cimq_module_shift_forward")
+        return out, desc, lsq, sizes, (xc, wc, aa, aw, ac, bc, bm, sg, cbuf)
+
+    @staticmethod
+    def forward(ctx, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act, stride,
+                padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, xbar, nbits_alpha):
+        out, desc, lsq, sizes, bufs = _CimModuleShiftConv._call(
+            x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act, stride, padding,
+            dilation, nbits_a, abitslice, nbits_w, wbitslice, xbar, nbits_alpha)
         ctx.desc, ctx.lsq, ctx.sizes = desc, lsq, sizes
-        ctx.bufs = (xc, wc, aa, aw, ac, bc, bm, sg, cbuf)
+        ctx.bufs = bufs
         ctx.save_for_backward(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim)
         return out
 
@@ -723,7 +834,11 @@ class _CimModuleShiftConv(torch.autograd.Function):
 def cim_module_shift_conv(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act, stride,
                           padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, xbar, nbits_alpha):
     """NCHW output of a Conv2dLSQCiM(adc_shift=True, adcbits=1.5) layer with its quantisers fused
-    (module_shift_supported must hold)."""
+    (module_shift_supported must hold).  Forward only for a call nothing can differentiate (inference_call)."""
+    if inference_call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim):
+        return _CimModuleShiftConv._call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask,
+                                         signed_act, stride, padding, dilation, nbits_a, abitslice, nbits_w,
+                                         wbitslice, xbar, nbits_alpha, inference=True)[0]
     return _CimModuleShiftConv.apply(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask,
                                      signed_act, stride, padding, dilation, nbits_a, abitslice, nbits_w, wbitslice,
                                      xbar, nbits_alpha)

@@ -189,6 +189,10 @@ def train_epoch(loader, model, criterion, optimizer, epoch, hp, max_steps=0, log
 
 
 def validate(loader, model, criterion, hp, max_steps=0):
+    """main_lsq.py's validate(): top-1 / top-5 accuracy and mean loss in eval mode under no_grad.
+    Nothing here selects the evaluation path: under no_grad every Conv2dLSQCiM runs libcimq's
+    forward-only mode by itself (CIMQ_OPT_INFERENCE: same outputs, no backward state) and keeps its
+    prepared weight side across the batches, so the weights are quantised once per input shape."""
     model.eval()
     seen, loss_sum, c1, c5 = 0, 0.0, 0.0, 0.0
     with torch.no_grad():

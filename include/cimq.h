@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define CIMQ_ABI_VERSION 14
+#define CIMQ_ABI_VERSION 15
 
 /* status codes */
 #define CIMQ_OK 0
@@ -72,6 +72,19 @@ extern "C" {
                                 and the backward recomputes the partial sums -- a smaller ctx (module_ctx_bytes;
                                 33.5 MB less per such layer at B = 256) for a slower backward on MI355X (DESIGN.md
                                 section 10).  Ignored elsewhere.  Since ABI 14 */
+/* (bit value 2 is not an option: descriptors carrying it are refused) */
+#define CIMQ_OPT_INFERENCE 4 /* forward only (evaluation under no-grad): cimq_forward, cimq_module_forward,
+                                cimq_module_shift_forward and cimq_module_prepare compute ``out`` bit for bit as
+                                without it -- same kernels, same summation order, same Philox draws -- and write
+                                nothing a backward would read: no state words, no backward activation words, none
+                                of the backward-only weight operands.  cimq_query_sizes then reports ctx_bytes ==
+                                module_ctx_bytes (the weight-side tables, plus the forward slice words on the routes
+                                whose forward does not quantise the activation itself), bwd_workspace_bytes == 0
+                                and a fwd_workspace_bytes of forward scratch only; wprep_bytes is unchanged, and a
+                                wprep buffer must be made with the descriptor it is used with.  cimq_module_route
+                                reports CIMQ_ROUTE_NONE for both backward roles.  Every other entry point that takes
+                                a cimq_conv_desc refuses the bit with CIMQ_EINVAL.  CIMQ_OPT_RECOMPUTE may be set
+                                with it and then has no effect.  Since ABI 15 */
 
 /* cimq_lsq_desc.flags */
 #define CIMQ_LSQ_ACCUMULATE_GRADS 1 /* cimq_module_backward adds the parameter gradients into
@@ -225,8 +238,9 @@ enum {
   CIMQ_ROUTE_GX5 = 6,      /* grad_x: cim_bwd_gx5_kernel (per input pixel, round 5) */
   CIMQ_ROUTE_GW5 = 7,      /* grad_w: cim_bwd_gw5_kernel (A-ready patch, round 5) */
   CIMQ_ROUTE_DENSE = 8,    /* the dense 1x1 path */
-  CIMQ_ROUTE_R6 = 9        /* grad_x and grad_w in cim_bwd_r6_kernel from RECOMPUTED partial sums (the forward
+  CIMQ_ROUTE_R6 = 9,       /* grad_x and grad_w in cim_bwd_r6_kernel from RECOMPUTED partial sums (the forward
                               writes no state words; round 6, ABI 13; only under CIMQ_OPT_RECOMPUTE since ABI 14) */
+  CIMQ_ROUTE_NONE = 10     /* route[1] / route[2] under CIMQ_OPT_INFERENCE: there is no backward.  Since ABI 15 */
 };
 int cimq_module_route(const cimq_conv_desc* d, int* route);
 int cimq_module_shift_forward(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* x, const float* weight,

@@ -1,0 +1,385 @@
+"""GPU: the forward-only mode (CIMQ_OPT_INFERENCE, ABI 15) end to end -- the output of every forward route bit
+for bit equal to the training forward's, nothing written past the small ctx, the backward refused, the
+Function / module / harness paths taking the mode by themselves under no-grad, its memory, and the weight-side
+cache a Conv2dLSQCiM keeps across the batches of an evaluation.  Shapes: test_inference_host.CASES (the smallest
+that reach each route: one and two output blocks, stride 2, several tile groups, two images per m-tile, the
+w8a8 first conv, w2a2, the multi-level ADC, the general kernels, the dense path in two tiles, the shift ADC)."""
+import numpy as np
+import pytest
+import torch
+
+from conftest import golden_manifest, load_golden, module_cases, rel_err
+from test_inference_host import CASES, INF
+
+pytestmark = pytest.mark.gpu
+
+
+def _F():
+    from cim_quantization_amd import functional as F
+    return F
+
+
+def _L():
+    import cim_quantization_amd._lib as L
+    return L
+
+
+_BUILT = {}
+
+
+def _case(name, dev):
+    """(module after its first-step initialisation, x, training-mode output), built once per case"""
+    if name in _BUILT:
+        return _BUILT[name]
+    import cim_quantization_amd._modules as my_nn
+    B, C, O, H, s, nb, xbar, adc, k, p, _ = CASES[name]
+    torch.manual_seed(sum(map(ord, name)))
+    m = my_nn.Conv2dLSQCiM(C, O, k, s, p, bias=False, nbits_w=nb, nbits_a=nb, nbits_alpha=8, wbitslice=1,
+                           abitslice=1, xbar=xbar, adcbits=adc, signed_xbar=True, stochastic_quant=False,
+                           adc_shift=(name == "shift"))
+    torch.nn.init.kaiming_normal_(m.weight)
+    m = m.to(dev).train()
+    g = torch.Generator().manual_seed(1 + sum(map(ord, name)))
+    x = torch.randn(B, C, H, H, generator=g)
+    if name != "conv1":  # (the first conv sees the signed, normalised image)
+        x = x.relu()
+    x = x.to(dev)
+    m(x)  # the first-step initialisation (lsq.py:532-563)
+    if name == "shift":
+        with torch.no_grad():
+            m.beta_cim.copy_(0.3 * m.alpha_cim * torch.randn(m.alpha_cim.shape, generator=g).to(dev))
+    out_t = m(x.clone().requires_grad_(True)).detach().clone()
+    _BUILT[name] = (m, x, out_t)
+    return _BUILT[name]
+
+
+def _route0(m, x):
+    F, L = _F(), _L()
+    desc, _ = F._module_descs(tuple(x.shape), m.weight, m.stride, m.padding, m.dilation, m.nbits_a, m.abitslice,
+                              m.nbits_w, m.wbitslice, m.adcbits, m.xbar, m.nbits_alpha, m.alpha_cim is not None, False)
+    if m.adc_shift:
+        desc.adc_variant = L.CIMQ_ADC_SHIFT_ROUND
+    return L.ROUTE_NAMES[L.module_route(desc)[0]]
+
+
+def _check_route(name, m, x):
+    """each test asserts its forward route first, so it cannot silently test another kernel"""
+    assert _route0(m, x) == CASES[name][-1], name
+    if name == "shift":
+        assert m._shift_fused(x)
+
+
+# ---------------------------------------------------------------------------------------------------
+# 1. bit identity
+# ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(CASES))
+def test_bit_identity(cuda_device, name):
+    m, x, out_t = _case(name, cuda_device)
+    _check_route(name, m, x)
+    try:
+        m.eval()
+        with torch.no_grad():
+            out_i = m(x)
+    finally:
+        m.train()
+    assert out_i.grad_fn is None and not out_i.requires_grad
+    assert torch.equal(out_t, out_i)
+
+
+@pytest.mark.parametrize("name", module_cases())
+def test_bit_identity_golden(cuda_device, monkeypatch, name):
+    """the module goldens' inputs and state: training and inference outputs equal, and the inference output
+    within test_module_steps_vs_golden's bar of the reference's (1e-6 of max(|ref|, sum of |terms|))"""
+    import cim_quantization_amd._modules as my_nn
+    from oracle import cim_module_oracle as cmo
+    from test_gpu_parity import _capture_oracle_ctx, _module_kwargs, _set_state_from_golden
+    cfg = golden_manifest()[name]["cfg"]
+    z = load_golden(name)
+    st, pd = cfg["s"], cfg["p"]
+    args = (cfg["C"], cfg["O"], (cfg["k"], cfg["k"]), (st, st), (pd, pd), (1, 1))
+    m = my_nn.Conv2dLSQCiM(*args, groups=1, bias=cfg["bias"], **_module_kwargs(cfg)).to(cuda_device)
+    om = cmo.OracleConv2dLSQCiM(*args, groups=1, bias=cfg["bias"], **_module_kwargs(cfg))
+    with torch.no_grad():
+        m.weight.copy_(torch.from_numpy(z["in_weight"]))
+        om.weight.copy_(torch.from_numpy(z["in_weight"]))
+    _set_state_from_golden(m, z, "ref_s0_")
+    _set_state_from_golden(om, z, "ref_s0_")
+    x = torch.from_numpy(z["in_x0"].copy()).to(cuda_device)
+    m.train()
+    out_t = m(x.clone().requires_grad_(True)).detach()
+    m.eval()
+    with torch.no_grad():
+        out_i = m(x)
+    assert torch.equal(out_t, out_i)
+    om.train()
+    box = _capture_oracle_ctx(monkeypatch)
+    with torch.no_grad():
+        om(torch.from_numpy(z["in_x0"].copy()))
+    c = box["c"]
+    bmask = np.abs(om.binary_mask.numpy().astype(np.float64))
+    terms = (np.abs(c.adc.astype(np.float64)) * bmask).sum(axis=(1, 2, 3)).transpose(0, 2, 1)
+    assert rel_err(out_i.cpu().numpy(), z["ref_s0_out"], terms.reshape(z["ref_s0_out"].shape)) < 1e-6
+
+
+# ---------------------------------------------------------------------------------------------------
+# the raw ABI
+# ---------------------------------------------------------------------------------------------------
+def _raw(m, x, options, ctx_bytes=None, fill=None, variant=None, seed=0):
+    """cimq_module_forward / cimq_module_shift_forward on module m's parameters with ``options`` in the
+    descriptor; returns (out, ctx buffer, sizes, desc, lsq, argument tensors)"""
+    F, L = _F(), _L()
+    dev = x.device
+    if m.adc_shift:
+        desc, lsq = F._shift_module_descs(tuple(x.shape), m.weight, m.stride, m.padding, m.dilation, m.nbits_a,
+                                          m.abitslice, m.nbits_w, m.wbitslice, m.xbar, m.nbits_alpha)
+    else:
+        desc, lsq = F._module_descs(tuple(x.shape), m.weight, m.stride, m.padding, m.dilation, m.nbits_a, m.abitslice,
+                                    m.nbits_w, m.wbitslice, m.adcbits, m.xbar, m.nbits_alpha, m.alpha_cim is not None,
+                                    False)
+    desc.options = options
+    if variant is not None:
+        desc.adc_variant = variant
+        desc.seed_lo, desc.seed_hi = seed & 0xFFFFFFFF, seed >> 32
+    sizes = L.query_sizes(desc)
+    B, O = x.shape[0], m.weight.shape[0]
+    Ho = (x.shape[2] + 2 * m.padding[0] - m.weight.shape[2]) // m.stride[0] + 1
+    out = torch.empty(B, O, Ho, Ho, device=dev)
+    cbuf = torch.empty(max(ctx_bytes or sizes.module_ctx_bytes, 1), device=dev, dtype=torch.uint8)
+    if fill is not None:
+        cbuf.fill_(fill)
+    ws = torch.empty(max(sizes.fwd_workspace_bytes, 1), device=dev, dtype=torch.uint8)
+    t = dict(x=x.contiguous(), w=m.weight.detach().contiguous(), aa=m.alpha_act.detach().reshape(-1)[:1].contiguous(),
+             aw=m.alpha_weight.detach().reshape(-1)[:1].contiguous(),
+             ac=None if m.alpha_cim is None else m.alpha_cim.detach().contiguous(),
+             bm=m.binary_mask.to(device=dev, dtype=torch.int8).contiguous(),
+             sg=m.signed_act.detach().to(torch.float32).reshape(-1)[:1].contiguous())
+    p = lambda v: None if v is None else v.data_ptr()  # noqa: E731
+    lib = L.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    if m.adc_shift:
+        t["bc"] = m.beta_cim.detach().contiguous()
+        rc = lib.cimq_module_shift_forward(desc, lsq, p(t["x"]), p(t["w"]), p(t["aa"]), p(t["aw"]), p(t["ac"]),
+                                           p(t["bc"]), p(t["bm"]), p(t["sg"]), p(out), p(cbuf), p(ws), stream)
+    else:
+        rc = lib.cimq_module_forward(desc, lsq, p(t["x"]), p(t["w"]), p(t["aa"]), p(t["aw"]), p(t["ac"]), p(t["bm"]),
+                                     p(t["sg"]), p(out), p(cbuf), p(ws), stream)
+    L.check(rc, "module forward")
+    torch.cuda.synchronize()
+    return out, cbuf, sizes, desc, lsq, t
+
+
+# 2. nothing written past the inference ctx
+@pytest.mark.parametrize("name", ["l1", "conv1", "w2a2", "dense", "shift"])
+def test_nothing_written_past_inference_ctx(cuda_device, name):
+    """a ctx of the TRAINING size filled with 0xA5 (a forward that still wrote state would stay inside it): every
+    byte from the inference ctx size on is untouched"""
+    L = _L()
+    m, x, out_t = _case(name, cuda_device)
+    _check_route(name, m, x)
+    d0 = _raw(m, x, 0)
+    s0 = L.query_sizes(d0[3])
+    assert torch.equal(d0[0], out_t)  # (the raw training forward is the module's)
+    out, cbuf, s1, *_ = _raw(m, x, INF, ctx_bytes=s0.ctx_bytes, fill=0xA5)
+    assert s1.ctx_bytes < s0.ctx_bytes and cbuf.numel() == s0.ctx_bytes
+    assert bool((cbuf[s1.ctx_bytes:] == 0xA5).all())
+    assert torch.equal(out, out_t)
+
+
+# 3. stochastic ADC
+def test_stochastic_adc_same_draws(cuda_device):
+    L = _L()
+    m, x, _ = _case("l1", cuda_device)
+    seed = 0x1234_5678_9ABC
+    out_t = _raw(m, x, 0, variant=L.CIMQ_ADC_STOCHASTIC, seed=seed)[0]
+    out_i = _raw(m, x, INF, variant=L.CIMQ_ADC_STOCHASTIC, seed=seed)[0]
+    other = _raw(m, x, INF, variant=L.CIMQ_ADC_STOCHASTIC, seed=seed + 1)[0]
+    assert torch.equal(out_t, out_i)
+    assert not torch.equal(out_i, other)  # (the draws do depend on the key)
+
+
+# 4. the backward is refused
+def test_backward_refused(cuda_device):
+    L = _L()
+    m, x, _ = _case("l1", cuda_device)
+    _check_route("l1", m, x)
+    out, cbuf, sizes, desc, lsq, t = _raw(m, x, INF)
+    s0 = L.query_sizes(_raw(m, x, 0)[3])
+    ws = torch.empty(s0.bwd_workspace_bytes, device=x.device, dtype=torch.uint8)
+    gx = torch.full_like(x, 7.25)
+    gw, gaa, gaw, gac = torch.empty_like(t["w"]), torch.empty_like(t["aa"]), torch.empty_like(t["aw"]), \
+        torch.empty_like(t["ac"])
+    gy = torch.ones_like(out)
+    p = lambda v: v.data_ptr()  # noqa: E731
+    lib = L.load()
+    rc = lib.cimq_module_backward(desc, lsq, p(gy), p(t["x"]), p(t["w"]), p(t["aa"]), p(t["aw"]), p(t["ac"]),
+                                  p(t["bm"]), p(t["sg"]), p(cbuf), p(gx), p(gw), p(gaa), p(gaw), p(gac), p(ws),
+                                  torch.cuda.current_stream().cuda_stream)
+    assert rc == L.CIMQ_EINVAL and b"CIMQ_OPT_INFERENCE" in lib.cimq_last_error()
+    torch.cuda.synchronize()
+    assert bool((gx == 7.25).all())
+
+
+# 5. the Function path
+@pytest.mark.parametrize("name", ["c48", "l1"])
+def test_function_path(cuda_device, name):
+    from test_gpu_parity import _dev, _random_inputs
+    F = _F()
+    B, C, O, H, s, nb, xbar, adc, k, p, _ = CASES[name]
+    cfg = dict(B=B, C=C, O=O, H=H, k=k, s=s, p=p, wb=nb, ab=nb, wbs=1, abs=1, xbar=xbar, adc=adc, signed=0)
+    inp = _random_inputs(cfg, 8100 + len(name))
+    dev = cuda_device
+
+    def args(grad):
+        return (_dev(inp["x_q"], dev, grad), _dev(inp["w_q"], dev, grad), (s, s), (p, p), (1, 1), nb, 1, nb, 1, adc,
+                xbar, _dev(inp["binary_mask"], dev), _dev(inp["alpha_q"], dev, grad), _dev(inp["sw"], dev),
+                _dev(inp["sa"], dev), False, _dev(inp["signed_act"], dev))
+    out_t = F.get_cim_output_signed.apply(*args(True))
+    assert out_t.grad_fn is not None
+    with torch.no_grad():
+        out_i = F.get_cim_output_signed.apply(*args(True))
+    out_d = F.get_cim_output_signed.apply(*args(False))  # grad enabled, only detached inputs
+    assert out_i.grad_fn is None and out_d.grad_fn is None
+    assert torch.equal(out_t.detach(), out_i) and torch.equal(out_t.detach(), out_d)
+
+
+@pytest.mark.parametrize("name", ["c48", "l1"])
+def test_torch_quantiser_module_path(cuda_device, name):
+    """an eval-mode module whose init_state is 0 runs the torch quantisers around cim_conv2d_lsq: its no-grad
+    output equals its grad-enabled one"""
+    import cim_quantization_amd._modules as my_nn
+    B, C, O, H, s, nb, xbar, adc, k, p, _ = CASES[name]
+    torch.manual_seed(5)
+    m = my_nn.Conv2dLSQCiM(C, O, k, s, p, bias=False, nbits_w=nb, nbits_a=nb, nbits_alpha=8, wbitslice=1, abitslice=1,
+                           xbar=xbar, adcbits=adc, signed_xbar=True, stochastic_quant=False)
+    torch.nn.init.kaiming_normal_(m.weight)
+    m = m.to(cuda_device).eval()
+    with torch.no_grad():  # usable step sizes without the first-step initialisation
+        m.alpha_act.fill_(0.21)
+        m.alpha_weight.fill_(0.07)
+        m.alpha_cim.copy_(0.21 * 0.07 * (1 + 3 * torch.rand(m.alpha_cim.shape, device=cuda_device)))
+    assert float(m.init_state) == 0
+    x = torch.randn(B, C, H, H, generator=torch.Generator().manual_seed(6)).relu().to(cuda_device)
+    out_t = m(x.clone().requires_grad_(True))
+    assert out_t.grad_fn is not None
+    with torch.no_grad():
+        out_i = m(x)
+    assert torch.equal(out_t.detach(), out_i)
+
+
+# 6. memory
+def test_inference_memory(cuda_device):
+    """the second no-grad call allocates out, the small ctx and the forward workspace (+ 16 KiB for the int8 mask
+    copy and allocator rounding); the training forward's ctx alone is larger than that"""
+    F, L = _F(), _L()
+    m, _, _ = _case("l1", cuda_device)
+    x = torch.randn(8, 16, 32, 32, generator=torch.Generator().manual_seed(3)).relu().to(cuda_device)
+    _check_route("l1", m, x)
+    desc, _ = F._module_descs(tuple(x.shape), m.weight, m.stride, m.padding, m.dilation, m.nbits_a, m.abitslice,
+                              m.nbits_w, m.wbitslice, m.adcbits, m.xbar, m.nbits_alpha, True, False, False, True)
+    s1 = L.query_sizes(desc)
+    desc.options = 0
+    s0 = L.query_sizes(desc)
+    try:
+        m.eval()
+        with torch.no_grad():
+            out = m(x)  # warm-up: makes the weight cache
+            nbytes = out.numel() * 4
+            del out
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            out = m(x)
+            torch.cuda.synchronize()
+            peak = torch.cuda.max_memory_allocated() - base
+    finally:
+        m.train()
+    bound = nbytes + s1.ctx_bytes + s1.fwd_workspace_bytes + 16 * 1024
+    print(f"peak {peak} bound {bound} training ctx {s0.module_ctx_bytes}")
+    assert peak <= bound
+    assert s0.module_ctx_bytes > bound
+
+
+# 7. the weight cache
+def test_weight_cache(cuda_device, monkeypatch):
+    import copy
+    L = _L()
+    m0, x, _ = _case("l2", cuda_device)
+    _check_route("l2", m0, x)
+    m = copy.deepcopy(m0)
+    m._inf_prep = None
+    lib = L.load()
+    calls = []
+    real = lib.cimq_module_prepare
+
+    def counted(*a):
+        calls.append(a[0])
+        return real(*a)
+    monkeypatch.setattr(lib, "cimq_module_prepare", counted)
+    m.eval()
+    with torch.no_grad():
+        y1 = m(x)
+        assert len(calls) == 1 and m._inf_prep is not None
+        y2 = m(x)
+        assert len(calls) == 1  # the second call reuses the cache
+        assert torch.equal(y1, y2)
+        # a parameter edit bumps its version: the next output is a freshly built module's
+        m.weight.mul_(1.5)
+        y3 = m(x)
+        assert len(calls) == 2
+    fresh = copy.deepcopy(m0)
+    with torch.no_grad():
+        fresh.weight.mul_(1.5)
+    fresh.eval()
+    with torch.no_grad():
+        assert torch.equal(y3, fresh(x))
+    # a call with grad enabled never reads the cache; train() drops it; the training step is that of a module
+    # that never ran inference
+    m.train()
+    assert m._inf_prep is None
+    never = copy.deepcopy(m0)
+    with torch.no_grad():
+        never.weight.mul_(1.5)
+    never.train()
+    gy = torch.randn(y1.shape, generator=torch.Generator().manual_seed(2)).to(cuda_device)
+    grads = []
+    n_before = len(calls)
+    for mod in (m, never):
+        xi = x.clone().requires_grad_(True)
+        mod(xi).backward(gy)
+        grads.append([xi.grad] + [p.grad for p in mod.parameters()])
+    for a, b in zip(*grads):
+        assert torch.equal(a, b)
+    assert len(calls) == n_before
+    # load_state_dict drops the cache
+    m.eval()
+    with torch.no_grad():
+        m(x)
+    assert m._inf_prep is not None
+    m.load_state_dict(m0.state_dict())
+    assert m._inf_prep is None
+    with torch.no_grad():
+        assert torch.equal(m(x), y1)
+
+
+# 8. the harness
+def test_validate_same_with_and_without_the_option(cuda_device, tmp_path, monkeypatch):
+    from cim_quantization_amd.harness import train
+    from cim_quantization_amd.harness.config import parse_hyperparam
+    from test_gpu_harness import PROTO
+    F = _F()
+    hp = parse_hyperparam(PROTO.format(log=str(tmp_path / "run"), data=str(tmp_path), extra=""))
+    torch.manual_seed(0)
+    model, _ = train.build_model(hp, cuda_device)
+    crit = torch.nn.CrossEntropyLoss()
+    g = torch.Generator().manual_seed(4)
+    batches = [(torch.randn(4, 3, 32, 32, generator=g).to(cuda_device),
+                torch.randint(0, 10, (4,), generator=g).to(cuda_device)) for _ in range(2)]
+    model.train()
+    crit(model(batches[0][0]), batches[0][1]).backward()  # one training step's forward + backward initialises it
+    for p in model.parameters():
+        p.grad = None
+    with_opt = train.validate(batches, model, crit, hp)
+    monkeypatch.setattr(F, "_INFERENCE", False)
+    without = train.validate(batches, model, crit, hp)
+    assert with_opt == without
+    assert all(np.isfinite(v) for v in with_opt)
