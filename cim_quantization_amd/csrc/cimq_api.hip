@@ -1,8 +1,8 @@
 // cimq_api.hip -- the extern "C" boundary of libcimq.so (declared in include/cimq.h).
 // Host-side geometry validation, ctx / workspace carving and the kernel launch sequences
 // that replace get_cim_output_signed.forward / backward (models/_modules/lsq.py:92-386).
-#define CIMQ_TU_MAIN
 #include "cimq_host.h"
+#include "cimq_prep.hip"
 #include "cimq_lsq.hip"
 
 using namespace cimq;

@@ -17,23 +17,12 @@
 //   grad_alpha: sum_m code * g per (pair, o)
 // All sums are fixed-order (per-wave registers / LDS regions added in wave order): bit-identical run
 // to run, no atomics.
-#pragma once
 #include <type_traits>
 
-#include "cimq_fused.hip"
+#include "cimq_bwd_dev.h"
+#include "cimq_fwd_stage.h"
 
 namespace cimq {
-
-struct VC1 {
-  int lw;       // log2(W)
-  int R;        // output rows per step (128 / W)
-  int nsteps;   // H / R
-  int RH, WP;   // staged input rows per step ((R - 1) + 3) and their word pitch (W + 2)
-  int SWD, NSEG, RSLOT;  // ring geometry (as V7)
-  int NCPBT;    // wcy blocks
-  int lcin;     // log2(C) or -1
-  unsigned o_xp, o_hp, o_ptab, o_prm, o_cel, o_g, o_ring, o_gal, o_red, o_e, o_wk, o_wc, lds;
-};
 
 template <bool LSQ>
 __global__ __launch_bounds__(512) void cim_bwd_c1_kernel(Geo g, VC1 v, const uint8_t* __restrict__ xcf,
@@ -214,7 +203,6 @@ __global__ __launch_bounds__(512) void cim_bwd_c1_kernel(Geo g, VC1 v, const uin
       float qs[NB];  // code * g over the lane's 4 pixels, per pair (k, j)
 #pragma unroll
       for (int j = 0; j < NB; ++j) qs[j] = 0.f;
-#ifndef CIMQ_EXP_C1_NOPAIRS  // attribution builds only (tools/kernel_experiment.py)
       auto addf = [](int& acc, bool pass, float c) { acc = __float_as_int(__int_as_float(acc) + (pass ? c : 0.f)); };
       // one pair: its partial sums (MFMA), STE pass bits into D_j / E_k, code * g into qs[j]; the
       // literal-ADC form (degenerate alpha, rare) and a non-standard mask take separate loops so the
@@ -301,7 +289,6 @@ __global__ __launch_bounds__(512) void cim_bwd_c1_kernel(Geo g, VC1 v, const uin
         else if (stdm) pairs(F{}, T{});
         else pairs(F{}, F{});
       }
-#endif
       // grad_alpha partials of slice k's pairs, channel r16, this wave's 16 pixels: the four 16-lane
       // rows summed by two half-wave swaps (no LDS), then lane row g4 adds pairs j = g4 and g4 + 4 to
       // the wave's LDS region (one read-modify-write per lane instead of one per pair)

@@ -2,7 +2,6 @@
 // libcimq kernels.  Compiled only for gfx950 (CDNA4): 64-lane waves, MFMA int8/bf16.
 #pragma once
 
-#include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 
 // every kernel's lane math (16-lane MFMA rows, xor-32 butterflies, threadIdx >> 6 wave ids)
@@ -10,64 +9,11 @@
 #if defined(__HIP_DEVICE_COMPILE__) && defined(__AMDGCN_WAVEFRONT_SIZE) && __AMDGCN_WAVEFRONT_SIZE != 64
 #error "libcimq assumes 64-lane wavefronts (gfx9 CDNA targets)"
 #endif
-#include <stdint.h>
+#include "cimq_types.h"
 
 // The kernels assume 64-lane waves (shuffle butterflies over 32..1, threadIdx >> 6 as the
 // wave id): build.py accepts only gfx9 (wave64-only) targets.
 namespace cimq {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-
-enum AdcMode { ADC_FP = 0, ADC_SIGN = 1, ADC_TERNARY = 2, ADC_MULTI = 3 };
-// cimq_conv_desc.adc_variant & 0xFF (include/cimq.h CIMQ_ADC_*)
-enum AdcVariant { VAR_LIBRARY = 0, VAR_STOCHASTIC = 1, VAR_SHIFT_ROUND = 2, VAR_SHIFT_SIGN = 3 };
-
-// Problem geometry, computed once on the host (cimq_api.hip) and passed by value.
-struct Geo {
-  int B, C, H, W, O, KH, KW, SH, SW, PH, PW, Ho, Wo;
-  int P, M, K, KHW, HW;
-  int xbar, T, KS, KTP;    // KS: 64-deep int8 K-steps per tile, KTP: LDS row pitch (bytes)
-  int FBT;                 // 16-wide f-blocks per tile (ceil(xbar/16))
-  int nbw, nba, bsw, bsa, NBP;  // NBP: bytes per input element in the packed act-code array
-  int Opad, OB16, NBLK, NKS;    // Opad=roundup(O,16); NBLK = nbw*Opad/16; NKS = ceil(NBLK/2)
-  int mode;
-  float qn, qp, thr_hi, thr_lo;  // ADC range; backward clamp thresholds fl32(Qp+1e-5), fl32(Qn-1e-5)
-  int input_kind;
-  float lsq_qp;
-  int psmax;               // bound on |partial sum| used by the threshold search
-  long long Nin;           // B*C*H*W
-  int onchw;               // out / grad_out layout: 0 = [B, P, O] (the Function's), 1 = NCHW (the module's)
-  int variant;             // AdcVariant; anything but VAR_LIBRARY runs the literal (general) kernels
-  int ps_int8;             // partial sums pass an int8 buffer before the ADC (scale_shift.py:401)
-  // host side, cimq_conv_desc.options (two halves of what was one int, so that the struct every kernel takes by
-  // value keeps its size and its offsets): CIMQ_OPT_RECOMPUTE -- the module backward recomputes partial sums --
-  // and CIMQ_OPT_INFERENCE -- forward only, nothing written that a backward would read
-  short recompute, inference;
-  uint32_t seed_lo, seed_hi;  // VAR_STOCHASTIC: Philox key
-  const unsigned char* wbase;  // host side: the weight-side ctx regions (cimq_lsq_desc.wprep); null: inside ctx
-};
-static_assert(sizeof(Geo) == 200, "Geo is every kernel's first argument: keep its size and offsets");
-
-// Per-(tile i, a-slice j, w-slice k, out-channel o) ADC / STE parameters, SoA.
-// index: ((i*nba + j)*nbw + k)*Opad + o
-struct Params {
-  int* thi;     // forward: ps >= thi -> code +1   (ternary mode)
-  int* tlo;     // forward: ps <= tlo -> code -1
-  int* mlo;     // backward: STE passes iff (unsigned)(ps - mlo) <= (unsigned)mhi (lsq.py:310-313)
-  int* mhi;     //   ... mhi holds the interval span
-  float* coef;  // alpha_q * binary_mask  (ternary / sign)
-  float* alpha; // alpha_q (literal paths)
-  float* ckj;   // [3][nbw*nba]: mask as float, cE = 2^-(bsa*j)*mask, cD = 2^-(bsw*k)*mask
-  int* flags;   // [0]: literal ADC (degenerate alpha / scales), [1..3] reserved
-  float* beta;  // shift of the scale + shift ADC variants (0 otherwise)
-  float* bsum;  // [Opad]: sum over (i, k, j) of beta * binary_mask (shift_fast forward)
-};
-
-__host__ __device__ inline int pidx(const Geo& g, int i, int j, int k, int o) {
-  return ((i * g.nba + j) * g.nbw + k) * g.Opad + o;
-}
 
 // ---------------------------------------------------------------------------------------
 // exact fp32 emulation of the reference's torch op sequence (compiled with -ffp-contract=off)
@@ -189,15 +135,6 @@ __device__ inline bool has_alpha(const Geo& g) {
   return g.mode == ADC_SIGN || g.mode == ADC_TERNARY || g.variant == VAR_SHIFT_ROUND || g.variant == VAR_SHIFT_SIGN;
 }
 __device__ inline bool is_shift(const Geo& g) { return g.variant == VAR_SHIFT_ROUND || g.variant == VAR_SHIFT_SIGN; }
-// The scale / shift "round" ADC of Conv2dLSQCiM(adc_shift=True) on the threshold fast path: 1.5 bits
-// with the library's range (codes -1, 0, 1), the library's fp16 partial sums (no int8 buffer), every
-// |ps| exact in fp16.  v = (u - beta) / alpha is then a monotone step function of the integer ps,
-// captured by integer thresholds like the library ADC; the output gains sum beta * mask per channel.
-__host__ __device__ inline bool shift_fast(const Geo& g) {
-  return g.variant == VAR_SHIFT_ROUND && g.mode == ADC_TERNARY && !g.ps_int8 && g.qp == 1.f && g.qn == -1.f &&
-         g.psmax <= 2048;
-}
-
 // torch.sign: NaN propagates
 __device__ inline float sign_nan(float v) { return (v > 0.f) ? 1.f : ((v < 0.f) ? -1.f : ((v != v) ? v : 0.f)); }
 
@@ -315,6 +252,8 @@ __device__ inline void split3(float a, uint16_t& hi, uint16_t& mid, uint16_t& lo
   lo = bf16_bits(r2);
 }
 
+__device__ inline size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
+
 __device__ inline v8bf as_v8bf(v4i x) { return __builtin_bit_cast(v8bf, x); }
 __device__ inline v4i as_v4i(v8bf x) { return __builtin_bit_cast(v4i, x); }
 
@@ -326,6 +265,94 @@ __device__ inline float rows4_sum(float v) {
   const float h = __uint_as_float(a[0]) + __uint_as_float(a[1]);
   const auto c = __builtin_amdgcn_permlane32_swap(__float_as_uint(h), __float_as_uint(h), false, false);
   return __uint_as_float(c[0]) + __uint_as_float(c[1]);
+}
+
+// fp32 -> three bf16 parts (hi + mid + lo), 8 values -> 3 MFMA operands (split3x8)
+// (a, b) -> bf16 hi / mid / lo pairs, low half a: round-to-nearest-even conversions and exact fp32
+// remainders (hi + mid + lo reproduces a to fp32 accuracy), one v_cvt_pk_bf16_f32 per level for both values
+__device__ inline uint32_t pk_bf16(float a, float b) {
+  uint32_t r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+__device__ inline void split3_pk(float a, float b, uint32_t& hi, uint32_t& mid, uint32_t& lo) {
+  hi = pk_bf16(a, b);
+  float ra = a - __uint_as_float(hi << 16), rb = b - __uint_as_float(hi & 0xffff0000u);
+  mid = pk_bf16(ra, rb);
+  ra = ra - __uint_as_float(mid << 16);
+  rb = rb - __uint_as_float(mid & 0xffff0000u);
+  lo = pk_bf16(ra, rb);
+}
+__device__ inline void split3x8(const float (&v)[8], v8bf& bh, v8bf& bm, v8bf& bl) {
+  v4i h, m, l;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    uint32_t a, b, c;
+    split3_pk(v[2 * e], v[2 * e + 1], a, b, c);
+    h[e] = (int)a;
+    m[e] = (int)b;
+    l[e] = (int)c;
+  }
+  bh = __builtin_bit_cast(v8bf, h);
+  bm = __builtin_bit_cast(v8bf, m);
+  bl = __builtin_bit_cast(v8bf, l);
+}
+
+// literal (threshold-free) per-partial-sum paths, kept out of line: degenerate alpha / scales
+__device__ __noinline__ inline float adc_literal_sum(v4i ps, int mode, float sw, float sa, float al, float qn,
+                                                    float qp, float mk, int r) {
+  return adc_literal(ps[r], mode, sw, sa, al, qn, qp) * mk;
+}
+__device__ __noinline__ inline float ste_literal(int p, int mode, float sw, float sa, float al, float thr_hi,
+                                                float thr_lo) {
+  const float bb = psb_literal(p, mode, sw, sa, al);
+  return ste_pass(bb, thr_hi, thr_lo) ? 1.f : 0.f;
+}
+__device__ __noinline__ inline float code_literal(int p, int mode, float sw, float sa, float al, float qn, float qp,
+                                                 float thr_hi, float thr_lo) {
+  const float bb = psb_literal(p, mode, sw, sa, al);
+  return alpha_code_literal(bb, mode, qn, qp, thr_hi, thr_lo);
+}
+// the shift ADC's literal path (shift_fast layers with a degenerate alpha / beta / scale): adc * mask
+// (scale_shift.py:421-429) and the state bits of the partial sum (v = (u - beta) / alpha: STE pass
+// unless v >= Qp + 1e-5 or v <= Qn - 1e-5, :469-484; code clamp(rint(v), -1, 1))
+// (scalar arguments only, as the helpers above: a Geo by reference would put it on the stack and
+// cost the whole kernel registers; shift_fast fixes ps_int8 = 0 and the range -1 .. 1)
+__device__ __noinline__ inline float shift_adc_literal(int p, float sw, float sa, float al, float be, float mk) {
+  const float u = (ps_half(p) * sw) * sa;  // u_var without the int8 buffer
+  const float v = (u - be) / al;
+  const float t = clamp_nan(rintf(v), -1.f, 1.f) * al;
+  return (t + be) * mk;
+}
+__device__ __noinline__ inline uint32_t shift_state_literal(int p, float sw, float sa, float al, float be,
+                                                           float thr_hi, float thr_lo) {
+  const float v = (((ps_half(p) * sw) * sa) - be) / al;
+  const bool pass = !(v >= thr_hi || v <= thr_lo);
+  const float code = clamp_nan(rintf(v), -1.f, 1.f);
+  return (pass ? 1u : 0u) | ((code != 0.f) ? 2u : 0u) | ((code < 0.f) ? 4u : 0u);
+}
+
+// state bits of one partial sum: bit 0 STE pass (lsq.py:310-313), bit 1 ADC code != 0, bit 2
+// ADC code < 0 (lsq.py:321-332)
+__device__ inline uint32_t st_bits(bool pass, float code) {
+  return (pass ? 1u : 0u) | ((code != 0.f) ? 2u : 0u) | ((code < 0.f) ? 4u : 0u);
+}
+
+// shift a bit in: x * 2 + c in one v_addc_co_u32 whose carry-in is the compare's lane mask
+// (the compiler spends a cndmask + shift/or on the plain expression)
+__device__ inline uint32_t shin(uint32_t x, uint64_t m) {
+  uint32_t r;
+  uint64_t co;
+  asm("v_addc_co_u32_e64 %0, %1, %2, %2, %3" : "=v"(r), "=s"(co) : "v"(x), "s"(m));
+  return r;
+}
+// ternary ADC term: hi ? cf : (lo ? -cf : 0) from the two compare masks (two cndmasks; the
+// plain expression makes the compiler rematerialise the masks as 0/1 vectors)
+__device__ inline float adc3(float cf, uint64_t mhi, uint64_t mlo) {
+  float a, r;
+  asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(a) : "v"(cf), "s"(mhi));
+  asm("v_cndmask_b32_e64 %0, %1, -%2, %3" : "=v"(r) : "v"(a), "v"(cf), "s"(mlo));
+  return r;
 }
 
 }  // namespace cimq

@@ -23,30 +23,11 @@
 // grad_w accumulates in LDS across the image's steps (or goes straight to the slab when the image
 // is one step); the slabs [image][tile][row][o] are summed in a fixed order by the module tail /
 // reduce kernels: bit-identical run to run, no atomics.
-#pragma once
 #include <type_traits>
 
-#include "cimq_v7.hip"
+#include "cimq_bwd_dev.h"
 
 namespace cimq {
-
-struct V9 {
-  int lw;        // log2(W)
-  int R;         // output rows per step (64 / W)
-  int nsteps;    // H / R
-  int SWD, NSEG; // ring segments (as V7): min(16, W) columns, W / SWD per row
-  int RSLOT;     // ring rows
-  int NCPBT;     // (c, kh)-row blocks of 4 per tile (the v8 grad_x operand wcy)
-  int lcin;      // log2(C), or -1
-  int NCG;       // most input channels one tile touches (staged plane channels)
-  int CPITCH;    // plane channel pitch (bf16): PROWS * W + 8 (the 8-element zero pad)
-  int KWP;       // (j, kw) plane pitch (bf16)
-  int PROWS;     // staged input rows per step: R + 2
-  int NGRP;      // 16-row groups of K
-  int gwl;       // 1: grad_w accumulates in LDS across steps; 0: one step per image, units write the slab
-  int nitems;    // plane staging items per unit: NCG * PROWS * W / 8 (<= 512)
-  unsigned o_ring, o_cel, o_red, o_plane, o_gwl, o_gal, o_st, o_g, lds;  // LDS layout (bytes)
-};
 
 template <int NB, int OBX, bool LSQ>
 __global__ __launch_bounds__(512) void cim_bwd_fused_kernel(Geo g, V9 v, const uint32_t* __restrict__ st,
@@ -200,7 +181,6 @@ __global__ __launch_bounds__(512) void cim_bwd_fused_kernel(Geo g, V9 v, const u
         if (i == 0) *reinterpret_cast<float4*>(gl + (t >> 4) * GP + (t & 15) * 4) = gvc[q];
       }
     }
-#ifndef CIMQ_EXP_F_NOSTAGE  // attribution builds only (tools/kernel_experiment.py): skip a part of the kernel
     if (it < v.nitems) {
 #pragma unroll
       for (int kw = 0; kw < 3; ++kw) {
@@ -218,7 +198,6 @@ __global__ __launch_bounds__(512) void cim_bwd_fused_kernel(Geo g, V9 v, const u
         }
       }
     }
-#endif
     // the next unit's loads go out now, behind this unit's work
     if (u + 1 < nunits) {
       const int s_n = (u + 1) / g.T, i_n = (u + 1) - s_n * g.T;
@@ -233,7 +212,6 @@ __global__ __launch_bounds__(512) void cim_bwd_fused_kernel(Geo g, V9 v, const u
     auto unit_roles = [&](auto smc) {
       constexpr bool SMC = decltype(smc)::value;
     if (gxw) {
-#ifndef CIMQ_EXP_F_NOGX
       // ================= grad_x: G from the state words, MFMA against wcy, ring =================
       v8bf Gh[NKS], Gm[NKS], Gl[NKS];
       uint4 sq[OBX];
@@ -276,31 +254,15 @@ __global__ __launch_bounds__(512) void cim_bwd_fused_kernel(Geo g, V9 v, const u
       v4i anx[NKS];
 #pragma unroll
       for (int sk = 0; sk < NKS; ++sk) anx[sk] = wt[sk * 64];
-#ifdef CIMQ_EXP_F_PF2  // experiment: the weight blocks two (c, kh)-blocks ahead
-      v4i anx2[NKS];
-      if (ncb > 1) {
-#pragma unroll
-        for (int sk = 0; sk < NKS; ++sk) anx2[sk] = wt[(NKS + sk) * 64];
-      }
-#endif
 #pragma unroll 1
       for (int cb = 0; cb < ncb; ++cb) {
         v4i acur[NKS];
 #pragma unroll
         for (int sk = 0; sk < NKS; ++sk) acur[sk] = anx[sk];
-#ifdef CIMQ_EXP_F_PF2
-#pragma unroll
-        for (int sk = 0; sk < NKS; ++sk) anx[sk] = anx2[sk];
-        if (cb + 2 < ncb) {
-#pragma unroll
-          for (int sk = 0; sk < NKS; ++sk) anx2[sk] = wt[((cb + 2) * NKS + sk) * 64];
-        }
-#else
         if (cb + 1 < ncb) {
 #pragma unroll
           for (int sk = 0; sk < NKS; ++sk) anx[sk] = wt[((cb + 1) * NKS + sk) * 64];
         }
-#endif
         v4f acc = v4f{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int sk = 0; sk < NKS; ++sk) {
@@ -329,9 +291,7 @@ __global__ __launch_bounds__(512) void cim_bwd_fused_kernel(Geo g, V9 v, const u
           }
         }
       }
-#endif
     } else {
-#ifndef CIMQ_EXP_F_NOGW
       // ================= grad_w (+ grad_alpha): B = g * D_j, A from the planes =================
       const int flo = i * g.xbar;
       const int ngt = (min(g.xbar, g.K - flo) + 15) >> 4;  // row groups of tile i
@@ -433,7 +393,6 @@ __global__ __launch_bounds__(512) void cim_bwd_fused_kernel(Geo g, V9 v, const u
           }
         }
       }
-#endif
     }
     };
     if (std_mask) unit_roles(std::true_type{});

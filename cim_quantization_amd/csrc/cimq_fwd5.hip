@@ -21,104 +21,10 @@
 // backward (bit 3*(k*3 + j) + {0 STE pass, 1 code != 0, 2 code < 0}), the backward ctx words of the rows
 // the m-tile owns; the ADC sum runs in the same order (tiles ascending, k and j descending), so out is
 // bit-identical to that kernel's.
-#pragma once
-#include "cimq_kernels_v3.hip"
+#include "cimq_fwd_stage.h"
 
 namespace cimq {
 
-constexpr int kF5MaxTc = 8;   // (tile, channel-block) pairs: 2 / 4 / 8 for C = 16 / 32 / 64 at xbar 128
-constexpr int kF5MaxGrp = 4;  // tile groups
-
-// host-computed plan (cimq_host.h: f5_plan)
-struct F5 {
-  int lwo;                 // log2(Wo)
-  int lwi;                 // log2(W)
-  int codes;               // 1: the ctx holds one code byte per element (ctx_codes: grad_w is cim_bwd_gw5_kernel)
-  int IPM;                 // images per 128-pixel m-tile (1: the m-tile is R output rows of one image)
-  int R, RH, WP;           // output rows per image slot, patch rows (R-1)*SH + 3, patch row length W + 2
-  int NCBP;                // channel blocks one patch holds (the widest group's span)
-  int nmt;                 // M / 128
-  int ntc;                 // (tile, channel-block) pairs
-  int ngrp;                // tile groups
-  int tcmax;               // most pairs in one group
-  // (int tables: the kernel indexes them with wave-uniform runtime indices, which scalar loads serve
-  // only at dword granularity -- byte tables became per-lane global loads of the kernel arguments)
-  int tc0[kF5MaxTc + 1];  // first pair of tile i (tc0[T] = ntc)
-  int tcb[kF5MaxTc];      // channel block of pair t
-  int gt0[kF5MaxGrp + 1]; // first tile of group q (gt0[ngrp] = T)
-  int gcb0[kF5MaxGrp], gcb1[kF5MaxGrp];  // channel-block span of group q
-  int gown[kF5MaxGrp];    // first channel block whose ctx words group q writes
-};
-
-// the part of the plan the weight prologue needs (kept small: it travels in every PrepJob)
-struct F5W {
-  int ntc;
-  unsigned char tc0[kF5MaxTc + 1];
-  unsigned char tcb[kF5MaxTc];
-};
-inline F5W f5w_of(const F5& v) {
-  F5W w;
-  w.ntc = v.ntc;
-  for (int i = 0; i <= kF5MaxTc; ++i) w.tc0[i] = v.tc0[i];
-  for (int i = 0; i < kF5MaxTc; ++i) w.tcb[i] = v.tcb[i];
-  return w;
-}
-
-// the weight operand of one (ob, pair t, K-step s, w-slice k) fragment, lane l: output channel
-// o = ob*16 + (l & 15), byte e = w-slice k of weight (c = cb*16 + e, position p = 4s + (l >> 4)),
-// rint(slice) as int8 as in wfrag_item; zero when p > 8 or the row f = c*9 + p is outside tile i
-// wf5[((ob*ntc + t)*3 + s)*3 + k][64]
-template <typename WS>
-__device__ inline void wf5_item(const Geo& g, const F5W& v, const WS& ws, v4i* __restrict__ wf5, int t) {
-  const int lane = t & 63;
-  int r = t >> 6;
-  const int k = r % 3;
-  r /= 3;
-  const int s = r % 3;
-  r /= 3;
-  const int tc = r % v.ntc;
-  const int ob = r / v.ntc;
-  int i = 0;
-  while (v.tc0[i + 1] <= tc) ++i;
-  const int flo = i * g.xbar, fhi = min(flo + g.xbar, g.K);
-  const int p = 4 * s + (lane >> 4);
-  const int n = k * g.Opad + ob * 16 + (lane & 15);
-  uint32_t wd[4] = {0, 0, 0, 0};
-  if (p < 9) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int c = v.tcb[tc] * 16 + e;
-      const int f = c * 9 + p;
-      int val = 0;
-      if (c < g.C && f >= flo && f < fhi) val = clamp_i8(wslice(g, ws, f, n));
-      wd[e >> 2] |= ((uint32_t)(uint8_t)(int8_t)val) << (8 * (e & 3));
-    }
-  }
-  v4i o;
-  o.x = (int)wd[0]; o.y = (int)wd[1]; o.z = (int)wd[2]; o.w = (int)wd[3];
-  wf5[t] = o;
-}
-
-// act_words_tab's table entry with the clamp moved after the rounding (rint(clamp(q, 0, Qp)) = clamp(rint(q),
-// 0, Qp) for integer bounds): v_cvt_i32_f32 saturates +-inf and the NaN test picks the table's NaN entry
-__device__ inline uint2 act_words_q5(float v, float sa, int qp, int nan_e, const uint32_t* lut, int& code) {
-  const float q = v / sa;
-  int e;
-  asm("v_cvt_i32_f32 %0, %1" : "=v"(e) : "v"(rintf(q)));
-  e = min(max(e, 0), qp);
-  e = (q == q) ? e : nan_e;
-  code = e;
-  return *reinterpret_cast<const uint2*>(lut + 2 * e);
-}
-
-// n / d for 0 <= n < 2^20, d < 2^10 (inv = 1 / d in fp32): exact, no correction step needed
-__device__ inline int sdiv(int n, float inv) { return (int)(((float)n + 0.5f) * inv); }
-
-// LDS byte offset of the patch element (row, channel-block slot, col) of one image slot, slice 0
-// (slice j at + 16 j)
-__device__ inline int f5_off(int NCB, int WP, int row, int cb, int col) { return ((row * NCB + cb) * WP + col) * 48; }
-
-#ifdef CIMQ_TU_FWD5  // defined in its launcher's translation unit only
 // NOB 16-channel output blocks per block (512 threads each): the NOB halves share the block's staged
 // activation patch (f5_plan: NOB = 2 where OB16 is even, one 1024-thread block per CU)
 // WST: write the backward's state words and ctx (false where the module backward recomputes the partial sums,
@@ -284,12 +190,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512 * NOB, 512 * NOB), amd
         }
       };
       // (one instance of each phase: the first round, which every thread runs, holds the barrier)
-#ifdef CIMQ_EXP_FWD5_NOSTAGE  // attribution builds only: the patch staged for the block's first m-tile only
-      if (mt != (int)blockIdx.x) {
-        __syncthreads();
-        if (v.ngrp > 1) stage_b(q);
-      } else
-#endif
       for (int base = (int)threadIdx.x, first = 1; first || base < n; base += SU * NT, first = 0) {
         ldx(base);
         if (first) {
@@ -320,13 +220,9 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512 * NOB, 512 * NOB), amd
             for (int k = 0; k < 3; ++k)
 #pragma unroll
               for (int j = 0; j < 3; ++j)
-#ifdef CIMQ_EXP_FWD5_NOMFMA  // attribution builds only (tools/kernel_experiment.py): wrong results
-                ps[k * 3 + j] = (first && s == 0) ? (a[j] ^ w[k]) : (ps[k * 3 + j] + (a[j] ^ w[k]));
-#else
                 ps[k * 3 + j] = (first && s == 0)
                                     ? __builtin_amdgcn_mfma_i32_16x16x64_i8(a[j], w[k], v4i{0, 0, 0, 0}, 0, 0, 0)
                                     : __builtin_amdgcn_mfma_i32_16x16x64_i8(a[j], w[k], ps[k * 3 + j], 0, 0, 0);
-#endif
           }
         };
         ksteps(v.tc0[i], true);  // f5_plan: every tile has at least one pair
@@ -345,10 +241,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512 * NOB, 512 * NOB), amd
 #pragma unroll
               for (int r = 0; r < 4; ++r) {
                 const int p = ps[k * 3 + j][r];
-#ifdef CIMQ_EXP_FWD5_NOADC
-                acc[r] += (float)(p ^ pv.x) * cf;
-                continue;
-#endif
                 const uint64_t mhi = __builtin_amdgcn_ballot_w64(p >= pv.x);
                 const uint64_t mlo = __builtin_amdgcn_ballot_w64(p <= pv.y);
                 const uint64_t mps = WST ? __builtin_amdgcn_ballot_w64((unsigned)(p - pv.z) <= (unsigned)pv.w) : 0ull;
@@ -393,6 +285,5 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512 * NOB, 512 * NOB), amd
     }
   }
 }
-#endif  // CIMQ_TU_FWD5
 
 }  // namespace cimq

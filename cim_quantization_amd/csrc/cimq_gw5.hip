@@ -18,32 +18,15 @@
 //     keeping its grad_w / grad_alpha sums in registers across the block's m-tiles.  At the end the 8
 //     waves are summed in LDS in wave order and the block writes its part of the chunk's slab (the
 //     module epilogue sums the slabs in chunk order: deterministic).
-#pragma once
 #include <type_traits>
 
-#include "cimq_v7.hip"
+#include "cimq_bwd_dev.h"
 
 namespace cimq {
 
 // n / d for 0 <= n < 2^20, d < 2^10 (inv = 1 / d in fp32): exact
 __device__ inline int sdiv5(int n, float inv) { return (int)(((float)n + 0.5f) * inv); }
 
-// the code -> ctx word table's entry for out-of-image elements (a zero word; codes are <= 256)
-constexpr int kZeroCode = 259;
-
-struct G5 {
-  int lwo;     // log2(Wo)
-  int lwi;     // log2(W)
-  int codes;   // 1: the ctx holds one activation code byte per element (the forward was cim_fwd5_kernel with
-               // ctx_codes): expanded through the act word table, as the forward's staging does
-  int IPM;     // images per 128-pixel m-tile (1: the m-tile is R output rows of one image)
-  int R, RH, WP;  // output rows per image slot, staged input rows R + 2, patch row length W + 2
-  int nmt;     // M / 128
-  int nst;     // m-tiles per block (chunk)
-  int nchunks; // blocks = slab chunks
-};
-
-#if defined(CIMQ_TU_GW5) || defined(CIMQ_TU_GXW5)
 // SS: the conv stride (1 or 2): a compile-time constant, so the pixel-pair offsets stay immediates
 // SP: the row blocks of the block's two tiles split at fb = 8 - (cb mod 8) (its first 144 cb mod 128 rows lie in the
 // first tile), compiled in so that the MFMA chains of consecutive row blocks are not separated by branches and
@@ -121,11 +104,7 @@ __device__ __forceinline__ void gw5_body(int bx, int by, const Geo& g, const G5&
   const int HWi = g.H * g.W;
   const float invRH = 1.f / (float)v.RH, invIPM = 1.f / (float)v.IPM;
   const int tpi = g.P >= 128 ? g.P / 128 : 1;
-#ifdef CIMQ_EXP_GW5_EMPTY  // attribution builds only: the prologue and the slab epilogue without any m-tile
-  const int mt_lo = bx * v.nst, mt_hi = mt_lo;
-#else
   const int mt_lo = bx * v.nst, mt_hi = min(mt_lo + v.nst, v.nmt);
-#endif
   // the m-tile loop with the block's row-block split SPL compiled in (0: the per-block table)
   auto mtiles = [&](auto spc) __attribute__((always_inline)) {
     constexpr int SPL = decltype(spc)::value;
@@ -141,12 +120,7 @@ __device__ __forceinline__ void gw5_body(int bx, int by, const Geo& g, const G5&
     const int sl = pw / PI, pin0 = pw - sl * PI;  // image slot, pixel within the slot
     const int b = b0 + sl;
     float4 gq;
-#ifdef CIMQ_EXP_GW5_NOLOAD  // attribution builds only: no global reads in the m-tile loop (wrong results)
-    gq = make_float4(1e-3f * o, 2e-3f, 3e-3f * mt, 4e-3f);
-    if (false) {
-#else
     if (g.onchw) {
-#endif
       gq = *reinterpret_cast<const float4*>(gout + ((size_t)b * g.O + o) * g.P + p0 + pin0);
     } else {  // the Function path's [B, P, O]
       const float* gp = gout + ((size_t)b * g.P + p0 + pin0) * g.O + o;
@@ -159,11 +133,7 @@ __device__ __forceinline__ void gw5_body(int bx, int by, const Geo& g, const G5&
       for (int q = 0; q < 2; ++q)
 #pragma unroll
         for (int e = 0; e < 4; ++e)
-#ifdef CIMQ_EXP_GW5_NOLOAD
-          sq[q][e] = (uint32_t)(m * 2654435761u + e * 40503u + o) & 0x7FFFFFFu;
-#else
           sq[q][e] = q < ntl ? st[((size_t)(i_lo + q) * g.M + m + e) * g.O + o] : 0u;
-#endif
     }
     // A-ready patch: input rows oh0 * SH - 1 .. (oh0 + R - 1) * SH + 1 of each image slot, the block's 16
     // channels; item = (c, slot, row, col) (W a power of two; the divisions by RH and CH as exact
@@ -188,11 +158,7 @@ __device__ __forceinline__ void gw5_body(int bx, int by, const Geo& g, const G5&
         // (a code byte, expanded below through the LDS table, or the word itself)
         // (unsigned offsets: the loads take the scalar base + 32-bit offset form)
         const uint32_t xi = ok ? (uint32_t)(xb + (slt * g.C + c) * HWi + row * g.W + col) : 0u;
-#ifdef CIMQ_EXP_GW5_NOLOAD
-        const uint32_t w = CODES ? (xi & 7u) : xi * 0x010203u;
-#else
         const uint32_t w = CODES ? (uint32_t)reinterpret_cast<const uint8_t*>(xcb)[xi] : xcb[xi];
-#endif
         wv[u] = ok ? w : (CODES ? (uint32_t)kZeroCode : 0u);
       }
     };
@@ -235,11 +201,7 @@ __device__ __forceinline__ void gw5_body(int bx, int by, const Geo& g, const G5&
         for (int q = 0; q < 2; ++q) {
           if (q >= ntl) break;
           const uint32_t s0 = sq[q][e0], s1 = sq[q][e0 + 1];
-#ifdef CIMQ_EXP_GW5_NOGA
-          if (false) {
-#else
           if (own[q]) {
-#endif
             // grad_alpha partials (lsq.py:321-333): code * g, the code the signed 2-bit field at bit 3kj + 1
 #pragma unroll
             for (int kj = 0; kj < 9; ++kj) {
@@ -283,10 +245,6 @@ __device__ __forceinline__ void gw5_body(int bx, int by, const Geo& g, const G5&
             const int ao = (int)((aoffp[fb >> 1] >> (16 * (fb & 1))) & 0xFFFFu);
             const uint2 a0 = pat[ao + poff], a1 = pat[ao + poff + SS];
             const v8bf a = as_v8bf(v4i{(int)a0.x, (int)a0.y, (int)a1.x, (int)a1.y});
-#ifdef CIMQ_EXP_GW5_NOMFMA
-            acc[fb][0] += (float)a[0] + (float)bh[0] + (float)bm[1] + (float)bl[2];
-            continue;
-#endif
             acc[fb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bh, acc[fb], 0, 0, 0);
             acc[fb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bm, acc[fb], 0, 0, 0);
             acc[fb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bl, acc[fb], 0, 0, 0);
@@ -304,20 +262,6 @@ __device__ __forceinline__ void gw5_body(int bx, int by, const Geo& g, const G5&
   }
 
   // the block's part of its chunk's slab: the 8 waves summed in LDS in wave order
-#ifdef CIMQ_EXP_GW5_NOEPI
-  {
-    float* gws = gw_slab + (size_t)bx * g.T * g.FBT * 16 * g.Opad;
-    float t = 0.f;
-#pragma unroll
-    for (int fb = 0; fb < 9; ++fb) t += acc[fb][0] + acc[fb][1] + acc[fb][2] + acc[fb][3];
-#pragma unroll
-    for (int q = 0; q < 2; ++q)
-#pragma unroll
-      for (int kj = 0; kj < 9; ++kj) t += ga[q][kj];
-    gws[threadIdx.x] = t;
-    return;
-  }
-#endif
   __syncthreads();
   float* red = reinterpret_cast<float*>(smem);  // [8 waves][FC row blocks][64 lanes][4] (g5_plan: >= 24 KB)
   const size_t rows = (size_t)g.T * g.FBT * 16;
@@ -366,9 +310,7 @@ __device__ __forceinline__ void gw5_body(int bx, int by, const Geo& g, const G5&
     __syncthreads();
   }
 }
-#endif  // CIMQ_TU_GW5 || CIMQ_TU_GXW5
 
-#ifdef CIMQ_TU_GW5
 template <int SS, bool CODES, int SP>
 __global__ __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_per_eu(4, 4)))
 void cim_bwd_gw5_kernel(Geo g, G5 v, const uint32_t* __restrict__ st, const uint32_t* __restrict__ xcb, Params pp,
@@ -376,6 +318,5 @@ void cim_bwd_gw5_kernel(Geo g, G5 v, const uint32_t* __restrict__ st, const uint
                         float* __restrict__ ga_slab) {
   gw5_body<SS, CODES, SP>((int)blockIdx.x, (int)blockIdx.y, g, v, st, xcb, pp, gout, cal, gw_slab, ga_slab);
 }
-#endif  // CIMQ_TU_GW5
 
 }  // namespace cimq

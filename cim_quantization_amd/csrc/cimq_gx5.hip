@@ -15,63 +15,19 @@
 // tiles).  Waves: (16-pixel group, 16-channel input block); a wave whose channel block tile i does not
 // touch skips its MFMAs.  Every grad_x value is produced by one lane, stored once after the LSQ
 // backward: no fold pass, no ring, no atomics.
-#pragma once
-#include "cimq_v7.hip"
+#include "cimq_bwd_dev.h"
+#include "cimq_operands.h"
 
 namespace cimq {
 
-struct X5 {
-  int nmt;     // H / 4 * B: m-tiles of four input rows
-  int tpi;     // m-tiles per image
-  int CBN;     // 16-channel input blocks (1 or 2) = 16-channel output halves
-  int NPG;     // 16-pixel groups per m-tile: W / 4 (8 or 4); waves = NPG * CBN = 8
-  int lw;      // log2(W)
-};
-
-// weight operand of (tile i, output half h, position p, K-step s, input block cb), lane l: channel
-// c = 16 cb + (l & 15), K values kappa = 32 s + 8 (l >> 4) + e (e < 8) = (k, o) = (kappa / 16, 16 h + kappa % 16),
-// int8(slice_k) of weight (o, f = 9 c + p) as bf16 (wcy_item's values), zero for kappa >= 48 or f outside
-// tile i: wg5[((((i * CBN + h) * 9 + p) * 2 + s) * CBN + cb) * 64 + l]
-template <typename WS>
-__device__ inline void wg5_item(const Geo& g, const WS& ws, v4i* __restrict__ wg5, int t) {
-  const int CBN = g.C / 16;
-  const int lane = t & 63;
-  int r = t >> 6;
-  const int cb = r % CBN;
-  r /= CBN;
-  const int s = r & 1;
-  r >>= 1;
-  const int p = r % 9;
-  r /= 9;
-  const int h = r % CBN, i = r / CBN;
-  const int c = 16 * cb + (lane & 15);
-  const int f = c * 9 + p;
-  const int flo = i * g.xbar, fhi = min(flo + g.xbar, g.K);
-  const bool ok = c < g.C && f >= flo && f < fhi;
-  uint32_t wd[4] = {0, 0, 0, 0};
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int kap = 32 * s + 8 * (lane >> 4) + e;
-    const int k = kap >> 4, o = 16 * h + (kap & 15);
-    float val = 0.f;
-    if (ok && k < g.nbw) val = (float)to_i8_wrap(wslice(g, ws, f, k * g.Opad + o));
-    wd[e >> 1] |= (uint32_t)bf16_bits(val) << (16 * (e & 1));
-  }
-  v4i q;
-  q.x = (int)wd[0]; q.y = (int)wd[1]; q.z = (int)wd[2]; q.w = (int)wd[3];
-  wg5[t] = q;
-}
-
-#ifdef CIMQ_TU_GX5
-// the Function entry points' prologue (prep_all: w_q already quantised) builds the same operand
+// the kernel's weight operand (wg5_item, cimq_operands.h) from a quantised w_q: the Function entry points'
+// prologue (prep_all); the module prologue builds the same operand in module_prep_weights (cimq_lsq.hip)
 __global__ void prep_wg5_kernel(Geo g, const float* __restrict__ w_q, const float* __restrict__ sw_p, int total,
                                 v4i* __restrict__ wg5) {
   const WSrc ws{w_q, *sw_p, 0, 0.f, 0.f};
   for (int t = blockIdx.x * blockDim.x + threadIdx.x; t < total; t += gridDim.x * blockDim.x) wg5_item(g, ws, wg5, t);
 }
-#endif  // CIMQ_TU_GX5
 
-#if defined(CIMQ_TU_GX5) || defined(CIMQ_TU_GXW5)
 // the kernel body for workgroup bid of nblk (cim_bwd_gx5_kernel, and the first part of the grid of
 // cim_bwd_gxw5_kernel, which runs grad_w's workgroups behind it in the same launch)
 template <int CBN>  // 16-channel input blocks = output halves (X5::CBN)
@@ -120,9 +76,6 @@ __device__ __forceinline__ void gx5_body(int bid, int nblk, const Geo& g, const 
   for (int mt = bid; mt < v.nmt; mt += nblk) {
     const int b = mt / v.tpi, r0 = (mt - b * v.tpi) * 4;  // input rows r0 .. r0 + 3
     v4f acc = v4f{0.f, 0.f, 0.f, 0.f};
-#ifdef CIMQ_EXP_GX5_CHAINS
-    v4f acc1 = v4f{0.f, 0.f, 0.f, 0.f};
-#endif
     // grad_out of the m-tile's G-patch items, both output halves: read once here, used by every tile's step
     // (it was re-read per tile)
     float gvr[2][2][4];
@@ -154,11 +107,7 @@ __device__ __forceinline__ void gx5_body(int bid, int nblk, const Geo& g, const 
 #pragma unroll
       for (int u = 0; u < NWI; ++u) {
         const int idx = threadIdx.x + u * 512;
-#ifdef CIMQ_EXP_GX5_NOLOAD  // attribution builds only: no global reads in the step (wrong results)
-        if (idx < NW5) wv[u] = v4i{idx, ih2, u, 1};
-#else
         if (idx < NW5) wv[u] = wg5[ih2 * NW5 + idx];
-#endif
       }
       uint4 s4r[2];
 #pragma unroll
@@ -169,11 +118,7 @@ __device__ __forceinline__ void gx5_body(int bid, int nblk, const Geo& g, const 
         s4r[kk] = make_uint4(0u, 0u, 0u, 0u);
         if (it < NG && (unsigned)oh < (unsigned)g.Ho) {
           const int m = b * g.P + oh * g.Wo + col;
-#ifdef CIMQ_EXP_GX5_NOLOAD
-          s4r[kk] = make_uint4((uint32_t)m, (uint32_t)it, 7u, (uint32_t)i);
-#else
           s4r[kk] = *reinterpret_cast<const uint4*>(st + ((i * g.M + m) * g.O + 4 * ((it & 3) + 4 * h)));
-#endif
         }
       }
       __syncthreads();  // the previous step's (or m-tile's) MFMAs are done with the patch and weights
@@ -222,59 +167,13 @@ __device__ __forceinline__ void gx5_body(int bid, int nblk, const Geo& g, const 
           }
         }
       };
-#ifndef CIMQ_EXP_GX5_NOBUILD  // attribution builds only: the G patch left as the first step built it
       if (std_mask) build(std::true_type{});
       else build(std::false_type{});
-#else
-      if (mt == bid && i == 0) {
-        if (std_mask) build(std::true_type{});
-        else build(std::false_type{});
-      }
-#endif
       __syncthreads();
       // the wave's 16 input pixels x 16 channels: 9 positions x 2 K-steps x 3 planes, unless tile i holds
       // none of the block's rows (f = 9 c + p for c in c_lo .. c_hi)
       if (9 * c_hi + 8 < i * g.xbar || 9 * c_lo >= (i + 1) * g.xbar) continue;
       const v4i* wb = reinterpret_cast<const v4i*>(smem + OW5) + cb * 64 + lane;
-#ifdef CIMQ_EXP_GX5_DPP
-      // (tried, round 6: 5 us per launch SLOWER than the nine reads below) per kernel row kh the wave reads only
-      // the kw = 1 window; kw = 0 / 2 are its pixels shifted by one lane within each 16-lane row (DPP row_shl /
-      // row_shr: the pixels of a row are consecutive columns), the row's edge lane (r16 = 15 for kw = 0, r16 = 0
-      // for kw = 2) reading its one column outside the window by itself
-#pragma unroll
-      for (int kh = 0; kh < 3; ++kh) {
-        const uint8_t* pc = smem + (size_t)((rl + 2 - kh) * WP + iw0 + r16 + 1) * 96 + 16 * g4;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          v4i c[3];
-#pragma unroll
-          for (int pl = 0; pl < 3; ++pl) c[pl] = *reinterpret_cast<const v4i*>(pc + pl * PLANE + 64 * s);
-#pragma unroll
-          for (int kw = 0; kw < 3; ++kw) {
-            const int p = kh * 3 + kw;
-            const v8bf w = as_v8bf(wb[(p * 2 + s) * CBN * 64]);
-            v4i a[3];
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) {
-              if (kw == 1) {
-                a[pl] = c[pl];
-              } else {
-                // kw = 0: lane r16 takes pixel r16 + 1 (row_shl:1); kw = 2: pixel r16 - 1 (row_shr:1)
-#pragma unroll
-                for (int d = 0; d < 4; ++d)
-                  a[pl][d] = kw == 0 ? __builtin_amdgcn_update_dpp(0, c[pl][d], 0x101, 0xF, 0xF, true)
-                                     : __builtin_amdgcn_update_dpp(0, c[pl][d], 0x111, 0xF, 0xF, true);
-                if (r16 == (kw == 0 ? 15 : 0))
-                  a[pl] = *reinterpret_cast<const v4i*>(pc + (kw == 0 ? 96 : -96) + pl * PLANE + 64 * s);
-              }
-            }
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_v8bf(a[0]), w, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_v8bf(a[1]), w, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_v8bf(a[2]), w, acc, 0, 0, 0);
-          }
-        }
-      }
-#else
 #pragma unroll
       for (int p = 0; p < 9; ++p) {
         const int kh = p / 3, kw = p - 3 * kh;
@@ -286,27 +185,12 @@ __device__ __forceinline__ void gx5_body(int bid, int nblk, const Geo& g, const 
           const v8bf am = as_v8bf(*reinterpret_cast<const v4i*>(pa + PLANE + 64 * s));
           const v8bf al = as_v8bf(*reinterpret_cast<const v4i*>(pa + 2 * PLANE + 64 * s));
           const v8bf w = as_v8bf(wb[(p * 2 + s) * CBN * 64]);
-#ifdef CIMQ_EXP_GX5_NOMFMA
-          acc[0] += (float)ah[0] + (float)am[1] + (float)al[2] + (float)w[3];
-          continue;
-#endif
-#ifdef CIMQ_EXP_GX5_CHAINS  // attribution builds: the two K-steps into separate accumulators (two MFMA chains)
-          v4f& a2 = s == 0 ? acc : acc1;
-          a2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, w, a2, 0, 0, 0);
-          a2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, w, a2, 0, 0, 0);
-          a2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, w, a2, 0, 0, 0);
-#else
           acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, w, acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, w, acc, 0, 0, 0);
           acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, w, acc, 0, 0, 0);
-#endif
         }
       }
-#endif
     }
-#ifdef CIMQ_EXP_GX5_CHAINS
-    acc += acc1;
-#endif
     // acc[r]: input pixel (r0 + rl, iw0 + 4 g4 + r), channel c_lo + r16: scale, LSQ activation backward, store
     const int ih = r0 + rl, iw = iw0 + 4 * g4;
     const int gi = ((b * g.C + c_lo + r16) * g.H + ih) * g.W + iw;
@@ -340,9 +224,7 @@ __device__ __forceinline__ void gx5_body(int bid, int nblk, const Geo& g, const 
     gsa_part[bid] = t;
   }
 }
-#endif  // CIMQ_TU_GX5 || CIMQ_TU_GXW5
 
-#ifdef CIMQ_TU_GX5
 template <int CBN>
 __global__ __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_per_eu(4, 8)))
 void cim_bwd_gx5_kernel(Geo g, X5 v, const uint32_t* __restrict__ st, const v4i* __restrict__ wg5, Params pp,
@@ -351,6 +233,5 @@ void cim_bwd_gx5_kernel(Geo g, X5 v, const uint32_t* __restrict__ st, const v4i*
                         float* __restrict__ gsa_part) {
   gx5_body<CBN>((int)blockIdx.x, (int)gridDim.x, g, v, st, wg5, pp, sw_p, sa_p, gout, x, gx, gsa_part);
 }
-#endif  // CIMQ_TU_GX5
 
 }  // namespace cimq

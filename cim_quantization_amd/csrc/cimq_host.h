@@ -1,6 +1,7 @@
 // cimq_host.h -- host-side plans, layouts, error state and the kernel timer shared by the
 // translation units of libcimq.so (cimq_api.hip and the cimq_part_*.hip launchers, which are
-// compiled in parallel).
+// compiled in parallel).  Host code only: it sees the kernels' plan structs and constants through
+// cimq_types.h; each unit includes the kernel file(s) it launches itself.
 #pragma once
 #include <math.h>
 #include <stdarg.h>
@@ -14,12 +15,7 @@
 #include <string>
 
 #include "../../include/cimq.h"
-#include "cimq_c1.hip"
-#include "cimq_fwd5.hip"
-#include "cimq_gw5.hip"
-#include "cimq_gx5.hip"
-#include "cimq_r6.hip"
-
+#include "cimq_types.h"
 
 namespace cimq {
 
@@ -236,7 +232,7 @@ inline CtxLayout ctx_layout_compute(const Geo& g) {
   }
   L.xhat = o; o = align256(o + (size_t)g.Nin * g.NBP);   // backward (int8 ctx) slice bytes
   L.alut = o; o = align256(o + (size_t)4 * 301);         // ctx codes: code -> ctx word (ctx_codes), format word 300
-  // per-partial-sum state words written by the fast forward (cimq_kernels_v3.hip: StWord)
+  // per-partial-sum state words written by the fast forward (cim_fwd_v3_kernel)
   // (v7: one uint32 per (i, m, o) -- never larger for nbw >= 2; the max covers nbw == 1)
   // state words: per-(k) words of the v3-v6 kernels, or the v7 compact words (4 B, or three
   // 64-bit planes for w8a8) per (tile, pixel, channel)
@@ -436,9 +432,6 @@ inline void gw_pitches(const Geo& g, V7& v) {
 inline Plan7 v7_plan_compute(const Geo& g) {
   Plan7 p;
   memset(&p, 0, sizeof(p));
-#ifdef CIMQ_NO_V7
-  return p;
-#endif
   const Plan3 p3 = v3_plan(g);
   if (!p3.ok) return p;
   // instantiated slice pairs: w3a3 / w2a2 (interleaved state words) and w8a8 (plane state words)
@@ -1155,14 +1148,14 @@ int launch_fwd_any(const Geo& g, uint8_t* ctx, const float* sw, const float* sa,
 // cimq_part_fwd5.hip: the w3a3 module forward on the slice-planar patch (f5_plan)
 int launch_fwd5(const Geo& g, const Plan5& p, uint8_t* ctx, const float* sw, const float* sa, float* out,
                 hipStream_t s, const ActQ* aq);
-// cimq_part_gx5.hip: grad_x (+ the fused act-LSQ backward) of the 16 -> 16-channel 32-wide layers (x5_plan)
+// cimq_part_gxw5.hip: grad_x (+ the fused act-LSQ backward) of the 16 -> 16-channel 32-wide layers (x5_plan)
 int launch_gx5(const Geo& g, const PlanX5& p, const uint8_t* ctx, const float* sw, const float* sa, const float* gout,
                const float* x, float* gx, uint8_t* ws, hipStream_t s);
 // ... and its weight operand from a quantised w_q (the Function entry points' prologue, prep_all)
 int launch_prep_wg5(const Geo& g, const float* w_q, const float* sw, uint8_t* ctx, hipStream_t s);
-// cimq_part_gw5.hip: grad_w + grad_alpha slabs of the w3a3 stride-1 16 / 32-channel layers (g5_plan)
+// ... grad_w + grad_alpha slabs of the w3a3 stride-1 16 / 32-channel layers (g5_plan)
 int launch_gw5(const Geo& g, const PlanG5& p, const uint8_t* ctx, const float* gout, uint8_t* ws, hipStream_t s);
-// cimq_part_gxw5.hip: both in one launch (grad_x's workgroups, then grad_w's)
+// ... and both in one launch (grad_x's workgroups, then grad_w's)
 int launch_gxw5(const Geo& g, const PlanX5& px, const PlanG5& pw, const uint8_t* ctx, const float* sw, const float* sa,
                 const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s);
 // cimq_part_dense.hip: the dense path (dense_plan) -- forward, and grad_x + grad_w / grad_alpha slabs
@@ -1181,7 +1174,7 @@ int launch_bwd_general(const Geo& g, const uint8_t* ctx, const float* sw, const 
 // cimq_part_bwd.hip: per-chunk sums of |ps * sw * sa| for the alpha_cim initialisation
 int launch_alpha_init_sums(const Geo& g, const uint8_t* ctx, const float* sw, const float* sa,
                            const float* signed_act, uint8_t* ws, hipStream_t s);
-// cimq_part_v7_*.hip: the v7 backward (grad_x v8 + grad_w v7) for one slice-pair shape
+// cimq_part_v7.hip: the v7 backward (grad_x v8 + grad_w v7) for one slice-pair shape
 template <int NBW, int NBA>
 int launch_v7_n(const Geo& g, const Plan7& p, const uint8_t* ctx, const float* sw, const float* sa,
                 const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, bool lsq,

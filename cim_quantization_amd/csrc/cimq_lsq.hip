@@ -6,8 +6,8 @@
 //   scale = (max(alpha_cim) - min(alpha_cim)) / (2^b - 2),
 // each value with the reference's fp32 op sequence, and their autograd backward with the
 // order in which torch's engine accumulates the contributions.
-#pragma once
 #include "cimq_lsq_dev.h"
+#include "cimq_operands.h"
 
 namespace cimq {
 

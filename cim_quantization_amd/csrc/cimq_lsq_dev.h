@@ -1,7 +1,7 @@
 // cimq_lsq_dev.h -- device side of the LSQ quantiser backward: the module epilogue kernels
 // (cimq_lsq.hip), one layer per launch or packed over a chain of layers (cimq_pending_flush).
 #pragma once
-#include "cimq_kernels_v3.hip"
+#include "cimq_device.h"
 
 namespace cimq {
 
@@ -11,6 +11,30 @@ struct LsqArgs {
   int nbits_alpha;       // 0: no alpha_cim
   int nalpha;            // numel(alpha_cim) = T*nbw*nba*O
 };
+
+// ---------------------------------------------------------------------------------------
+// coalesced, thread-parallel slab reductions: 64 consecutive outputs x 4 chunk lanes / block
+// ---------------------------------------------------------------------------------------
+// 64 consecutive outputs per block, blockDim/64 chunk lanes per output; every lane keeps four
+// independent loads in flight.  Returns the sum in the threads of the first wave.
+__device__ inline float reduce_chunks(const float* __restrict__ slab, size_t chunk_stride, int nchunks,
+                                      size_t idx, float* red) {
+  // 8 independent loads in flight per lane: the few reducer blocks are latency-bound
+  const int sub = threadIdx.x >> 6, nsub = blockDim.x >> 6;
+  float a[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  int c = sub;
+  for (; c + 7 * nsub < nchunks; c += 8 * nsub) {
+#pragma unroll
+    for (int u = 0; u < 8; ++u) a[u] += slab[(size_t)(c + u * nsub) * chunk_stride + idx];
+  }
+  for (; c < nchunks; c += nsub) a[0] += slab[(size_t)c * chunk_stride + idx];
+  red[threadIdx.x] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+  __syncthreads();
+  float v = 0.f;
+  if (sub == 0)
+    for (int t = 0; t < nsub; ++t) v += red[threadIdx.x + 64 * t];
+  return v;
+}
 
 // block-wide reductions: across the wave with lane shuffles, then across the (<= 16) waves
 // through LDS with one barrier.  red needs 4 * 16 floats.
@@ -246,19 +270,10 @@ __device__ inline void gw_lsq_role(const Geo& g, const LsqArgs& q, const ModuleT
     const size_t i0 = ((size_t)blk * a.lpr + (threadIdx.x & (a.lpr - 1))) * 4;
     const bool mine = (int)threadIdx.x < a.lpr && i0 < nout;
     GwPre pre[4];
-#ifdef CIMQ_EXP_TAIL_NOEPI  // attribution builds only (tools/kernel_experiment.py)
-#pragma unroll
-    for (int u = 0; u < 4; ++u) pre[u] = GwPre{-1, 0.f, 0.f};
-#else
 #pragma unroll
     for (int u = 0; u < 4; ++u) pre[u] = mine ? gw_pre(g, a, i0 + u) : GwPre{-1, 0.f, 0.f};
-#endif
-#ifdef CIMQ_EXP_TAIL_NOSLAB
-    const float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-#else
     const float4 v = reduce_chunks4(a.gw_slab, nout, a.nchunks, i0 < nout ? i0 : 0, a.lpr,
                                     reinterpret_cast<float4*>(red));
-#endif
     if (threadIdx.x >= 64) return;
     float p_mul = 0.f, p_div = 0.f;
     const float nbw = (float)g.nbw;

@@ -2,8 +2,8 @@
 // general recompute kernels, lsq.py:244-386: every ADC variant, any conv geometry; deterministic,
 // no atomics) and the alpha_cim initialisation sums (lsq.py:35-87).  Own translation unit of
 // libcimq.so.
-#define CIMQ_TU_BWD
 #include "cimq_host.h"
+#include "cimq_kernels_bwd.hip"
 
 namespace cimq {
 

@@ -15,8 +15,8 @@
 // kernels decode E / D from the pass bits and grad_alpha's code * g from the fields.  grad_w and grad_alpha leave
 // per-chunk slabs in the layout the module epilogue reduces (module_bwd_tail_kernel).
 // Own translation unit of libcimq.so.
-#define CIMQ_TU_DENSE
 #include "cimq_host.h"
+#include "cimq_fwd_stage.h"
 
 namespace cimq {
 
@@ -94,11 +94,7 @@ __device__ inline void dense_fwd_body(const Geo& g, const uint8_t* __restrict__ 
   // out accumulators of the four channel blocks in LDS ([wave][ob][lane]); one block's in registers
   float4* acc_l = accs + wave * 4 * 64 + lane;
   for (int i = 0; i < g.T; ++i) {
-#ifdef CIMQ_EXP_DENSE_NOPRM
-    if (!LIT && i == 0) {
-#else
     if (!LIT) {
-#endif
       __syncthreads();
       for (int t = threadIdx.x; t < NKJ * 64; t += 256) {
         const int col = t & 63, jk = t >> 6, j = jk / NBW, k = jk - j * NBW;
@@ -168,12 +164,8 @@ __device__ inline void dense_fwd_body(const Geo& g, const uint8_t* __restrict__ 
             const float cf = cfl[pcol];
 #pragma unroll
             for (int r = 0; r < 4; ++r)
-#ifdef CIMQ_EXP_DENSE_NOADC  // attribution builds only (tools/kernel_experiment.py): wrong results
-              acc[r] += (float)ps[j][r] * cf + (float)pv.x;
-#else
               if constexpr (WST) adc_ps(ps[j][r], pv, cf, acc[r], sp[r], sz[r], sn[r]);
               else adc_ps_out(ps[j][r], pv, cf, acc[r]);
-#endif
           } else {
             // degenerate alpha / scales: the literal ADC per partial sum (as cim_fwd_v3_kernel)
             const int o = og * 64 + ob * 16 + r16;
@@ -200,11 +192,7 @@ __device__ inline void dense_fwd_body(const Geo& g, const uint8_t* __restrict__ 
         const size_t m = (size_t)m0 + wave * 16 + 4 * g4 + r;
         // code fields: lo -> 11, hi -> 01 (lo wins, as the ADC's second select)
         const uint32_t code = spread16(sz[r] | sn[r]) | (spread16(sn[r]) << 1);
-#ifndef CIMQ_EXP_DENSE_NOSTORE
         st[((size_t)i * g.M + m) * g.O + o] = make_uint2(code, sp[r] & 0xFFFFu);
-#else
-        if (code == 0x12345u) st[m] = make_uint2(code, sp[r]);
-#endif
       }
       if (i + 1 < g.T) {
         acc_l[ob * 64] = make_float4(acc[0], acc[1], acc[2], acc[3]);
@@ -271,14 +259,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void d
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       const int c0 = i * g.xbar + ks * 64 + 16 * g4;
-#ifdef CIMQ_EXP_DENSE_NOX
-      if (true) {
-#pragma unroll
-        for (int e = 0; e < 16; ++e) w[ks][e] = (uint32_t)(mrow * 131 + c0 * 7 + e) & 0x01010101u;
-      } else if (c0 < g.C) {
-#else
       if (c0 < g.C) {
-#endif
         const uint4* src = reinterpret_cast<const uint4*>(xcf + ((size_t)mrow * g.C + c0) * 4);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -291,18 +272,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void d
       }
     }
     __syncthreads();  // the previous tile's readers of prm / wkl are done
-#ifdef CIMQ_EXP_DENSE_NOSTAGE
-    if (i == 0)
-#endif
     for (int t = threadIdx.x; t < NKJ * 64; t += 512) {
       const int col = t & 63, jk = t >> 6, j = jk / NBW, k = jk - j * NBW;
       const int pi = pidx(g, i, j, k, og * 64 + col);
       prm[t] = make_int4(pp.thi[pi], pp.tlo[pi], pp.mlo[pi], pp.mhi[pi]);
       cfl[t] = pp.coef[pi];
     }
-#ifdef CIMQ_EXP_DENSE_NOSTAGE
-    if (i == 0)
-#endif
     stage_w(i, 0);
     v4i xs[NBA][KS];
 #pragma unroll
@@ -319,9 +294,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void d
     for (int ob = 0; ob < 4; ++ob) {
       if (ob == 2) {
         __syncthreads();  // half 0 read by every wave
-#ifndef CIMQ_EXP_DENSE_NOSTAGE
         stage_w(i, 1);
-#endif
         __syncthreads();
       }
       float acc[4];
@@ -353,12 +326,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void d
           const float cf = cfl[pcol];
 #pragma unroll
           for (int r = 0; r < 4; ++r)
-#ifdef CIMQ_EXP_DENSE_NOADC
-            acc[r] += (float)ps[j][r] * cf + (float)pv.x;
-#else
             if constexpr (WST) adc_ps(ps[j][r], pv, cf, acc[r], sp[r], sz[r], sn[r]);
             else adc_ps_out(ps[j][r], pv, cf, acc[r]);
-#endif
         }
       }
       const int o = og * 64 + ob * 16 + r16;
@@ -367,11 +336,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void d
         if constexpr (!WST) continue;
         const size_t m = (size_t)m0 + wave * 16 + 4 * g4 + r;
         const uint32_t code = spread16(sz[r] | sn[r]) | (spread16(sn[r]) << 1);
-#ifndef CIMQ_EXP_DENSE_NOSTORE
         st[((size_t)i * g.M + m) * g.O + o] = make_uint2(code, sp[r] & 0xFFFFu);
-#else
-        if (code == 0x12345u) st[m] = make_uint2(code, sp[r]);
-#endif
       }
       if (i + 1 < g.T) {
         acc_l[ob * 64] = make_float4(acc[0], acc[1], acc[2], acc[3]);

@@ -3,6 +3,8 @@
 // grad_x + grad_w + grad_alpha partials.
 // Own translation unit of libcimq.so.
 #include "cimq_host.h"
+#include "cimq_fused.hip"
+#include "cimq_c1.hip"
 
 namespace cimq {
 

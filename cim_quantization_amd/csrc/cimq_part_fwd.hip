@@ -1,6 +1,8 @@
 // cimq_part_fwd.hip -- forward launch sequences (lsq.py:166-233): the v3 fast-path kernel and
 // the general kernel (also the partial-sum debug hook).  Own translation unit of libcimq.so.
 #include "cimq_host.h"
+#include "cimq_kernels.hip"
+#include "cimq_kernels_v3.hip"
 
 namespace cimq {
 

@@ -1,7 +1,7 @@
 // cimq_part_fwd5.hip -- launch of the w3a3 module forward on the slice-planar patch (cimq_fwd5.hip,
 // lsq.py:141-233 with the activation quantiser of lsq.py:544-549).  Own translation unit of libcimq.so.
-#define CIMQ_TU_FWD5
 #include "cimq_host.h"
+#include "cimq_fwd5.hip"
 
 namespace cimq {
 

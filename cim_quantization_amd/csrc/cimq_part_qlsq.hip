@@ -8,8 +8,8 @@
 //   is the reference's conv of integer-valued fp32 tensors while |sum| < 2^24), and the
 //   elementwise part of its backward.
 // Own translation unit of libcimq.so (extern "C" entry points declared in include/cimq.h).
-#define CIMQ_TU_QLSQ
 #include "cimq_host.h"
+#include "cimq_device.h"
 
 namespace cimq {
 

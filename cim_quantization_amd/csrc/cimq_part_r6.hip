@@ -1,7 +1,7 @@
 // cimq_part_r6.hip -- launch of the recompute backward of the w3a3 16 -> 16 stride-1 module layers (cimq_r6.hip,
 // lsq.py:244-386 + lsq.py:549).  Own translation unit of libcimq.so.
-#define CIMQ_TU_R6
 #include "cimq_host.h"
+#include "cimq_r6.hip"
 
 namespace cimq {
 

@@ -15,6 +15,7 @@
 // an LDS lookup per partial sum.  Sums are per-lane registers, a fixed shuffle / LDS tree per block and
 // a fixed-order sum over the pixel chunks (shift_combine_kernel): bit-identical run to run, no atomics.
 #include "cimq_host.h"
+#include "cimq_fwd_stage.h"
 
 namespace cimq {
 

@@ -1,10 +1,9 @@
-// cimq_v7_launch.h -- launch sequence of the v7 backward (cim_bwd_gx_v8_kernel +
-// cim_bwd_gw_v7_kernel, cimq_v7.hip) as a template over the slice-pair shape; each shape is
-// instantiated in its own translation unit (cimq_part_v7_*.hip) so they compile in parallel.
+// cimq_part_v7.hip -- launch sequence of the v7 backward (cim_bwd_gx_v8_kernel + cim_bwd_gw_v7_kernel,
+// cimq_v7.hip) as a template over the slice-pair shape, instantiated for w2a2, w3a3 and w8a8 layers.
 // parts: bit 0 the grad_x kernel, bit 1 the grad_w kernel (CIMQ_LSQ_DEFER_GW launches them apart,
-// grad_w on the caller's second stream).
-#pragma once
+// grad_w on the caller's second stream).  Own translation unit of libcimq.so.
 #include "cimq_host.h"
+#include "cimq_v7.hip"
 
 namespace cimq {
 
@@ -69,5 +68,8 @@ int launch_v7_n(const Geo& g, const Plan7& p, const uint8_t* ctx, const float* s
   }
 }
 
+template CIMQ_V7_SIG(2, 2);
+template CIMQ_V7_SIG(3, 3);
+template CIMQ_V7_SIG(8, 8);
 
 }  // namespace cimq

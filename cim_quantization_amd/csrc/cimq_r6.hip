@@ -23,73 +23,11 @@
 // grad_alpha likewise; the block writes one slab chunk per image (the module tail sums the B chunks in
 // order: deterministic, no atomics).  Reads x and g once per element (plus the two rows of overlap of the
 // staging), writes gx once: the algorithmic traffic of SURVEY 8(d), no state words.
-#pragma once
-#include "cimq_fwd5.hip"
+#include "cimq_bwd_dev.h"
+#include "cimq_fwd_stage.h"
 
 namespace cimq {
 
-// host plan (cimq_host.h: r6_plan)
-struct R6 {
-  int tc0[3];  // first (tile, channel-block) pair of tile i in cim_fwd5_kernel's operand (f5_plan)
-  int ntc;     // pairs
-  int nmt;     // m-tiles per image (H / 4)
-};
-
-// geometry of the 16-channel layer (r6_plan checks it)
-constexpr int kR6C = 16, kR6W = 32, kR6R = 4, kR6T = 2;
-constexpr int kR6KO = 3 * kR6C;          // kappa (k, o) per tile: 48
-constexpr int kR6NK = kR6T * kR6KO;      // kappa per G-patch pixel: 96 = 3 K-steps
-constexpr int kR6KSG = kR6NK / 32;
-
-// the gx operand: lane l of (position p, K-step s): input channel c = l & 15, kappa = 32 s + 8 (l >> 4) + e
-// (e < 8) = (tile i, w-slice k, output channel o) = (kappa / 48, (kappa % 48) / 16, kappa % 16), the value
-// int8(slice_k) of weight (o, f = 9 c + p) as bf16 (the backward's ctx slice, lsq.py:160), zero unless row f is
-// in tile i: wx6[(p * 3 + s) * 64 + l]
-template <typename WS>
-__device__ inline void wx6_item(const Geo& g, const WS& ws, v4i* __restrict__ wx6, int t) {
-  const int lane = t & 63;
-  const int r = t >> 6;
-  const int s = r % kR6KSG, p = r / kR6KSG;
-  const int c = lane & 15;
-  const int f = c * 9 + p;
-  uint32_t wd[4] = {0, 0, 0, 0};
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int kap = 32 * s + 8 * (lane >> 4) + e;
-    const int i = kap / kR6KO, rem = kap - i * kR6KO, k = rem >> 4, o = rem & 15;
-    float val = 0.f;
-    if (c < g.C && i < g.T && f >= i * g.xbar && f < min((i + 1) * g.xbar, g.K) && k < g.nbw)
-      val = (float)to_i8_wrap(wslice(g, ws, f, k * g.Opad + o));
-    wd[e >> 1] |= (uint32_t)bf16_bits(val) << (16 * (e & 1));
-  }
-  v4i q;
-  q.x = (int)wd[0]; q.y = (int)wd[1]; q.z = (int)wd[2]; q.w = (int)wd[3];
-  wx6[t] = q;
-}
-constexpr int kR6WxItems = 9 * kR6KSG * 64;
-
-// LDS layout of cim_bwd_r6_kernel (bytes; 159.3 KB: one workgroup per CU)
-struct R6L {
-  static constexpr int RP = kR6R + 2, WP = kR6W + 2;
-  static constexpr int GPX = kR6NK * 2 + 16;  // G-patch pixel pitch: 13 16-B slots, a wave's 16 pixels on distinct slots
-  static constexpr int GROW = WP * GPX;       // one G-patch row of one plane
-  static constexpr int GPL = kR6R * GROW;     // one plane
-  static constexpr int EXP = 36;              // exchange pitch (floats per input channel): 16-B writes on distinct banks
-  static constexpr int O_XP = 0;                             // forward slice patch [RP][WP][3 slices][16 ch] int8 (f5_off)
-  static constexpr int O_XH = O_XP + RP * WP * 48;           // ctx slices, A-ready [C][RP][WP] x (bf16 x0|x1, x2|0)
-  static constexpr int O_GP = O_XH + kR6C * RP * WP * 8;     // G patch [3 planes][R][WP][NK] bf16; exchange aliases it
-  static constexpr int O_CA = O_GP + 3 * GPL;                // carried partial rows [2][C][W] fp32
-  static constexpr int O_WX = O_CA + 2 * kR6C * kR6W * 4;    // gx operand [9][KSG][64] x 16 B
-  static constexpr int O_PR = O_WX + kR6WxItems * 16;        // ADC / STE thresholds [T][9 kj][16 o] int4
-  static constexpr int O_AL = O_PR + kR6T * 9 * 16 * 16;     // act word table [Qp + 2][fwd, bwd]
-  static constexpr int O_CE = O_AL + 260 * 8;                // cE_kj [9], cD_kj [9]
-  static constexpr int LDS = O_CE + 32 * 4;
-};
-static_assert(R6L::LDS <= 160 * 1024, "r6 LDS budget");
-static_assert(9 * 8 * 64 * 16 <= 3 * R6L::GPL, "r6 gw reduction buffer");
-static_assert(2 * kR6T * 9 * 8 * 16 * 4 <= 3 * R6L::GPL, "r6 grad_alpha reduction buffer");
-
-#ifdef CIMQ_TU_R6
 // STE pass bits of one tile's 9 slice pairs: bit k*3 + j
 __device__ inline float r6_E(uint32_t pw, int k, bool std_mask, const float* cel) {
   if (std_mask) return (float)(__popc(pw & (7u << (3 * k))) << k);
@@ -243,11 +181,9 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_pe
   };
 
   const int nmt = v.nmt;
-#ifndef CIMQ_EXP_R6_NO_WFPF
   v4i wnx[9];  // the next tile's forward weight fragments, in flight one tile ahead
 #pragma unroll
   for (int q = 0; q < 9; ++q) wnx[q] = wf5[(size_t)v.tc0[0] * 9 * 64 + lane + q * 64];
-#endif
   float xv[2][4];
   stage_load(0, xv);
   float4 gq = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -272,7 +208,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_pe
     for (int i = 0; i < T; ++i) {
       // the tile's forward weight fragments [s][k] (cim_fwd5_kernel's operand, output block 0)
       v4i wfr[9];
-#ifndef CIMQ_EXP_R6_NO_WFPF
       {
         const v4i* wt = wf5 + (size_t)v.tc0[i + 1 < T ? i + 1 : 0] * 9 * 64 + lane;
 #pragma unroll
@@ -281,11 +216,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_pe
           wnx[q] = wt[q * 64];
         }
       }
-#else
-      const v4i* wt = wf5 + (size_t)v.tc0[i] * 9 * 64 + lane;
-#pragma unroll
-      for (int q = 0; q < 9; ++q) wfr[q] = wt[q * 64];
-#endif
       v4i ps[9];
 #pragma unroll
       for (int s = 0; s < 3; ++s) {
@@ -414,7 +344,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_pe
     }
     __syncthreads();  // (B1) the G patch is complete; the patches' readers are done
     if (more) stage_store(r0 + R, xv);  // the next m-tile's patches (its phase A reads them after B4)
-#ifndef CIMQ_EXP_R6_NO_XFPF
     float4 xf[2];  // the finished rows' x (act-LSQ backward), in flight behind the gx MFMAs
     {
       const int t = (int)threadIdx.x;
@@ -428,7 +357,6 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_pe
           xf[u] = *reinterpret_cast<const float4*>(x + ((b * C + c) * H + ih) * W + iw);
       }
     }
-#endif
     if (DBG) {
       __syncthreads();
       gq = gqn;
@@ -477,12 +405,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_pe
       float4* ca = reinterpret_cast<float4*>(smem + O_CA);
       auto fin = [&](int ih, float4 v4, int u) {
         const int gi = ((b * C + c) * H + ih) * W + iw;
-#ifndef CIMQ_EXP_R6_NO_XFPF
         const float4 xv4 = xf[u];
-#else
-        (void)u;
-        const float4 xv4 = *reinterpret_cast<const float4*>(x + gi);
-#endif
         const float xs[4] = {xv4.x, xv4.y, xv4.z, xv4.w};
         const float vs[4] = {v4.x, v4.y, v4.z, v4.w};
         float o4[4];
@@ -572,6 +495,5 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512, 512), amdgpu_waves_pe
     ga_slab[((size_t)b * g.T * 9 + q) * g.Opad + o] = t;
   }
 }
-#endif  // CIMQ_TU_R6
 
 }  // namespace cimq

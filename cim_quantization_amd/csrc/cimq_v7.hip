@@ -25,71 +25,11 @@
 //
 // Both replace the state-word (16-bit per (i, k, quad, o)) kernels of cimq_kernels_v3.hip /
 // cimq_gx_v6.hip on layers the v7 plan accepts (host: v7_plan in cimq_api.hip).
-#pragma once
 #include <type_traits>
 
-#include "cimq_kernels_v3.hip"
-#include "cimq_lsq_dev.h"
-
-#ifndef CIMQ_FOLD_XB
-#define CIMQ_FOLD_XB 1  // the grad_x folds' elements per thread and round (cimq_v7 / cimq_fused)
-#endif
+#include "cimq_bwd_dev.h"
 
 namespace cimq {
-
-struct V7 {
-  int lw;       // log2(Wo)
-  // grad_x (v8: ring fold)
-  int NCPBT;    // (c, kh)-row blocks of 4 per tile (wcy operand)
-  int SWD;      // segment width: min(16, Wo) output columns per 16-lane MFMA column group
-  int NSEG;     // segments per output row
-  int NRS;      // output rows per step (64 pixels)
-  int RSLOT;    // ring rows (NRS + 2)
-  int NPART;    // waves sharing one pixel group (split over (c, kh)-blocks)
-  int lwin, lcin;  // log2(W), log2(C) (the v7 path takes power-of-two W and C)
-  // grad_x
-  int RB;       // input rows owned by one block
-  int nbands;   // bands per image
-  int FBX;      // f-blocks per tile (FBT)
-  // grad_w
-  int NSLOT;    // staged input rows per 128-pixel stage
-  int CPITCH;   // plane channel pitch (bf16 elements)
-  int nstage;   // 128-pixel stages per chunk
-  int nchunks;  // pixel chunks
-  int whole;    // 1: a stage is 128/P whole images; 0: a stage is 128/Wo rows of one image
-  int CPL;      // channels per staged plane: min(16, C)
-  int NTL;      // most crossbar tiles touching one 16-channel block (grad_alpha LDS regions)
-  int GSH;      // grad_x, NPART > 1, at most 2 o-blocks: the NPART waves of a pixel group build disjoint G chunks and
-                // exchange them through LDS (else every wave builds all of them)
-  int KWP;      // grad_w: (slice j, kw) plane pitch (bf16 elements, >= CPL * CPITCH; gw_pitches)
-};
-
-// pass-bit masks of the state word: all j of slice k / all k of slice j
-__host__ __device__ constexpr uint32_t pass_mask_k(int k, int nba) {
-  uint32_t m = 0;
-  for (int j = 0; j < nba; ++j) m |= 1u << (3 * (k * nba + j));
-  return m;
-}
-__host__ __device__ constexpr uint32_t pass_mask_j(int j, int nbw, int nba) {
-  uint32_t m = 0;
-  for (int k = 0; k < nbw; ++k) m |= 1u << (3 * (k * nba + j));
-  return m;
-}
-
-// uniform (scalar-register) copies of values every lane computed identically
-__device__ inline float sgpr_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-__device__ inline uint64_t sgpr_u64(uint64_t v) {
-  return (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) |
-         ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32);
-}
-
-// lane l <- lane l+1 / l-1 of the same 16-lane row (0 past the row's end)
-__device__ inline float dpp_from_next(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x101, 0xF, 0xF, true));
-}
-__device__ inline float dpp_from_prev(float v) {
-  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xF, 0xF, true));
-}
 
 // ---------------------------------------------------------------------------------------
 // grad_x, v8: unfolded product with the (c, kh, kw) rows ordered so that the nn.Fold adjoint
@@ -411,33 +351,6 @@ __global__ __launch_bounds__(256 * NPART) void cim_bwd_gx_v8_kernel(Geo g, V7 v,
 // block = (pixel chunk, (channel block cb, output block ob)); a chunk is nstage stages of 128
 // output pixels; in a stage wave w owns the 32 pixels 32w..32w+31 (one MFMA K-step).
 // stride 1 (v7_plan); at most 3 crossbar tiles touch one 16-channel block.
-// ctx slice bytes of one input element: NBP = 4 (uint32) or 8 (uint2) bytes, slice j in byte j
-__device__ inline uint32_t xbyte(uint32_t w, int j) { return (w >> (8 * j)) & 0xFFu; }
-__device__ inline uint32_t xbyte(uint2 w, int j) { return (j < 4 ? (w.x >> (8 * j)) : (w.y >> (8 * (j - 4)))) & 0xFFu; }
-template <typename XW>
-__device__ inline XW xzero();
-template <>
-__device__ inline uint32_t xzero<uint32_t>() { return 0u; }
-template <>
-__device__ inline uint2 xzero<uint2>() { return make_uint2(0u, 0u); }
-// n consecutive elements from a 16-B aligned source by 16-B loads
-template <int N>
-__device__ inline void xload(const uint32_t* src, uint32_t* d) {
-#pragma unroll
-  for (int q = 0; q < N / 4; ++q) {
-    const uint4 t = reinterpret_cast<const uint4*>(src)[q];
-    d[4 * q] = t.x; d[4 * q + 1] = t.y; d[4 * q + 2] = t.z; d[4 * q + 3] = t.w;
-  }
-}
-template <int N>
-__device__ inline void xload(const uint2* src, uint2* d) {
-#pragma unroll
-  for (int q = 0; q < N / 2; ++q) {
-    const uint4 t = reinterpret_cast<const uint4*>(src)[q];
-    d[2 * q] = make_uint2(t.x, t.y); d[2 * q + 1] = make_uint2(t.z, t.w);
-  }
-}
-
 template <int NBW, int NBA, int SS>
 __global__ __launch_bounds__(256, 2) void cim_bwd_gw_v7_kernel(Geo g, V7 v, const uint32_t* __restrict__ st,
                                                             const uint8_t* __restrict__ xcb, Params pp,

@@ -1,5 +1,5 @@
 """The activation-prep kernel's branch-free digit formula (act_words in
-cim_quantization_amd/csrc/cimq_kernels.hip) against the oracle's slicing chain.
+cim_quantization_amd/csrc/cimq_operands.h) against the oracle's slicing chain.
 
 The reference slices x_int = x_q / sa (lsq.py:466-509) by floor / remainder on fp32 values;
 x_int is not always an integer (fl(fl(r*sa)/sa) != r for some r, sa: the "6 - eps" slice

@@ -1,7 +1,7 @@
 """GPU parity of the module path's activation prep on inputs that sit on the quantiser's edges.
 
 The prep tabulates the slice words of every LSQ code r = rint(clamp(x/sa, 0, Qp)) once per
-block (cimq_kernels.hip, act_lut_build) and looks each element up by its code.  These inputs
+block (cimq_operands.h, act_lut_build) and looks each element up by its code.  These inputs
 put x/sa exactly on the rint ties (k + 0.5 with a power-of-two step size, so the division is
 exact), just inside and outside the clamp range, on -0.0 and on large magnitudes, and the layer
 is checked against the module oracle (lsq.py:522-588): out, every gradient, and the ADC codes
