@@ -21,8 +21,9 @@ int prep_all(const Geo& g, const float* x, const float* w_q, const float* sa, co
              const float* alpha_q, const int8_t* bmask, const float* signed_act, uint8_t* ctx,
              hipStream_t s, bool need_params, bool need_wgx, const float* beta = nullptr) {
   CtxLayout L = ctx_layout(g);
+  const Route r = route_of(g);
   const int blk = 256;
-  if (!inf_actq(g)) {  // (there the forward's row staging quantises, and the ctx has no slice words)
+  if (!r.actq) {  // (there the forward's row staging quantises, and the ctx has no slice words)
     // one 4-element item per thread up to 8192 blocks (fewer, fatter blocks measured slower)
     int grid = cdiv(g.Nin, 4 * blk);
     if (grid > act_blocks()) grid = act_blocks();
@@ -41,25 +42,22 @@ int prep_all(const Geo& g, const float* x, const float* w_q, const float* sa, co
                        reinterpret_cast<v4i*>(wreg(g, ctx) + L.wfrag));
     CIMQ_TRY(check_hip("prep_wfrag"));
   }
-  if (need_wgx) {
-    const Plan7 p7 = v7_plan(g);
-    // the general / v6 grad_x operands only where the v7 backward will not run
-    if (!(p7.ok && (g.variant == VAR_LIBRARY || shift_stats_ok(g)))) {
-      // the general grad_x operand where the v7 backward will not run
-      int total = g.T * g.FBT * g.NKS * 64;
-      hipLaunchKernelGGL(prep_wgx_kernel, dim3(cdiv(total, blk)), dim3(blk), 0, s, g, w_q, sw,
-                         reinterpret_cast<v4i*>(wreg(g, ctx) + L.wgx));
-      CIMQ_TRY(check_hip("prep_wgx"));
-    }
-    if (p7.ok) {
-      const int tc = g.T * p7.v.NCPBT * g.NKS * 64;
-      hipLaunchKernelGGL(prep_wcy_kernel, dim3(cdiv(tc, blk)), dim3(blk), 0, s, g, w_q, sw, p7.v.NCPBT,
-                         reinterpret_cast<v4i*>(wreg(g, ctx) + L.wcy));
-      CIMQ_TRY(check_hip("prep_wcy"));
-    }
-    // cim_bwd_gx5_kernel's operand (x5_plan: the RAW_LSQ Function path runs that kernel too)
-    CIMQ_TRY(launch_prep_wg5(g, w_q, sw, ctx, s));
+  // the backward's weight operands (none in a forward-only call; need_wgx: the alpha_cim init has no backward)
+  if (need_wgx && r.wgx) {
+    int total = g.T * g.FBT * g.NKS * 64;
+    hipLaunchKernelGGL(prep_wgx_kernel, dim3(cdiv(total, blk)), dim3(blk), 0, s, g, w_q, sw,
+                       reinterpret_cast<v4i*>(wreg(g, ctx) + L.wgx));
+    CIMQ_TRY(check_hip("prep_wgx"));
   }
+  if (need_wgx && r.wcy) {
+    const int ncpbt = v7_plan(g).v.NCPBT;
+    const int tc = g.T * ncpbt * g.NKS * 64;
+    hipLaunchKernelGGL(prep_wcy_kernel, dim3(cdiv(tc, blk)), dim3(blk), 0, s, g, w_q, sw, ncpbt,
+                       reinterpret_cast<v4i*>(wreg(g, ctx) + L.wcy));
+    CIMQ_TRY(check_hip("prep_wcy"));
+  }
+  // cim_bwd_gx5_kernel's operand (the RAW_LSQ Function path runs that kernel too)
+  if (need_wgx && r.wg5) CIMQ_TRY(launch_prep_wg5(g, w_q, sw, ctx, s));
   Params pp = params_of(g, ctx);
   if (need_params) {
     if (hipMemsetAsync(pp.flags, 0, 16, s) != hipSuccess) return fail(CIMQ_EHIP, "memset flags");
@@ -71,56 +69,52 @@ int prep_all(const Geo& g, const float* x, const float* w_q, const float* sa, co
   return CIMQ_OK;
 }
 
-// layers whose backward is the separate v7 grad_x / grad_w pair: with CIMQ_LSQ_DEFER_GW the grad_w
-// kernel leaves cimq_module_backward for cimq_module_backward_params (the fused / first-conv kernels
-// and the general paths produce both in one pass)
-static bool gw_deferrable(const Geo& g) {
-  return g.variant == VAR_LIBRARY && v7_bwd(g) && !c1_plan(g).ok && !v9_plan(g).ok && !r6_bwd(g);
+// The backward kernels of the layer's route.  parts: bit 0 grad_x (with everything a single-pass backward
+// produces), bit 1 grad_w where that is a launch of its own (Route::gw_own: with CIMQ_LSQ_DEFER_GW it leaves
+// cimq_module_backward for cimq_module_backward_params)
+int dispatch_bwd_any(const Geo& g, const uint8_t* ctx, const float* sw, const float* sa, const float* signed_act,
+                     const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, int parts = 3) {
+  const Route r = route_of(g);
+  if (parts != 3 && !r.gw_own) return fail(CIMQ_EINVAL, "internal: grad_w alone on a single-pass backward");
+  switch (r.gx) {
+    case CIMQ_ROUTE_R6:  // the module path's w3a3 16-channel layers: recompute, no state words (cimq_r6.hip)
+      if (!signed_act) return fail(CIMQ_EINVAL, "internal: the recompute backward needs signed_act");
+      return launch_r6(g, r6_plan(g), ctx, sw, sa, signed_act, gout, x, gx, ws, s);
+    case CIMQ_ROUTE_C1: return launch_c1(g, c1_plan(g), ctx, sw, sa, gout, x, gx, ws, s, r.lsq_fused);
+    case CIMQ_ROUTE_FUSED: return launch_fused(g, v9_plan(g), ctx, sw, sa, gout, x, gx, ws, s, r.lsq_fused);
+    case CIMQ_ROUTE_GX5:
+    case CIMQ_ROUTE_V7:
+      if (g.NBP == 8) return launch_v7_n<8, 8>(g, v7_plan(g), ctx, sw, sa, gout, x, gx, ws, s, parts);
+      if (g.nbw == 2) return launch_v7_n<2, 2>(g, v7_plan(g), ctx, sw, sa, gout, x, gx, ws, s, parts);
+      return launch_v7_n<3, 3>(g, v7_plan(g), ctx, sw, sa, gout, x, gx, ws, s, parts);
+    case CIMQ_ROUTE_DENSE: return launch_dense_bwd(g, ctx, sw, gout, gx, ws, s, r.lsq_fused ? x : nullptr, sa);
+    case CIMQ_ROUTE_GENERAL: return launch_bwd_general(g, ctx, sw, sa, signed_act, gout, x, gx, ws, s);
+    default: return fail(CIMQ_EINVAL, "internal: a forward-only descriptor has no backward");
+  }
 }
 
-// parts: bit 0 grad_x (with everything a single-pass backward produces), bit 1 the deferred grad_w
-// kernel of a gw_deferrable layer
-int dispatch_bwd_any(const Geo& g, const uint8_t* ctx, const float* sw, const float* sa, const float* signed_act,
-                     const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, bool* lsq_fused,
-                     int parts = 3) {
-  if (parts == 2 && !gw_deferrable(g)) return fail(CIMQ_EINVAL, "internal: grad_w alone on a single-pass backward");
-  if (!v7_bwd(g)) {
-    if (dense_plan(g)) {
-      *lsq_fused = g.input_kind == CIMQ_INPUT_RAW_LSQ && dense_lsq_parts(g) > 0;
-      return launch_dense_bwd(g, ctx, sw, gout, gx, ws, s, *lsq_fused ? x : nullptr, sa);
-    }
-    return launch_bwd_general(g, ctx, sw, sa, signed_act, gout, x, gx, ws, s, lsq_fused);
+// grad_w = sa * (slab sum over the backward's pixel chunks)
+int launch_reduce_gw(const Geo& g, const float* sa, uint8_t* ws, float* grad_w, hipStream_t s) {
+  WsLayout W = ws_layout(g);
+  const long long nout = (long long)g.T * g.FBT * 16 * g.Opad;
+  hipLaunchKernelGGL(reduce_gw_v3_kernel, dim3(cdiv(nout, 64)), dim3(1024), 0, s, g, W.nchunks_bwd,
+                     reinterpret_cast<const float*>(ws + W.gw_slab), sa, grad_w);
+  return check_hip("reduce_gw");
+}
+
+// the act-LSQ partials of the backward just run, Route::act_parts of them in the workspace: left by the grad_x
+// kernel, or by the separate pass over grad_x here; grad_sa: their sum (nullptr: a module epilogue sums them)
+int launch_act_lsq(const Geo& g, const float* x, const float* sa, float* grad_x, uint8_t* ws, float* grad_sa,
+                   hipStream_t s) {
+  const Route r = route_of(g);
+  float* part = reinterpret_cast<float*>(ws + ws_layout(g).lsq_part);
+  if (!r.lsq_fused) {
+    hipLaunchKernelGGL(lsq_act_bwd_kernel, dim3(r.act_parts), dim3(256), 0, s, g.Nin, x, sa, g.lsq_qp, grad_x, part);
+    CIMQ_TRY(check_hip("lsq_act_bwd"));
   }
-  if (r6_bwd(g)) {  // the module path's w3a3 16-channel layers: recompute, no state words (cimq_r6.hip)
-    if (!signed_act) return fail(CIMQ_EINVAL, "internal: the recompute backward needs signed_act");
-    *lsq_fused = true;
-    return launch_r6(g, r6_plan(g), ctx, sw, sa, signed_act, gout, x, gx, ws, s);
-  }
-  const PlanC1 pc = c1_plan(g);
-  if (pc.ok) {
-    const bool lsq = g.input_kind == CIMQ_INPUT_RAW_LSQ;
-    *lsq_fused = lsq;
-    return launch_c1(g, pc, ctx, sw, sa, gout, x, gx, ws, s, lsq);
-  }
-  const Plan9 p9 = v9_plan(g);
-  if (p9.ok) {
-    const bool lsq = g.input_kind == CIMQ_INPUT_RAW_LSQ;
-    *lsq_fused = lsq;
-    return launch_fused(g, p9, ctx, sw, sa, gout, x, gx, ws, s, lsq);
-  }
-  const Plan7 p7 = v7_plan(g);
-  if (p7.ok) {
-    const bool lsq = g.input_kind == CIMQ_INPUT_RAW_LSQ;
-    *lsq_fused = lsq;
-    if (g.NBP == 8) return launch_v7_n<8, 8>(g, p7, ctx, sw, sa, gout, x, gx, ws, s, lsq, parts);
-    if (g.nbw == 2) return launch_v7_n<2, 2>(g, p7, ctx, sw, sa, gout, x, gx, ws, s, lsq, parts);
-    return launch_v7_n<3, 3>(g, p7, ctx, sw, sa, gout, x, gx, ws, s, lsq, parts);
-  }
-  if (dense_plan(g)) {
-    *lsq_fused = g.input_kind == CIMQ_INPUT_RAW_LSQ && dense_lsq_parts(g) > 0;
-    return launch_dense_bwd(g, ctx, sw, gout, gx, ws, s, *lsq_fused ? x : nullptr, sa);
-  }
-  return launch_bwd_general(g, ctx, sw, sa, signed_act, gout, x, gx, ws, s, lsq_fused);
+  if (!grad_sa) return CIMQ_OK;
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, r.act_parts, part, grad_sa);
+  return check_hip("sum_partials");
 }
 
 int launch_reduce_galpha(const Geo& g, const uint8_t* ctx, uint8_t* ws, float cgrad, int init, const float* sw,
@@ -144,20 +138,6 @@ int launch_reduce_slab(const Geo& g, const uint8_t* ctx, uint8_t* ws, size_t sla
   return check_hip("reduce_slab");
 }
 
-// number of act-LSQ partials the backward leaves in ws (fused into the fused / v7 grad_x kernels,
-// else one per lsq_act_bwd_kernel block)
-int act_parts(const Geo& g) {
-  if (v7_bwd(g)) {
-    if (v9_plan(g).ok || c1_plan(g).ok || r6_bwd(g)) return g.B;
-    const PlanX5 p5 = x5_plan(g);
-    if (p5.ok) return p5.nblk;
-    return g.B * v7_plan(g).v.nbands;
-  }
-  if (dense_plan(g) && g.input_kind == CIMQ_INPUT_RAW_LSQ && dense_lsq_parts(g) > 0) return dense_lsq_parts(g);
-  int grid = cdiv(g.Nin, 256);
-  return grid > kLsqParts ? kLsqParts : grid;
-}
-
 }  // namespace
 
 extern "C" {
@@ -175,9 +155,8 @@ int cimq_query_sizes(const cimq_conv_desc* d, cimq_sizes* out) {
   WsLayout W = ws_layout(g);
   out->fwd_workspace_bytes = W.total;
   out->bwd_workspace_bytes = g.inference ? 0 : W.total;  // (forward only: there is no backward)
-  Geo gm = g;
-  gm.onchw = 1;  // the module entry points' layout: no state words where their backward recomputes
-  out->module_ctx_bytes = ctx_layout(gm).total;
+  // the module entry points' ctx: no state words where their backward recomputes them
+  out->module_ctx_bytes = ctx_layout(module_form(g)).total;
   return CIMQ_OK;
 }
 
@@ -196,10 +175,10 @@ int cimq_forward(const cimq_conv_desc* d, const float* x, const float* w_q, cons
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   uint8_t* c = reinterpret_cast<uint8_t*>(ctx);
   // forward only (CIMQ_OPT_INFERENCE): no backward weight operands; the activation quantiser in the forward's
-  // row staging where that applies (inf_actq: the same words, bit for bit, without the pass over x)
-  CIMQ_TRY(prep_all(g, x, w_q, sa, sw, alpha_q, binary_mask, signed_act, c, s, true, !g.inference));
+  // row staging where that applies (Route::actq: the same words, bit for bit, without the pass over x)
+  CIMQ_TRY(prep_all(g, x, w_q, sa, sw, alpha_q, binary_mask, signed_act, c, s, true, true));
   const ActQ aq{x, signed_act};
-  return launch_fwd_any(g, c, sw, sa, out, nullptr, nullptr, s, inf_actq(g) ? &aq : nullptr);
+  return launch_fwd_any(g, c, sw, sa, out, nullptr, nullptr, s, route_of(g).actq ? &aq : nullptr);
 }
 
 int cimq_shift_forward(const cimq_conv_desc* d, const float* x, const float* w_q, const float* sa,
@@ -236,49 +215,24 @@ int cimq_shift_backward(const cimq_conv_desc* d, const float* grad_out, const fl
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const uint8_t* c = reinterpret_cast<const uint8_t*>(ctx);
   uint8_t* w = reinterpret_cast<uint8_t*>(ws);
-  bool lsq_fused = false;
-  if (v7_plan(g).ok && shift_stats_ok(g)) {
+  const Route r = route_of(g);
+  if (r.shift_stats && !binary_mask) return fail(CIMQ_EINVAL, "null binary_mask");
+  CIMQ_TRY(dispatch_bwd_any(g, c, sw, sa, signed_act, grad_out, x, grad_x, w, s));
+  CIMQ_TRY(launch_reduce_gw(g, sa, w, grad_w, s));
+  if (r.shift_stats) {
     // the shift ADC on the fast path (shift_fast): grad_x / grad_w from the state words as for the
     // library ADC (same STE mask), the step-size gradients from the statistics kernel
-    if (!binary_mask) return fail(CIMQ_EINVAL, "null binary_mask");
-    CIMQ_TRY(dispatch_bwd_any(g, c, sw, sa, signed_act, grad_out, x, grad_x, w, s, &lsq_fused));
-    WsLayout W = ws_layout(g);
-    const long long nout = (long long)g.T * g.FBT * 16 * g.Opad;
-    hipLaunchKernelGGL(reduce_gw_v3_kernel, dim3(cdiv(nout, 64)), dim3(1024), 0, s, g, W.nchunks_bwd,
-                       reinterpret_cast<const float*>(w + W.gw_slab), sa, grad_w);
-    CIMQ_TRY(check_hip("reduce_gw"));
     CIMQ_TRY(launch_shift_stats(g, c, sw, sa, grad_out, binary_mask, w, grad_alpha, grad_beta, s));
-    if (g.input_kind == CIMQ_INPUT_RAW_LSQ) {
-      if (!lsq_fused) return fail(CIMQ_EINVAL, "internal: unfused act-LSQ backward on the v7 path");
-      hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, act_parts(g),
-                         reinterpret_cast<float*>(w + W.lsq_part), grad_sa);
-      CIMQ_TRY(check_hip("sum_partials"));
-    }
-    return CIMQ_OK;
+  } else {
+    // the general kernels.  grad_alpha: sign variant sum sign * G / sqrt(numel * Qp) (scale_shift.py:283); round
+    // variant without the factor (:491 commented out); grad_beta: sum over the clamped region / all of G
+    WsLayout W = ws_layout(g);
+    const double numel = (double)g.B * g.T * g.nbw * g.nba * g.P * g.O;
+    const float cgrad = g.variant == VAR_SHIFT_SIGN ? (float)(1.0 / sqrt(numel * (double)g.qp)) : 1.f;
+    CIMQ_TRY(launch_reduce_slab(g, c, w, W.ga_slab, cgrad, sw, sa, grad_alpha, s));
+    CIMQ_TRY(launch_reduce_slab(g, c, w, W.gb_slab, 1.f, sw, sa, grad_beta, s));
   }
-  CIMQ_TRY(launch_bwd_general(g, c, sw, sa, signed_act, grad_out, x, grad_x, w, s, &lsq_fused));
-  WsLayout W = ws_layout(g);
-  {
-    const long long nout = (long long)g.T * g.FBT * 16 * g.Opad;
-    hipLaunchKernelGGL(reduce_gw_v3_kernel, dim3(cdiv(nout, 64)), dim3(1024), 0, s, g, W.nchunks_bwd,
-                       reinterpret_cast<const float*>(w + W.gw_slab), sa, grad_w);
-    CIMQ_TRY(check_hip("reduce_gw"));
-  }
-  // grad_alpha: sign variant sum sign * G / sqrt(numel * Qp) (scale_shift.py:283); round variant
-  // without the factor (:491 commented out); grad_beta: sum over the clamped region / all of G
-  const double numel = (double)g.B * g.T * g.nbw * g.nba * g.P * g.O;
-  const float cgrad = g.variant == VAR_SHIFT_SIGN ? (float)(1.0 / sqrt(numel * (double)g.qp)) : 1.f;
-  CIMQ_TRY(launch_reduce_slab(g, c, w, W.ga_slab, cgrad, sw, sa, grad_alpha, s));
-  CIMQ_TRY(launch_reduce_slab(g, c, w, W.gb_slab, 1.f, sw, sa, grad_beta, s));
-  if (g.input_kind == CIMQ_INPUT_RAW_LSQ) {
-    float* part = reinterpret_cast<float*>(w + W.lsq_part);
-    int grid = cdiv(g.Nin, 256);
-    if (grid > kLsqParts) grid = kLsqParts;
-    hipLaunchKernelGGL(lsq_act_bwd_kernel, dim3(grid), dim3(256), 0, s, g.Nin, x, sa, g.lsq_qp, grad_x, part);
-    CIMQ_TRY(check_hip("lsq_act_bwd"));
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, grid, part, grad_sa);
-    CIMQ_TRY(check_hip("sum_partials"));
-  }
+  if (g.input_kind == CIMQ_INPUT_RAW_LSQ) CIMQ_TRY(launch_act_lsq(g, x, sa, grad_x, w, grad_sa, s));
   return CIMQ_OK;
 }
 
@@ -305,13 +259,14 @@ int cimq_debug_state_codes(const cimq_conv_desc* d, const void* ctx, int8_t* cod
   Geo g;
   CIMQ_TRY(make_geo(d, &g));
   if (!ctx || !code_out || !pass_out) return fail(CIMQ_EINVAL, "null pointer argument");
-  if (!v7_plan(g).ok || c1_plan(g).ok)
+  const StateFmt fmt = route_of(g).state;
+  if (fmt != ST_V7 && fmt != ST_PLANES)
     return fail(CIMQ_EUNSUPPORTED, "this layer's forward writes no v7 state words (the first conv's backward recomputes them)");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const uint8_t* c = reinterpret_cast<const uint8_t*>(ctx);
   const long long n = (long long)g.T * g.M * g.O;
-  hipLaunchKernelGGL(decode_state_kernel, dim3(std::min(cdiv(n, 256), 8192)), dim3(256), 0, s, g, g.NBP == 8 ? 1 : 0,
-                     c + ctx_layout(g).st, code_out, pass_out);
+  hipLaunchKernelGGL(decode_state_kernel, dim3(std::min(cdiv(n, 256), 8192)), dim3(256), 0, s, g,
+                     fmt == ST_PLANES ? 1 : 0, c + ctx_layout(g).st, code_out, pass_out);
   return check_hip("decode_state");
 }
 
@@ -322,7 +277,8 @@ int cimq_debug_recompute_codes(const cimq_conv_desc* d, const float* x, const fl
   CIMQ_TRY(make_geo(d, &g));
   if (!x || !signed_act || !ctx || !st_scratch || !code_out || !pass_out) return fail(CIMQ_EINVAL, "null pointer argument");
   g.onchw = 1;  // the module entry points' layer
-  if (!r6_bwd(g)) return fail(CIMQ_EUNSUPPORTED, "this layer's module backward does not recompute the partial sums");
+  if (route_of(g).gx != CIMQ_ROUTE_R6)
+    return fail(CIMQ_EUNSUPPORTED, "this layer's module backward does not recompute the partial sums");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const uint8_t* c = reinterpret_cast<const uint8_t*>(ctx);
   const float* scal = reinterpret_cast<const float*>(wreg(g, c) + ctx_layout(g).lsq_scal);
@@ -351,35 +307,14 @@ int cimq_backward(const cimq_conv_desc* d, const float* grad_out, const float* x
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const uint8_t* c = reinterpret_cast<const uint8_t*>(ctx);
   uint8_t* w = reinterpret_cast<uint8_t*>(ws);
-  bool lsq_fused = false;
-  CIMQ_TRY(dispatch_bwd_any(g, c, sw, sa, signed_act, grad_out, x, grad_x, w, s, &lsq_fused));
-  WsLayout W = ws_layout(g);
-  {
-    const long long nout = (long long)g.T * g.FBT * 16 * g.Opad;
-    hipLaunchKernelGGL(reduce_gw_v3_kernel, dim3(cdiv(nout, 64)), dim3(1024), 0, s, g, W.nchunks_bwd,
-                       reinterpret_cast<const float*>(w + W.gw_slab), sa, grad_w);
-    CIMQ_TRY(check_hip("reduce_gw"));
-  }
+  CIMQ_TRY(dispatch_bwd_any(g, c, sw, sa, signed_act, grad_out, x, grad_x, w, s));
+  CIMQ_TRY(launch_reduce_gw(g, sa, w, grad_w, s));
   if ((g.mode == ADC_SIGN || g.mode == ADC_TERNARY) && grad_alpha) {
     const double numel = (double)g.B * g.T * g.nbw * g.nba * g.P * g.O;
     const float cgrad = (float)(1.0 / sqrt(numel * (double)g.qp));  // lsq.py:323,330
     CIMQ_TRY(launch_reduce_galpha(g, c, w, cgrad, 0, sw, sa, grad_alpha, s));
   }
-  if (g.input_kind == CIMQ_INPUT_RAW_LSQ) {
-    float* part = reinterpret_cast<float*>(w + W.lsq_part);
-    int nparts;
-    if (lsq_fused) {
-      nparts = act_parts(g);
-    } else {
-      int grid = cdiv(g.Nin, 256);
-      if (grid > kLsqParts) grid = kLsqParts;
-      hipLaunchKernelGGL(lsq_act_bwd_kernel, dim3(grid), dim3(256), 0, s, g.Nin, x, sa, g.lsq_qp, grad_x, part);
-      CIMQ_TRY(check_hip("lsq_act_bwd"));
-      nparts = grid;
-    }
-    hipLaunchKernelGGL(sum_partials_kernel, dim3(1), dim3(256), 0, s, nparts, part, grad_sa);
-    CIMQ_TRY(check_hip("sum_partials"));
-  }
+  if (g.input_kind == CIMQ_INPUT_RAW_LSQ) CIMQ_TRY(launch_act_lsq(g, x, sa, grad_x, w, grad_sa, s));
   return CIMQ_OK;
 }
 
@@ -428,7 +363,7 @@ static TailLaunch tail_job(const Geo& g, const LsqArgs& la, const cimq_lsq_desc*
   const int per_blk = a.wide ? 1024 : a.lpr == 0 ? 64 : 4 * a.lpr;
   a.nwb = cdiv(nout_w, per_blk);
   a.nga = has_alpha ? cdiv((long long)g.T * g.nbw * g.nba * g.Opad, per_blk) : 0;
-  a.napart = act_parts(g);
+  a.napart = route_of(g).act_parts;
   a.accum = (q->flags & CIMQ_LSQ_ACCUMULATE_GRADS) ? 1 : 0;
   a.gapart = (has_alpha && la.nalpha > kFinishInReg && tune("WIDE_TAIL", 1)) ? reinterpret_cast<float*>(w + W.gapart) : nullptr;
   a.gaq_ready = gaq_ready;
@@ -559,6 +494,7 @@ static ModulePrep module_prep_args(const Geo& g, const float* x, const float* we
                                    const float* signed_act, uint8_t* c, int* nwblk) {
   CtxLayout L = ctx_layout(g);
   uint8_t* wr = wreg(g, c);
+  const Route r = route_of(g);
   const Plan7 p7 = v7_plan(g);
   ModulePrep a;
   memset(&a, 0, sizeof(a));
@@ -570,7 +506,7 @@ static ModulePrep module_prep_args(const Geo& g, const float* x, const float* we
   a.signed_act = signed_act;
   a.bmask = binary_mask;
   a.xcf = c ? c + L.xcode : nullptr;
-  a.xcb = c ? c + L.xhat : nullptr;
+  a.xcb = (c && !g.inference) ? c + L.xhat : nullptr;  // (forward only: no backward words)
   a.wfrag = reinterpret_cast<v4i*>(wr + L.wfrag);
   a.wgx = reinterpret_cast<v4i*>(wr + L.wgx);
   a.wcy = reinterpret_cast<v4i*>(wr + L.wcy);
@@ -578,33 +514,32 @@ static ModulePrep module_prep_args(const Geo& g, const float* x, const float* we
   a.scal = reinterpret_cast<float*>(wr + L.lsq_scal);
   a.nact_blocks = (int)std::min<long long>(cdiv(g.Nin, 4 * 256), act_blocks());
   a.nwf = g.T * g.KS * g.NBLK * 64;
-  a.nwg = p7.ok ? 0 : g.T * g.FBT * g.NKS * 64;       // general / dense grad_x operand
+  // the backward's operands as the Route asks for them (none in a forward-only call)
+  a.nwg = r.wgx ? g.T * g.FBT * g.NKS * 64 : 0;       // general / dense grad_x operand
   a.ncpbt = p7.ok ? p7.v.NCPBT : 1;
-  a.nwc = p7.ok ? g.T * p7.v.NCPBT * g.NKS * 64 : 0;  // v8 grad_x operand
+  a.nwc = r.wcy ? g.T * p7.v.NCPBT * g.NKS * 64 : 0;  // v8 grad_x operand
   const Plan5 p5 = f5_plan(g);
   a.wf5 = reinterpret_cast<v4i*>(wr + L.wf5);
   a.f5 = f5w_of(p5.v);
   a.nw5 = (int)f5_frag_items(g, p5);  // cim_fwd5_kernel's weight operand
   a.wg5 = reinterpret_cast<v4i*>(wr + L.wg5);
-  a.nwx5 = (int)(x5_frag_bytes(g) / 16);  // cim_bwd_gx5_kernel's weight operand
+  a.nwx5 = r.wg5 ? (int)(x5_frag_bytes(g) / 16) : 0;  // cim_bwd_gx5_kernel's weight operand
   a.wx6 = reinterpret_cast<v4i*>(wr + L.wx6);
-  a.nwx6 = (int)(r6_frag_bytes(g) / 16);  // cim_bwd_r6_kernel's gx operand
+  a.nwx6 = r.wx6 ? (int)(r6_frag_bytes(g) / 16) : 0;  // cim_bwd_r6_kernel's gx operand
   a.npp = g.T * g.nba * g.nbw * g.Opad + g.nbw * g.nba;
-  if (g.inference) {  // forward only: no backward words, none of the backward-only weight roles
-    a.xcb = nullptr;
-    a.nwg = a.nwc = a.nwx5 = a.nwx6 = 0;
-  }
   *nwblk = std::max(1, std::min(cdiv(a.nwf + a.nwg + a.nwc + a.nw5 + a.nwx5 + a.nwx6 + a.npp, 256), 1024));
   return a;
 }
 
-// the checks every module entry point shares; applies q->wprep.  shift: the cimq_module_shift_*
-// entry points (the shift ADC on the fast path, no prepared weight side)
+// the checks every module entry point shares, and the module form of the geometry (the output layout flag is
+// fixed here: every entry point plans with the same Geo from its first line); applies q->wprep.  shift: the
+// cimq_module_shift_* entry points (the shift ADC on the fast path, no prepared weight side)
 static int module_geo(const cimq_conv_desc* d, const cimq_lsq_desc* q, Geo* g, LsqArgs* la, bool shift = false) {
   CIMQ_TRY(make_geo(d, g));
   if (g->input_kind != CIMQ_INPUT_RAW_LSQ) return fail(CIMQ_EINVAL, "module entry points take the raw activation");
+  *g = module_form(*g);
   if (shift) {
-    if (g->variant != VAR_SHIFT_ROUND || !v7_plan(*g).ok || !shift_stats_ok(*g))
+    if (g->variant != VAR_SHIFT_ROUND || !route_of(*g).shift_stats)
       return fail(CIMQ_EUNSUPPORTED, "cimq_module_shift_*: the shift ADC on a fast-path layer only "
                                      "(adc_variant CIMQ_ADC_SHIFT_ROUND, adc 1.5, 2 or 3 equal slices, v7 shapes)");
     if (q && q->wprep) return fail(CIMQ_EINVAL, "cimq_module_shift_*: no prepared weight side");
@@ -613,6 +548,18 @@ static int module_geo(const cimq_conv_desc* d, const cimq_lsq_desc* q, Geo* g, L
   }
   CIMQ_TRY(lsq_args(*g, q, la));
   g->wbase = reinterpret_cast<const unsigned char*>(q->wprep);
+  return CIMQ_OK;
+}
+
+// alpha_cim is the sign / ternary ADC's scale (adc 1 / 1.5): required there, with its gradient in a backward, and
+// ignored elsewhere (la->nbits_alpha = 0 then says there is none)
+static int check_alpha(const Geo& g, LsqArgs* la, const float* alpha_cim, const float* grad_alpha_cim, bool bwd = true) {
+  if (g.mode != ADC_SIGN && g.mode != ADC_TERNARY) {
+    la->nbits_alpha = 0;
+    return CIMQ_OK;
+  }
+  if (!alpha_cim || (bwd && !grad_alpha_cim) || la->nbits_alpha == 0)
+    return fail(CIMQ_EINVAL, bwd ? "adc 1 / 1.5 need alpha_cim and grad_alpha_cim" : "adc 1 / 1.5 need alpha_cim");
   return CIMQ_OK;
 }
 
@@ -625,9 +572,9 @@ static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
   CIMQ_TRY(module_geo(d, q, &g, &la, beta_cim != nullptr));
   if (!x || !weight || !alpha_act || !alpha_weight || !binary_mask || !signed_act || !out || !ctx || !ws)
     return fail(CIMQ_EINVAL, "null pointer argument");
-  const bool has_alpha = g.mode == ADC_SIGN || g.mode == ADC_TERNARY;
-  if (has_alpha && (!alpha_cim || la.nbits_alpha == 0)) return fail(CIMQ_EINVAL, "adc 1 / 1.5 need alpha_cim");
-  if (!has_alpha) la.nbits_alpha = 0;
+  CIMQ_TRY(check_alpha(g, &la, alpha_cim, nullptr, false));
+  const bool has_alpha = la.nbits_alpha > 0;
+  const Route r = route_of(g);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   uint8_t* c = reinterpret_cast<uint8_t*>(ctx);
   CtxLayout L = ctx_layout(g);
@@ -642,7 +589,7 @@ static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
       nwblk = std::max(1, std::min(cdiv(a.nwf + a.nwg + a.nwc + a.nw5 + a.nwx5 + a.nwx6 + a.npp, 256), 1024));
     }
     if (g.wbase) nwblk = 0;  // weight side prepared (cimq_module_prepare): the activation quantiser only
-    if (fwd_actq_ok(g)) a.nact_blocks = 0;  // the forward's row staging quantises (stage_rows_q)
+    if (r.actq) a.nact_blocks = 0;  // the forward's row staging quantises (stage_rows_q)
     if (a.nact_blocks + nwblk == 0) goto prepared;
     {
     const int slot = prof_begin(KID_PREP_ACT, g, s);
@@ -662,13 +609,10 @@ static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
     }
   }
 prepared:
-  const Plan3 p = v3_plan(g);
-  if (p.ok) {
-    g.onchw = 1;
-    const ActQ aq{x, signed_act};
-    return launch_fwd_any(g, c, scal + 1, scal, out, nullptr, nullptr, s, fwd_actq_ok(g) ? &aq : nullptr);
-  }
-  if (dense_plan(g)) return launch_fwd_any(g, c, scal + 1, scal, out, nullptr, nullptr, s);  // P = 1: NCHW is [B, P, O]
+  const ActQ aq{x, signed_act};
+  // (the fast forward writes NCHW, g.onchw; the dense one's P = 1: NCHW is [B, P, O])
+  if (r.fwd != CIMQ_ROUTE_GENERAL)
+    return launch_fwd_any(g, c, scal + 1, scal, out, nullptr, nullptr, s, r.actq ? &aq : nullptr);
   // general kernels write [B, P, O]; the module returns NCHW
   WsLayout W = ws_layout(g);
   float* bpo = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(ws) + W.bpo);
@@ -691,55 +635,19 @@ int cimq_module_route(const cimq_conv_desc* d, int* route) {
   CIMQ_TRY(make_geo(d, &g));
   if (!route) return fail(CIMQ_EINVAL, "null route");
   if (g.input_kind != CIMQ_INPUT_RAW_LSQ) return fail(CIMQ_EINVAL, "module entry points take the raw activation");
-  // the ctx / workspace layouts must not depend on state the entry points set only at launch (the
-  // module path's NCHW flag): cimq_query_sizes, the prologue and the kernels compute them separately
-  // (the module path's ctx may END earlier -- no state-word region where its backward recomputes them -- and
-  // its backward's chunk / partial counts are that backward's; every offset and the workspace size agree)
-  {
-    Geo g1 = g;
-    g1.onchw = 1;
-    const CtxLayout a = ctx_layout(g), c = ctx_layout(g1);
-    const WsLayout w0 = ws_layout(g), w1 = ws_layout(g1);
-    if (c.total > a.total || a.wbytes != c.wbytes || a.st != c.st || a.wg5 != c.wg5 || a.wx6 != c.wx6 ||
-        w0.total != w1.total || w0.gw_slab != w1.gw_slab || w0.ga_slab != w1.ga_slab || w0.lsq_part != w1.lsq_part ||
-        (!r6_bwd(g1) && (w0.nchunks_bwd != w1.nchunks_bwd || act_parts(g) != act_parts(g1))))
-      return fail(CIMQ_EINVAL, "internal: layouts depend on the output layout flag");
-  }
-  g.onchw = 1;  // the module path's layout (as module_forward_impl sets it)
-  route[0] = route[1] = route[2] = CIMQ_ROUTE_GENERAL;
-  // forward (module_forward_impl -> launch_fwd_any -> launch_fwd)
-  if (v3_plan(g).ok) {
-    route[0] = (fwd_actq_ok(g) && f5_plan(g).ok) ? CIMQ_ROUTE_FWD5 : CIMQ_ROUTE_V3;
-  } else if (dense_plan(g)) {
-    route[0] = CIMQ_ROUTE_DENSE;
-  }
-  if (g.inference) {  // forward only: there is no backward
-    route[1] = route[2] = CIMQ_ROUTE_NONE;
-    return CIMQ_OK;
-  }
-  // backward (dispatch_bwd_any)
-  if (v7_bwd(g)) {
-    if (r6_bwd(g)) {
-      route[1] = route[2] = CIMQ_ROUTE_R6;
-    } else if (c1_plan(g).ok) {
-      route[1] = route[2] = CIMQ_ROUTE_C1;
-    } else if (v9_plan(g).ok) {
-      route[1] = route[2] = CIMQ_ROUTE_FUSED;
-    } else if (v7_plan(g).ok) {
-      route[1] = x5_plan(g).ok ? CIMQ_ROUTE_GX5 : CIMQ_ROUTE_V7;
-      route[2] = g5_plan(g).ok ? CIMQ_ROUTE_GW5 : CIMQ_ROUTE_V7;
-    }
-  } else if (dense_plan(g)) {
-    route[1] = route[2] = CIMQ_ROUTE_DENSE;
-  }
+  // the Function and the module entry points route a descriptor differently but share its buffers
+  if (!routes_agree(g)) return fail(CIMQ_EINVAL, "internal: layouts depend on the output layout flag");
+  const Route r = route_of(module_form(g));
+  route[0] = r.fwd;
+  route[1] = r.gx;
+  route[2] = r.gw;
   return CIMQ_OK;
 }
 
 int cimq_module_shift_supported(const cimq_conv_desc* d) {
   Geo g;
   if (make_geo(d, &g) != CIMQ_OK) return 0;
-  return (g.input_kind == CIMQ_INPUT_RAW_LSQ && g.variant == VAR_SHIFT_ROUND && v7_plan(g).ok && shift_stats_ok(g))
-             ? 1 : 0;
+  return (g.input_kind == CIMQ_INPUT_RAW_LSQ && g.variant == VAR_SHIFT_ROUND && route_of(g).shift_stats) ? 1 : 0;
 }
 
 int cimq_module_shift_forward(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* x, const float* weight,
@@ -765,45 +673,28 @@ static int module_backward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q,
   if (!grad_out || !x || !weight || !signed_act || !ctx || !grad_x || !grad_weight || !grad_alpha_act ||
       !grad_alpha_weight || !ws)
     return fail(CIMQ_EINVAL, "null pointer argument");
-  const bool has_alpha = g.mode == ADC_SIGN || g.mode == ADC_TERNARY;
-  if (has_alpha && (!alpha_cim || !grad_alpha_cim || la.nbits_alpha == 0))
-    return fail(CIMQ_EINVAL, "adc 1 / 1.5 need alpha_cim and grad_alpha_cim");
-  if (!has_alpha) la.nbits_alpha = 0;
+  CIMQ_TRY(check_alpha(g, &la, alpha_cim, grad_alpha_cim));
+  const Route r = route_of(g);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const uint8_t* c = reinterpret_cast<const uint8_t*>(ctx);
   uint8_t* w = reinterpret_cast<uint8_t*>(ws);
-  CtxLayout L = ctx_layout(g);
-  WsLayout W = ws_layout(g);
-  const float* scal = reinterpret_cast<const float*>(wreg(g, c) + L.lsq_scal);
+  const float* scal = reinterpret_cast<const float*>(wreg(g, c) + ctx_layout(g).lsq_scal);
   const float* sa = scal;
   const float* sw = scal + 1;
-  const Plan3 p = v3_plan(g);
   const float* gsrc = grad_out;
-  if (p.ok) {
-    g.onchw = 1;
-  } else if (!dense_plan(g)) {  // (P = 1: NCHW grad_out is already [B, P, O])
-    float* bpo = reinterpret_cast<float*>(w + W.bpo);
+  // the general backward reads [B, P, O] grad_out, also behind the fast forward (a v3 layer off the v7 plan, e.g.
+  // w4a4); the fast kernels read NCHW (g.onchw), and the dense path's P = 1
+  if (r.gx == CIMQ_ROUTE_GENERAL) {
+    float* bpo = reinterpret_cast<float*>(w + ws_layout(g).bpo);
     hipLaunchKernelGGL(nchw_to_bpo_kernel, dim3(std::min(cdiv((long long)g.M * g.O, 256), 8192)), dim3(256), 0, s,
                        g, grad_out, bpo);
     CIMQ_TRY(check_hip("nchw_to_bpo"));
     gsrc = bpo;
   }
-  bool lsq_fused = false;
-  const bool defer = (q->flags & CIMQ_LSQ_DEFER_GW) && gw_deferrable(g);
-  CIMQ_TRY(dispatch_bwd_any(g, c, sw, sa, signed_act, gsrc, x, grad_x, w, s, &lsq_fused, defer ? 1 : 3));
-  // the act-LSQ partials: fused into the fast grad_x kernel, a separate pass otherwise
-  float* part = reinterpret_cast<float*>(w + W.lsq_part);
-  int nparts;
-  if (lsq_fused) {
-    nparts = act_parts(g);
-  } else {
-    int grid = cdiv(g.Nin, 256);
-    if (grid > kLsqParts) grid = kLsqParts;
-    hipLaunchKernelGGL(lsq_act_bwd_kernel, dim3(grid), dim3(256), 0, s, g.Nin, x, sa, g.lsq_qp, grad_x, part);
-    CIMQ_TRY(check_hip("lsq_act_bwd"));
-    nparts = grid;
-  }
-  if (nparts != act_parts(g)) return fail(CIMQ_EINVAL, "internal: act-LSQ partial count mismatch");
+  const bool defer = (q->flags & CIMQ_LSQ_DEFER_GW) && r.gw_own;
+  CIMQ_TRY(dispatch_bwd_any(g, c, sw, sa, signed_act, gsrc, x, grad_x, w, s, defer ? 1 : 3));
+  // the act-LSQ partials: fused into the fast grad_x kernel, a separate pass otherwise (the epilogue sums them)
+  CIMQ_TRY(launch_act_lsq(g, x, sa, grad_x, w, nullptr, s));
   if (pend) {
     // the epilogue joins the pending ones: cimq_pending_flush (or a full list, or a layer whose
     // gradient buffers a pending one writes) launches them all, packed.  Until then this layer's
@@ -875,10 +766,7 @@ int cimq_module_backward_tail(const cimq_conv_desc* d, const cimq_lsq_desc* q, c
   CIMQ_TRY(module_geo(d, q, &g, &la));
   if (!weight || !ctx || !grad_weight || !grad_alpha_act || !grad_alpha_weight || !ws)
     return fail(CIMQ_EINVAL, "null pointer argument");
-  const bool has_alpha = g.mode == ADC_SIGN || g.mode == ADC_TERNARY;
-  if (has_alpha && (!alpha_cim || !grad_alpha_cim || la.nbits_alpha == 0))
-    return fail(CIMQ_EINVAL, "adc 1 / 1.5 need alpha_cim and grad_alpha_cim");
-  if (!has_alpha) la.nbits_alpha = 0;
+  CIMQ_TRY(check_alpha(g, &la, alpha_cim, grad_alpha_cim));
   return module_tail(g, la, q, reinterpret_cast<const uint8_t*>(ctx), reinterpret_cast<uint8_t*>(ws), weight,
                      alpha_cim, grad_weight, grad_alpha_act, grad_alpha_weight, grad_alpha_cim,
                      reinterpret_cast<hipStream_t>(stream));
@@ -895,19 +783,14 @@ int cimq_module_backward_params(const cimq_conv_desc* d, const cimq_lsq_desc* q,
   if (!(q->flags & CIMQ_LSQ_DEFER_GW)) return fail(CIMQ_EINVAL, "cimq_module_backward_params needs CIMQ_LSQ_DEFER_GW");
   if (!grad_out || !weight || !ctx || !grad_weight || !grad_alpha_act || !grad_alpha_weight || !ws)
     return fail(CIMQ_EINVAL, "null pointer argument");
-  const bool has_alpha = g.mode == ADC_SIGN || g.mode == ADC_TERNARY;
-  if (has_alpha && (!alpha_cim || !grad_alpha_cim || la.nbits_alpha == 0))
-    return fail(CIMQ_EINVAL, "adc 1 / 1.5 need alpha_cim and grad_alpha_cim");
-  if (!has_alpha) la.nbits_alpha = 0;
+  CIMQ_TRY(check_alpha(g, &la, alpha_cim, grad_alpha_cim));
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const uint8_t* c = reinterpret_cast<const uint8_t*>(ctx);
   uint8_t* w = reinterpret_cast<uint8_t*>(ws);
-  if (v3_plan(g).ok) g.onchw = 1;  // as module_backward_impl: the backward that ran was the module path's
-  if (gw_deferrable(g)) {
+  if (route_of(g).gw_own) {
     // the grad_w kernel cimq_module_backward left out (grad_out NCHW, as the v7 path reads it there)
     const float* scal = reinterpret_cast<const float*>(wreg(g, c) + ctx_layout(g).lsq_scal);
-    bool lsq_fused = false;
-    CIMQ_TRY(dispatch_bwd_any(g, c, scal + 1, scal, nullptr, grad_out, nullptr, nullptr, w, s, &lsq_fused, 2));
+    CIMQ_TRY(dispatch_bwd_any(g, c, scal + 1, scal, nullptr, grad_out, nullptr, nullptr, w, s, 2));
   }
   return module_tail(g, la, q, c, w, weight, alpha_cim, grad_weight, grad_alpha_act, grad_alpha_weight,
                      grad_alpha_cim, s);
@@ -933,14 +816,10 @@ int cimq_module_shift_backward(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const uint8_t* c = reinterpret_cast<const uint8_t*>(ctx);
   uint8_t* w = reinterpret_cast<uint8_t*>(ws);
-  CtxLayout L = ctx_layout(g);
   WsLayout W = ws_layout(g);
-  const float* scal = reinterpret_cast<const float*>(wreg(g, c) + L.lsq_scal);
-  g.onchw = 1;
-  bool lsq_fused = false;
-  CIMQ_TRY(dispatch_bwd_any(g, c, scal + 1, scal, signed_act, grad_out, x, grad_x, w, s, &lsq_fused));
-  if (!lsq_fused)
-    return fail(CIMQ_EINVAL, "internal: act-LSQ partials off the fused grad_x");
+  const float* scal = reinterpret_cast<const float*>(wreg(g, c) + ctx_layout(g).lsq_scal);
+  // (module_geo: a v7-plan layer, whose grad_x kernel leaves the act-LSQ partials)
+  CIMQ_TRY(dispatch_bwd_any(g, c, scal + 1, scal, signed_act, grad_out, x, grad_x, w, s));
   // d loss / d alpha_q and grad_beta (scale_shift.py:488-501) from the statistics kernel, then the
   // module epilogue (grad_w + weight-LSQ backward, alpha_cim's quantiser, the step sizes) from there
   CIMQ_TRY(launch_shift_stats(g, c, scal + 1, scal, grad_out, binary_mask, w, reinterpret_cast<float*>(w + W.gaq),
@@ -966,14 +845,11 @@ int cimq_module_prepare(int n, const cimq_prepare_item* items, void* stream) {
     CIMQ_TRY(module_geo(it.desc, &q, &g, &la));
     if (!it.weight || !it.alpha_act || !it.alpha_weight || !it.binary_mask || !it.wprep)
       return fail(CIMQ_EINVAL, "item %d: null pointer argument", i);
-    const bool has_alpha = g.mode == ADC_SIGN || g.mode == ADC_TERNARY;
-    if (has_alpha && (!it.alpha_cim || la.nbits_alpha == 0))
-      return fail(CIMQ_EINVAL, "item %d: adc 1 / 1.5 need alpha_cim", i);
-    if (!has_alpha) la.nbits_alpha = 0;
+    CIMQ_TRY(check_alpha(g, &la, it.alpha_cim, nullptr, false));
     PrepJob& j = pk.job[pk.n];
     j.g = g;
     j.q = la;
-    j.a = module_prep_args(g, nullptr, it.weight, it.alpha_act, it.alpha_weight, has_alpha ? it.alpha_cim : nullptr,
+    j.a = module_prep_args(g, nullptr, it.weight, it.alpha_act, it.alpha_weight, la.nbits_alpha ? it.alpha_cim : nullptr,
                            it.binary_mask, nullptr, nullptr, &j.nwblk);
     j.a.nact_blocks = 0;
     pk.blk0[pk.n] = grid;

@@ -177,99 +177,6 @@ inline int make_geo(const cimq_conv_desc* d, Geo* out) {
   return CIMQ_OK;
 }
 
-// ctx: the weight-side regions first ([0, wbytes): weight operand fragments, ADC / STE
-// parameters, the module's step sizes -- functions of the parameters only, so a prepared
-// buffer (cimq_module_prepare, cimq_lsq_desc.wprep) can hold them instead), then the
-// activation-side regions (slice words, state words) of one forward.
-inline bool dense_plan(const Geo& g);
-
-struct CtxLayout {
-  size_t xcode, xhat, alut, wfrag, wf5, wg5, wx6, wgx, wcy, thi, tlo, mlo, mhi, coef, alpha, beta, bsum, ckj, flags, st;
-  size_t lsq_scal;  // module entry points: sa, sw, alpha scale, max, min
-  size_t wbytes;    // end of the weight-side regions
-  size_t total;
-};
-
-inline size_t f5_frag_bytes(const Geo& g);  // after f5_plan
-inline size_t x5_frag_bytes(const Geo& g);  // after x5_plan
-inline size_t r6_frag_bytes(const Geo& g);  // after r6_plan
-inline bool r6_bwd(const Geo& g);           // after r6_plan
-inline bool fwd_actq_ok(const Geo& g);      // after v7_plan
-
-// A forward-only call (CIMQ_OPT_INFERENCE) whose forward kernel quantises the activation in its own row staging
-// (stage_rows_q / cim_fwd5_kernel): no prologue pass over x, no slice words in the ctx.  The module entry points'
-// fwd_actq_ok layers, and the same shapes through cimq_forward (cim_fwd_v3_kernel with [B, P, O] output).
-inline bool inf_actq(const Geo& g) { return g.inference && fwd_actq_ok(g); }
-
-inline CtxLayout ctx_layout_compute(const Geo& g) {
-  CtxLayout L;
-  size_t o = 0;
-  const size_t npar = (size_t)g.T * g.nba * g.nbw * g.Opad;
-  L.wfrag = o; o = align256(o + (size_t)g.T * g.KS * g.NBLK * 64 * 16);
-  L.wf5 = o; o = align256(o + f5_frag_bytes(g));  // cim_fwd5_kernel's weight operand
-  L.wg5 = o; o = align256(o + x5_frag_bytes(g));  // cim_bwd_gx5_kernel's weight operand
-  L.wx6 = o; o = align256(o + r6_frag_bytes(g));  // cim_bwd_r6_kernel's gx operand
-  L.wgx = o; o = align256(o + (size_t)g.T * g.FBT * g.NKS * 64 * 16);
-  L.wcy = o; o = align256(o + (size_t)g.T * 12 * g.NKS * 64 * 16);  // v8 grad_x operand (<= 12 blocks / tile)
-  L.thi = o; o = align256(o + npar * 4);
-  L.tlo = o; o = align256(o + npar * 4);
-  L.mlo = o; o = align256(o + npar * 4);
-  L.mhi = o; o = align256(o + npar * 4);
-  L.coef = o; o = align256(o + npar * 4);
-  L.alpha = o; o = align256(o + npar * 4);
-  L.beta = o; o = align256(o + npar * 4);
-  L.bsum = o; o = align256(o + (size_t)g.Opad * 4);
-  L.ckj = o; o = align256(o + 3 * 64 * 4);
-  L.flags = o; o = align256(o + 16);
-  L.lsq_scal = o; o = align256(o + 16 * 4);
-  L.wbytes = o;
-  L.xcode = o; o = align256(o + (inf_actq(g) ? (size_t)0 : (size_t)g.Nin * g.NBP));  // forward slice bytes
-  if (g.inference) {
-    // forward only (CIMQ_OPT_INFERENCE): the ctx ends here -- no backward slice words, no code table, no state;
-    // their offsets point at the end and nothing is written through them
-    L.xhat = L.alut = L.st = L.total = o;
-    return L;
-  }
-  L.xhat = o; o = align256(o + (size_t)g.Nin * g.NBP);   // backward (int8 ctx) slice bytes
-  L.alut = o; o = align256(o + (size_t)4 * 301);         // ctx codes: code -> ctx word (ctx_codes), format word 300
-  // per-partial-sum state words written by the fast forward (cim_fwd_v3_kernel)
-  // (v7: one uint32 per (i, m, o) -- never larger for nbw >= 2; the max covers nbw == 1)
-  // state words: per-(k) words of the v3-v6 kernels, or the v7 compact words (4 B, or three
-  // 64-bit planes for w8a8) per (tile, pixel, channel)
-  // (the dense path, cimq_part_dense.hip: a uint2 of three 16-bit planes per (i, m, o))
-  // (none where the module backward recomputes the partial sums, cim_bwd_r6_kernel: the region is last, so
-  // the module path's smaller ctx -- cimq_sizes.module_ctx_bytes -- keeps every other offset)
-  L.st = o; o = align256(o + (r6_bwd(g) ? (size_t)0
-                                        : std::max({(size_t)g.T * g.nbw * g.M * g.O * (g.NBP == 4 ? 2 : 4),
-                                                    (size_t)g.T * g.M * g.O * (g.NBP == 4 ? 4 : 24),
-                                                    dense_plan(g) ? (size_t)g.T * g.M * g.O * 8 : (size_t)0})));
-  L.total = o;
-  return L;
-}
-inline CtxLayout ctx_layout(const Geo& g) { return memo_geo<CtxLayout, ctx_layout_compute>(g); }
-
-// base of the weight-side regions of a ctx: the prepared buffer when the call has one
-inline uint8_t* wreg(const Geo& g, const uint8_t* ctx) {
-  return const_cast<uint8_t*>(g.wbase ? g.wbase : ctx);
-}
-
-inline Params params_of(const Geo& g, uint8_t* ctx) {
-  CtxLayout L = ctx_layout(g);
-  uint8_t* base = wreg(g, ctx);
-  Params p;
-  p.thi = reinterpret_cast<int*>(base + L.thi);
-  p.tlo = reinterpret_cast<int*>(base + L.tlo);
-  p.mlo = reinterpret_cast<int*>(base + L.mlo);
-  p.mhi = reinterpret_cast<int*>(base + L.mhi);
-  p.coef = reinterpret_cast<float*>(base + L.coef);
-  p.alpha = reinterpret_cast<float*>(base + L.alpha);
-  p.beta = reinterpret_cast<float*>(base + L.beta);
-  p.bsum = reinterpret_cast<float*>(base + L.bsum);
-  p.ckj = reinterpret_cast<float*>(base + L.ckj);
-  p.flags = reinterpret_cast<int*>(base + L.flags);
-  return p;
-}
-
 // pixel chunking of the gw / init kernel: ~1024 blocks over (chunks x tiles x 32-col groups)
 inline void gw_chunks(const Geo& g, int* rows_per_chunk, int* nchunks) {
   const int og = (g.OB16 + 1) / 2;
@@ -367,66 +274,79 @@ struct Plan7 {
   int pairs;
 };
 
-// grad_w LDS plane pitches.  A row group's A fragment: lane l reads 16 B (8 bf16) at plane
-// kw*KWP + channel c*CPITCH + staged row (oh*SH + kh)*Wo + ow0, for row f = 16*gr + (l & 15) =
-// (c, kh, kw) and pixels 32*wave + 8*(l >> 4) of the stage.  ds_read_b128 serves a wave in 4 fixed
-// groups of 16 lanes, one LDS cycle per distinct address on a busy 16-B slot of the 256-B bank row
-// (MI355X_MICROARCH.md, LDS).  The unpadded pitches (CPITCH = NSLOT*Wo + 8, KWP = CPL*CPITCH) put
-// the three kw planes of a row on one slot: 140 cycles per stage-wave where 36 is the floor.
-inline int gw_read_cycles(const Geo& g, const V7& v, int cp, int kwp) {
+// LDS cycles of one ds_read_b128 of a wave whose lane l reads 16 B (8 bf16) at element address addr(l) (< 0: no
+// access).  The instruction serves the wave in 4 fixed groups of 16 lanes, one LDS cycle per distinct address on
+// a busy 16-B slot of the 256-B bank row (MI355X_MICROARCH.md, LDS).
+template <class F>
+inline int b128_read_cycles(F addr) {
   static const int grp[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
                                  {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
                                  {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},
                                  {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
   int cyc = 0;
-  for (int wave = 0; wave < 4; ++wave)
-    for (int gr = 0; gr * 16 < v.CPL * g.KHW; ++gr)
-      for (int q = 0; q < 4; ++q) {
-        int addr[16], slot[16];
-        for (int t = 0; t < 16; ++t) {
-          const int l = grp[q][t], f = 16 * gr + (l & 15);
-          const int c = f / g.KHW, tap = f - c * g.KHW, kh = tap / g.KW, kw = tap - kh * g.KW;
-          const int moff = 32 * wave + 8 * (l >> 4);
-          const int img = v.whole ? moff / g.P : 0, pim = v.whole ? moff % g.P : moff;
-          addr[t] = c < v.CPL ? kw * kwp + c * cp + (img * g.H + (pim / g.Wo) * g.SH + kh) * g.Wo + pim % g.Wo : -1;
-          slot[t] = addr[t] < 0 ? -1 : (addr[t] / 8) % 16;  // rows past CPL read one zero pad (broadcast)
-        }
-        int worst = 1;
-        for (int s = 0; s < 16; ++s) {
-          int n = 0;
-          for (int t = 0; t < 16; ++t) {
-            if (slot[t] != s) continue;
-            bool dup = false;
-            for (int u = 0; u < t; ++u) dup = dup || addr[u] == addr[t];
-            n += dup ? 0 : 1;
-          }
-          worst = std::max(worst, n);
-        }
-        cyc += worst;
+  for (int q = 0; q < 4; ++q) {
+    int a[16];
+    for (int t = 0; t < 16; ++t) a[t] = addr(grp[q][t]);
+    int worst = 1;
+    for (int s = 0; s < 16; ++s) {
+      int n = 0;
+      for (int t = 0; t < 16; ++t) {
+        if (a[t] < 0 || (a[t] / 8) % 16 != s) continue;
+        bool dup = false;
+        for (int u = 0; u < t; ++u) dup = dup || a[u] == a[t];
+        n += dup ? 0 : 1;
       }
+      worst = std::max(worst, n);
+    }
+    cyc += worst;
+  }
   return cyc;
 }
-// pads in 8-element (16-B) steps -- CPITCH by up to 24, KWP by up to 120 elements (<= 10 % more LDS) --
-// with the fewest read cycles, then the smallest planes; cached per geometry
-inline void gw_pitches(const Geo& g, V7& v) {
+// The bf16 plane pitches of a grad_w stage: CPITCH = cp0 (+ 8a, a < 4) per channel and KWP = nch * CPITCH (+ 8b,
+// b < 16) per kw plane -- pads in 16-B steps, <= 10 % more LDS -- with the fewest cycles(cp, kwp), then the
+// smallest planes; cached per key (one cache per caller)
+template <size_t N, class F>
+inline void plane_pitches(const std::array<int, N>& key, int cp0, int nch, bool search, F cycles, int* cpitch,
+                          int* kwp) {
   static std::mutex mu;
-  static std::map<std::array<int, 8>, std::pair<int, int>> memo;
-  const std::array<int, 8> key = {g.C, g.H, g.Wo, g.P, g.SH, g.KHW, v.NSLOT, v.whole};
+  static std::map<std::array<int, N>, std::pair<int, int>> memo;
   std::lock_guard<std::mutex> lk(mu);
   auto it = memo.find(key);
   if (it == memo.end()) {
-    const int cp0 = v.NSLOT * g.Wo + 8;
-    int best = -1, bcp = cp0, bkwp = v.CPL * cp0;
+    int best = -1, bcp = cp0, bkwp = nch * cp0;
     for (int a = 0; a < 4; ++a)
       for (int b = 0; b < 16; ++b) {
-        const int cp = cp0 + 8 * a, kwp = v.CPL * cp + 8 * b;
-        const int c = tune("GW_PAD", 1) ? gw_read_cycles(g, v, cp, kwp) : (a + b == 0 ? 0 : 1);
-        if (best < 0 || c < best || (c == best && kwp < bkwp)) { best = c; bcp = cp; bkwp = kwp; }
+        const int cp = cp0 + 8 * a, kp = nch * cp + 8 * b;
+        const int c = search ? cycles(cp, kp) : (a + b == 0 ? 0 : 1);
+        if (best < 0 || c < best || (c == best && kp < bkwp)) { best = c; bcp = cp; bkwp = kp; }
       }
     it = memo.emplace(key, std::make_pair(bcp, bkwp)).first;
   }
-  v.CPITCH = it->second.first;
-  v.KWP = it->second.second;
+  *cpitch = it->second.first;
+  *kwp = it->second.second;
+}
+
+// grad_w (cim_bwd_gw_v7_kernel) plane pitches.  A row group's A fragment: lane l reads plane kw*KWP + channel
+// c*CPITCH + staged row (oh*SH + kh)*Wo + ow0, for row f = 16*gr + (l & 15) = (c, kh, kw) and pixels
+// 32*wave + 8*(l >> 4) of the stage; rows past CPL read one zero pad (a broadcast, not counted).  The unpadded
+// pitches (CPITCH = NSLOT*Wo + 8, KWP = CPL*CPITCH) put the three kw planes of a row on one slot: 140 cycles per
+// stage-wave where 36 is the floor.
+inline void gw_pitches(const Geo& g, V7& v) {
+  const std::array<int, 8> key = {g.C, g.H, g.Wo, g.P, g.SH, g.KHW, v.NSLOT, v.whole};
+  auto cycles = [&](int cp, int kwp) {
+    int cyc = 0;
+    for (int wave = 0; wave < 4; ++wave)
+      for (int gr = 0; gr * 16 < v.CPL * g.KHW; ++gr)
+        cyc += b128_read_cycles([&](int l) {
+          const int f = 16 * gr + (l & 15);
+          const int c = f / g.KHW, tap = f - c * g.KHW, kh = tap / g.KW, kw = tap - kh * g.KW;
+          const int moff = 32 * wave + 8 * (l >> 4);
+          const int img = v.whole ? moff / g.P : 0, pim = v.whole ? moff % g.P : moff;
+          return c < v.CPL ? kw * kwp + c * cp + (img * g.H + (pim / g.Wo) * g.SH + kh) * g.Wo + pim % g.Wo : -1;
+        });
+    return cyc;
+  };
+  plane_pitches(key, v.NSLOT * g.Wo + 8, v.CPL, tune("GW_PAD", 1) != 0, cycles, &v.CPITCH, &v.KWP);
 }
 
 inline Plan7 v7_plan_compute(const Geo& g) {
@@ -520,63 +440,23 @@ struct Plan9 {
   V9 v;
 };
 
-// LDS read cycles of the fused kernel's grad_w A fragments (ds_read_b128, four fixed groups of 16 lanes,
-// one cycle per distinct address on a busy 16-B slot of the 256-B bank row; MI355X_MICROARCH.md, LDS) for
-// plane pitches cp (channel) and kwp (kw plane), over every row group of tile 0: lane l reads row
-// f = 16 gr + (l & 15) = (c, kh, kw) at kw*kwp + c*cp + kh*W + 8 (l >> 4); rows past the tile read one
-// zero pad (a broadcast)
-inline int fused_read_cycles(const Geo& g, int cp, int kwp) {
-  static const int grp[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27},
-                                 {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
-                                 {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59},
-                                 {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
-  const int flen = std::min(g.K, g.xbar);
-  int cyc = 0;
-  for (int gr = 0; gr * 16 < flen; ++gr)
-    for (int q = 0; q < 4; ++q) {
-      int addr[16], slot[16];
-      for (int t = 0; t < 16; ++t) {
-        const int l = grp[q][t], f = 16 * gr + (l & 15);
-        const int c = f / 9, tap = f - 9 * c, kh = tap / 3, kw = tap - 3 * kh;
-        addr[t] = f < flen ? kw * kwp + c * cp + kh * g.W + 8 * (l >> 4) : cp - 8;
-        slot[t] = (addr[t] / 8) % 16;
-      }
-      int worst = 1;
-      for (int sl = 0; sl < 16; ++sl) {
-        int n = 0;
-        for (int t = 0; t < 16; ++t) {
-          if (slot[t] != sl) continue;
-          bool dup = false;
-          for (int u = 0; u < t; ++u) dup = dup || addr[u] == addr[t];
-          n += dup ? 0 : 1;
-        }
-        worst = std::max(worst, n);
-      }
-      cyc += worst;
-    }
-  return cyc;
-}
-// plane pitches: CPITCH = PROWS*W + 8 (+ 8a), KWP = NCG*CPITCH (+ 8b), the fewest read cycles, then the
-// smallest planes; cached per geometry
+// the fused kernel's grad_w plane pitches (CPITCH = PROWS*W + 8, KWP = NCG*CPITCH unpadded), over every row
+// group of tile 0: lane l reads row f = 16 gr + (l & 15) = (c, kh, kw) at kw*kwp + c*cp + kh*W + 8 (l >> 4); rows
+// past the tile read one zero pad at cp - 8
 inline void fused_pitches(const Geo& g, V9& v) {
-  static std::mutex mu;
-  static std::map<std::array<int, 6>, std::pair<int, int>> memo;
   const std::array<int, 6> key = {g.W, g.K, g.xbar, v.PROWS, v.NCG, 0};
-  std::lock_guard<std::mutex> lk(mu);
-  auto it = memo.find(key);
-  if (it == memo.end()) {
-    const int cp0 = v.PROWS * g.W + 8;
-    int best = -1, bcp = cp0, bkwp = v.NCG * cp0;
-    for (int a = 0; a < 4; ++a)
-      for (int b = 0; b < 16; ++b) {
-        const int cp = cp0 + 8 * a, kwp = v.NCG * cp + 8 * b;
-        const int c = tune("FUSED_PAD", 1) ? fused_read_cycles(g, cp, kwp) : (a + b == 0 ? 0 : 1);
-        if (best < 0 || c < best || (c == best && kwp < bkwp)) { best = c; bcp = cp; bkwp = kwp; }
-      }
-    it = memo.emplace(key, std::make_pair(bcp, bkwp)).first;
-  }
-  v.CPITCH = it->second.first;
-  v.KWP = it->second.second;
+  const int flen = std::min(g.K, g.xbar);
+  auto cycles = [&](int cp, int kwp) {
+    int cyc = 0;
+    for (int gr = 0; gr * 16 < flen; ++gr)
+      cyc += b128_read_cycles([&](int l) {
+        const int f = 16 * gr + (l & 15);
+        const int c = f / 9, tap = f - 9 * c, kh = tap / 3, kw = tap - 3 * kh;
+        return f < flen ? kw * kwp + c * cp + kh * g.W + 8 * (l >> 4) : cp - 8;
+      });
+    return cyc;
+  };
+  plane_pitches(key, v.PROWS * g.W + 8, v.NCG, tune("FUSED_PAD", 1) != 0, cycles, &v.CPITCH, &v.KWP);
 }
 
 inline Plan9 v9_plan_compute(const Geo& g) {
@@ -725,23 +605,20 @@ inline bool shift_table_fits(const Geo& g) {
   return (size_t)g.nbw * g.nba * 16 * (2 * shift_table_range(g) + 1) * 4 <= 48 * 1024;
 }
 
-// the backward runs on the v7 plan's state words (v7 / fused / first-conv kernels): the library ADC, or
-// the shift ADC where the statistics kernel takes it; every other layer runs the general kernels
-// the module forward with the LSQ activation quantiser fused into the forward's row staging: the
-// v3 fast path with v7 state words (so no later kernel reads the forward slice words), 4-byte slice
-// words, the prologue's word table applicable, and not the first conv (whose backward re-reads the
-// forward words) or a shift layer (its statistics kernel does)
 struct ActQ {
   const float* x;
   const float* signed_act;
 };
-inline bool v7_bwd(const Geo& g);
-inline bool fwd_actq_ok(const Geo& g);
 
+// the backward runs on the v7 plan's state words (v7 / fused / first-conv kernels): the library ADC, or
+// the shift ADC where the statistics kernel takes it; every other layer runs the general kernels
 inline bool v7_bwd(const Geo& g) {
   return v7_plan(g).ok && (g.variant == VAR_LIBRARY || shift_stats_ok(g));
 }
 
+// the LSQ activation quantiser can run in the forward's row staging: the v3 fast path with v7 state words (so
+// no later kernel reads the forward slice words), 4-byte slice words, the prologue's word table applicable, and
+// not the first conv (whose backward re-reads the forward words) or a shift layer (its statistics kernel does)
 inline bool fwd_actq_ok(const Geo& g) {
   if (tune("ACTQ", 1) == 0) return false;
   return g.input_kind == CIMQ_INPUT_RAW_LSQ && g.NBP == 4 && g.variant == VAR_LIBRARY && g.W % 4 == 0 &&
@@ -859,8 +736,8 @@ inline PlanG5 g5_plan_compute(const Geo& g) {
   if (g.C % 16 != 0 || g.O % 16 != 0 || g.Wo % 4 != 0) return p;
   if (g.P >= 128 ? g.P % 128 != 0 : (128 % g.P != 0 || g.P % 16 != 0)) return p;
   if (g.M % 128 != 0) return p;  // whole 128-pixel m-tiles
-  // (no dependence on g.onchw: the ctx / workspace layouts are computed from the same Geo at query, prologue
-  // and launch time, and the module backward sets onchw only at launch; the kernel reads both layouts)
+  // (no dependence on g.onchw: the plans size weight-side ctx regions, which the Function and the module form
+  // of a descriptor share -- routes_agree; the kernel reads either grad_out layout)
   if (g.T != (9 * g.C + 127) / 128) return p;
   G5& v = p.v;
   v.lwo = 0;
@@ -963,18 +840,201 @@ inline PlanR6 r6_plan_compute(const Geo& g) {
 }
 inline PlanR6 r6_plan(const Geo& g) { return memo_geo<PlanR6, r6_plan_compute>(g); }
 inline size_t r6_frag_bytes(const Geo& g) { return r6_plan(g).ok ? (size_t)kR6WxItems * 16 : 0; }
-// decided at launch: the module entry points (g.onchw) run cim_fwd5_kernel, whose operand the recompute needs; the
-// Function path's forward writes state words and keeps the state-word backward
-inline bool r6_bwd(const Geo& g) { return g.onchw && !g.inference && r6_plan(g).ok; }
 
-// The module path's ctx as ONE activation-code byte per element (instead of the 4-byte backward word):
-// where the forward is cim_fwd5_kernel (which quantises the activation itself) and the layer's grad_w
-// is cim_bwd_gw5_kernel (dispatch_bwd_any's order: c1, fused, then the v7 pair), the only ctx reader.
-// Decided at launch: g.onchw is the module entry points' flag (the Function path's prologue writes words).
-// (c1_plan / v9_plan are declared above ws_layout.)
-inline bool ctx_codes(const Geo& g) {
-  return g.onchw && fwd_actq_ok(g) && f5_plan(g).ok && v7_bwd(g) && !c1_plan(g).ok && !v9_plan(g).ok &&
-         g5_plan(g).ok && !r6_bwd(g);
+// ---- the route: which kernels run a layer, and what they leave in the ctx and the workspace ----
+// The plans above say where each kernel applies; route_of alone says which of the applicable ones runs.  The
+// layouts, the prologues and every launcher read the Route.  g.onchw (the module entry points' output layout,
+// fixed by module_form before anything is asked) is part of the geometry: the Function entry points (0) and the
+// module entry points route a layer differently, with one weight-side and workspace layout (routes_agree).
+
+// the state words the forward writes into the ctx and the backward reads
+enum StateFmt {
+  ST_NONE,    // none: the backward recomputes the partial sums (cim_bwd_r6_kernel), or a forward-only call
+  ST_PERK,    // a word per (tile, weight slice, pixel, channel): the general kernels, cim_fwd_v3_kernel<CST 0>
+  ST_V7,      // v7 compact words, 4 B per (tile, pixel, channel): w2a2 / w3a3
+  ST_PLANES,  // three 64-bit planes per (tile, pixel, channel): w8a8
+  ST_C1,      // w8a8 first conv: its backward (cim_bwd_c1_kernel) recomputes them from the slice words
+  ST_DENSE,   // a uint2 of three 16-bit planes per (tile, row, channel): the dense path
+};
+
+struct Route {
+  int fwd, gx, gw;   // CIMQ_ROUTE_*; gx = gw = CIMQ_ROUTE_NONE in a forward-only call (CIMQ_OPT_INFERENCE)
+  bool actq;         // the forward quantises the activation in its own row staging: no prologue pass over x
+  StateFmt state;
+  int cst;           // cim_fwd_v3_kernel's CST instance for that format (forward only: the 10 + CST forms)
+  size_t st_bytes;   // the ctx's state-word region
+  bool codes;        // the ctx holds one activation-code byte per element, not the 4-byte backward word
+  bool lsq_fused;    // grad_x runs the act-LSQ backward too, leaving act_parts partials in the workspace
+  int act_parts;     // (not fused: one per lsq_act_bwd_kernel block)
+  int nchunks_bwd;   // slabs of grad_w / grad_alpha partials the backward leaves
+  int nchunks_ws;    // slabs the workspace holds: the Function and the module backward of a layer share a size
+  bool gw_own;       // grad_w is a launch of its own: CIMQ_LSQ_DEFER_GW can defer it
+  bool gxw5;         // ... unless deferred, cim_bwd_gx5_kernel and cim_bwd_gw5_kernel share one grid
+  bool shift_stats;  // a shift-ADC layer whose step-size gradients the statistics kernel takes (shift_stats_ok)
+  bool wgx, wcy, wg5, wx6;  // the backward weight operands the prologue builds
+};
+
+inline Route route_compute(const Geo& g) {
+  Route r;
+  memset(&r, 0, sizeof(r));
+  const bool raw = g.input_kind == CIMQ_INPUT_RAW_LSQ, v7b = v7_bwd(g), dense = dense_plan(g);
+  // forward.  cim_fwd5_kernel writes NCHW only; the Function path fuses the quantiser only where no backward
+  // needs the slice words
+  r.actq = fwd_actq_ok(g) && (g.onchw || g.inference);
+  r.fwd = v3_plan(g).ok ? ((g.onchw && r.actq && f5_plan(g).ok) ? CIMQ_ROUTE_FWD5 : CIMQ_ROUTE_V3)
+        : dense         ? CIMQ_ROUTE_DENSE
+                        : CIMQ_ROUTE_GENERAL;
+  // backward: the recompute (the module path's forward is cim_fwd5_kernel, whose operand it needs), the first
+  // conv, the fused kernel, then the v7 pair with gx5 / gw5 in either role; else dense, else general
+  int nchunks, rows;
+  gw_chunks(g, &rows, &nchunks);
+  const int gen_parts = std::min(cdiv(g.Nin, 256), kLsqParts);
+  r.act_parts = gen_parts;
+  if (v7b) {
+    r.lsq_fused = raw;
+    r.nchunks_bwd = r.act_parts = g.B;  // the one-kernel backwards: a workgroup per image
+    if (g.onchw && !g.inference && r6_plan(g).ok) {
+      r.gx = r.gw = CIMQ_ROUTE_R6;
+    } else if (c1_plan(g).ok) {
+      r.gx = r.gw = CIMQ_ROUTE_C1;
+    } else if (v9_plan(g).ok) {
+      r.gx = r.gw = CIMQ_ROUTE_FUSED;
+    } else {
+      const Plan7 p7 = v7_plan(g);
+      const PlanX5 px = x5_plan(g);
+      const PlanG5 pg = g5_plan(g);
+      r.gx = px.ok ? CIMQ_ROUTE_GX5 : CIMQ_ROUTE_V7;
+      r.gw = pg.ok ? CIMQ_ROUTE_GW5 : CIMQ_ROUTE_V7;
+      r.act_parts = px.ok ? px.nblk : g.B * p7.v.nbands;
+      r.nchunks_bwd = pg.ok ? pg.v.nchunks : p7.v.nchunks;
+      r.gw_own = g.variant == VAR_LIBRARY;
+      r.gxw5 = px.ok && pg.ok && tune("GXW5", 1);
+    }
+    if (!r.lsq_fused) r.act_parts = gen_parts;
+  } else if (dense) {
+    r.gx = r.gw = CIMQ_ROUTE_DENSE;
+    r.lsq_fused = raw && dense_lsq_parts(g) > 0;
+    if (r.lsq_fused) r.act_parts = dense_lsq_parts(g);
+    r.nchunks_bwd = cdiv(g.M, dense_rows_per_chunk(g));
+  } else {
+    r.gx = r.gw = CIMQ_ROUTE_GENERAL;
+    r.nchunks_bwd = nchunks;
+  }
+  r.nchunks_ws = std::max({nchunks, r.nchunks_bwd, r6_plan(g).ok ? g.B : 0});
+  r.shift_stats = v7b && g.variant != VAR_LIBRARY;
+  // the forward writes the format its kernel family has; the compact ones where the v7 plan holds
+  const StateFmt fam = dense                 ? ST_DENSE
+                     : !v7_plan(g).ok        ? ST_PERK
+                     : r.gx == CIMQ_ROUTE_C1 ? ST_C1
+                     : g.NBP == 8            ? ST_PLANES
+                                             : ST_V7;
+  r.state = r.gx == CIMQ_ROUTE_R6 ? ST_NONE : fam;
+  r.cst = fam == ST_V7 ? g.nbw : fam == ST_PLANES ? 8 : fam == ST_C1 ? 9 : 0;
+  // (the region holds any format of the shape: the v7 words are never larger than the per-k ones for nbw >= 2,
+  // the max covers nbw == 1)
+  r.st_bytes = r.state == ST_NONE ? (size_t)0
+                                  : std::max({(size_t)g.T * g.nbw * g.M * g.O * (g.NBP == 4 ? 2 : 4),
+                                              (size_t)g.T * g.M * g.O * (g.NBP == 4 ? 4 : 24),
+                                              dense ? (size_t)g.T * g.M * g.O * 8 : (size_t)0});
+  // ctx codes: the forward is cim_fwd5_kernel (it quantises the activation itself) and grad_w is
+  // cim_bwd_gw5_kernel, the ctx's only reader
+  r.codes = r.fwd == CIMQ_ROUTE_FWD5 && r.gw == CIMQ_ROUTE_GW5;
+  r.wgx = !v7b;  // the general / dense grad_x operand
+  r.wcy = v7b;   // the v8 grad_x operand (cim_bwd_gx_v8_kernel, the fused and first-conv kernels)
+  r.wg5 = x5_plan(g).ok;
+  r.wx6 = r6_plan(g).ok;
+  if (g.inference) {
+    // forward only: no backward, no state; the forward keeps its family's instance without the words.  (The
+    // chunk and partial counts stay those of the training form; nothing reads them.)
+    r.gx = r.gw = CIMQ_ROUTE_NONE;
+    r.state = ST_NONE;
+    r.st_bytes = 0;
+    if (r.cst == 2 || r.cst == 3 || r.cst == 8) r.cst += 10;
+    r.codes = r.lsq_fused = r.gw_own = r.gxw5 = r.wgx = r.wcy = r.wg5 = r.wx6 = false;
+  }
+  return r;
+}
+inline Route route_of(const Geo& g) { return memo_geo<Route, route_compute>(g); }
+
+// the module entry points' form of a geometry: NCHW output where the fast forward runs, fixed before anything
+// is asked of it ([B, P, O] through the workspace for the dense and general forwards)
+inline Geo module_form(Geo g) {
+  g.onchw = v3_plan(g).ok ? 1 : 0;
+  return g;
+}
+
+// ctx: the weight-side regions first ([0, wbytes): weight operand fragments, ADC / STE
+// parameters, the module's step sizes -- functions of the parameters only, so a prepared
+// buffer (cimq_module_prepare, cimq_lsq_desc.wprep) can hold them instead), then the
+// activation-side regions (slice words, state words) of one forward.
+struct CtxLayout {
+  size_t xcode, xhat, alut, wfrag, wf5, wg5, wx6, wgx, wcy, thi, tlo, mlo, mhi, coef, alpha, beta, bsum, ckj, flags, st;
+  size_t lsq_scal;  // module entry points: sa, sw, alpha scale, max, min
+  size_t wbytes;    // end of the weight-side regions
+  size_t total;
+};
+
+inline CtxLayout ctx_layout_compute(const Geo& g) {
+  CtxLayout L;
+  const Route r = route_of(g);
+  size_t o = 0;
+  const size_t npar = (size_t)g.T * g.nba * g.nbw * g.Opad;
+  L.wfrag = o; o = align256(o + (size_t)g.T * g.KS * g.NBLK * 64 * 16);
+  L.wf5 = o; o = align256(o + f5_frag_bytes(g));  // cim_fwd5_kernel's weight operand
+  L.wg5 = o; o = align256(o + x5_frag_bytes(g));  // cim_bwd_gx5_kernel's weight operand
+  L.wx6 = o; o = align256(o + r6_frag_bytes(g));  // cim_bwd_r6_kernel's gx operand
+  L.wgx = o; o = align256(o + (size_t)g.T * g.FBT * g.NKS * 64 * 16);
+  L.wcy = o; o = align256(o + (size_t)g.T * 12 * g.NKS * 64 * 16);  // v8 grad_x operand (<= 12 blocks / tile)
+  L.thi = o; o = align256(o + npar * 4);
+  L.tlo = o; o = align256(o + npar * 4);
+  L.mlo = o; o = align256(o + npar * 4);
+  L.mhi = o; o = align256(o + npar * 4);
+  L.coef = o; o = align256(o + npar * 4);
+  L.alpha = o; o = align256(o + npar * 4);
+  L.beta = o; o = align256(o + npar * 4);
+  L.bsum = o; o = align256(o + (size_t)g.Opad * 4);
+  L.ckj = o; o = align256(o + 3 * 64 * 4);
+  L.flags = o; o = align256(o + 16);
+  L.lsq_scal = o; o = align256(o + 16 * 4);
+  L.wbytes = o;
+  // forward slice bytes (none in a forward-only call whose forward quantises the activation itself)
+  L.xcode = o; o = align256(o + ((g.inference && r.actq) ? (size_t)0 : (size_t)g.Nin * g.NBP));
+  if (g.inference) {
+    // forward only (CIMQ_OPT_INFERENCE): the ctx ends here -- no backward slice words, no code table, no state;
+    // their offsets point at the end and nothing is written through them
+    L.xhat = L.alut = L.st = L.total = o;
+    return L;
+  }
+  L.xhat = o; o = align256(o + (size_t)g.Nin * g.NBP);   // backward (int8 ctx) slice bytes
+  L.alut = o; o = align256(o + (size_t)4 * 301);         // ctx codes: code -> ctx word (Route::codes), format word 300
+  // the state words (Route::state); the region is last, so the module path's smaller ctx where its backward
+  // recomputes them -- cimq_sizes.module_ctx_bytes -- keeps every other offset
+  L.st = o; o = align256(o + r.st_bytes);
+  L.total = o;
+  return L;
+}
+inline CtxLayout ctx_layout(const Geo& g) { return memo_geo<CtxLayout, ctx_layout_compute>(g); }
+
+// base of the weight-side regions of a ctx: the prepared buffer when the call has one
+inline uint8_t* wreg(const Geo& g, const uint8_t* ctx) {
+  return const_cast<uint8_t*>(g.wbase ? g.wbase : ctx);
+}
+
+inline Params params_of(const Geo& g, uint8_t* ctx) {
+  CtxLayout L = ctx_layout(g);
+  uint8_t* base = wreg(g, ctx);
+  Params p;
+  p.thi = reinterpret_cast<int*>(base + L.thi);
+  p.tlo = reinterpret_cast<int*>(base + L.tlo);
+  p.mlo = reinterpret_cast<int*>(base + L.mlo);
+  p.mhi = reinterpret_cast<int*>(base + L.mhi);
+  p.coef = reinterpret_cast<float*>(base + L.coef);
+  p.alpha = reinterpret_cast<float*>(base + L.alpha);
+  p.beta = reinterpret_cast<float*>(base + L.beta);
+  p.bsum = reinterpret_cast<float*>(base + L.bsum);
+  p.ckj = reinterpret_cast<float*>(base + L.ckj);
+  p.flags = reinterpret_cast<int*>(base + L.flags);
+  return p;
 }
 
 struct WsLayout {
@@ -991,17 +1051,11 @@ inline int shift_chunks(const Geo& g) {
 inline WsLayout ws_layout_compute(const Geo& g) {
   WsLayout W;
   gw_chunks(g, &W.rows, &W.nchunks);
-  // backward slabs: the v7 grad_w kernel's pixel chunks when it applies (the alpha_cim init
-  // kernel keeps gw_chunks' split: W.nchunks / W.rows)
-  // (the one-kernel backwards: one chunk per image; the v7 plan also covers shift-ADC layers that the
-  // statistics kernel does not take -- those run the general backward)
-  const Plan7 p7 = v7_plan(g);
-  const bool v7b = v7_bwd(g);
-  const PlanG5 pg5 = g5_plan(g);
-  W.nchunks_bwd = (v9_plan(g).ok || c1_plan(g).ok || r6_bwd(g)) ? g.B : pg5.ok ? pg5.v.nchunks : v7b ? p7.v.nchunks
-                : dense_plan(g) ? cdiv(g.M, dense_rows_per_chunk(g)) : W.nchunks;
-  // (sizes for either backward of a layer: the module path's recompute backward has one chunk per image)
-  const size_t nch = (size_t)std::max({W.nchunks, W.nchunks_bwd, r6_plan(g).ok ? g.B : 0});
+  // backward slabs: the grad_w kernel's pixel chunks (the alpha_cim init kernel keeps gw_chunks' split:
+  // W.nchunks / W.rows)
+  const Route r = route_of(g);
+  W.nchunks_bwd = r.nchunks_bwd;
+  const size_t nch = (size_t)r.nchunks_ws;
   size_t o = 0;
   if (g.inference) {
     // forward only (CIMQ_OPT_INFERENCE): the prologue's alpha_cim max / min partials (lsq_part), and the
@@ -1009,7 +1063,7 @@ inline WsLayout ws_layout_compute(const Geo& g) {
     W.gw_slab = W.ga_slab = W.gb_slab = W.ss_slab = W.qtab = 0;
     W.lsq_part = o; o = align256(o + sizeof(float) * std::max(kLsqParts, g.B * g.H));
     W.gaq = W.gapart = W.wpart = o;
-    W.bpo = o; o = align256(o + ((v3_plan(g).ok || dense_plan(g)) ? (size_t)0 : sizeof(float) * (size_t)g.M * g.O));
+    W.bpo = o; o = align256(o + (r.fwd != CIMQ_ROUTE_GENERAL ? (size_t)0 : sizeof(float) * (size_t)g.M * g.O));
     W.gxu = W.total = o;
     return W;
   }
@@ -1017,10 +1071,9 @@ inline WsLayout ws_layout_compute(const Geo& g) {
   W.ga_slab = o; o = align256(o + sizeof(float) * nch * g.T * g.nbw * g.nba * g.Opad);
   W.gb_slab = o; o = align256(o + (g.variant == VAR_SHIFT_ROUND || g.variant == VAR_SHIFT_SIGN
                                        ? sizeof(float) * nch * g.T * g.nbw * g.nba * g.Opad : 0));
-  // shift ADC on the fast path: per pixel chunk, tile, pair and channel the grad_alpha / grad_beta partials
   // shift ADC statistics (v7 shapes, shift_stats_ok): per pixel chunk, tile, pair and channel the
   // grad_alpha / grad_beta partials, and the q tables [T][OB16][nbw * nba][16][2R + 1] when they fit
-  const bool stats = p7.ok && shift_stats_ok(g);
+  const bool stats = r.shift_stats;
   W.ss_slab = o; o = align256(o + (stats ? sizeof(float) * shift_chunks(g) * g.T * 2 * g.nbw * g.nba * g.Opad : 0));
   W.qtab = o; o = align256(o + ((stats && shift_table_fits(g)) ? sizeof(float) * (size_t)g.T * g.OB16 * g.nbw * g.nba *
                                                                     16 * (2 * shift_table_range(g) + 1)
@@ -1033,11 +1086,35 @@ inline WsLayout ws_layout_compute(const Geo& g) {
   W.wpart = o; o = align256(o + sizeof(float) * 2 * (size_t)cdiv((long long)g.T * g.FBT * 16 * g.Opad, 64));
   W.bpo = o; o = align256(o + sizeof(float) * (size_t)g.M * g.O);
   // the general backward's unfolded grad_x [M][K] (folded by fold_gx_kernel)
-  W.gxu = o; o = align256(o + ((v7b || dense_plan(g)) ? 0 : sizeof(float) * (size_t)g.M * g.K));
+  W.gxu = o; o = align256(o + (r.gx != CIMQ_ROUTE_GENERAL ? 0 : sizeof(float) * (size_t)g.M * g.K));
   W.total = o;
   return W;
 }
 inline WsLayout ws_layout(const Geo& g) { return memo_geo<WsLayout, ws_layout_compute>(g); }
+
+// What the Function form (flag off: cimq_query_sizes' ctx_bytes and workspace sizes, a caller's buffers) and the
+// module form (flag on) of one descriptor must share: every weight-side ctx offset, so every prepared buffer; every
+// activation-side offset, only the ctx's end may come earlier on the module path (no state words where its
+// backward recomputes them); every workspace offset and the workspace size; the operands the prologue builds.
+inline bool routes_agree(const Geo& g) {
+  Geo g0 = g, g1 = g;
+  g0.onchw = 0;
+  g1.onchw = 1;
+  const Route r0 = route_of(g0), r1 = route_of(g1);
+  const CtxLayout a = ctx_layout(g0), c = ctx_layout(g1);
+  const WsLayout w0 = ws_layout(g0), w1 = ws_layout(g1);
+  const size_t ca[] = {a.wfrag, a.wf5, a.wg5, a.wx6, a.wgx, a.wcy, a.thi, a.tlo, a.mlo, a.mhi, a.coef, a.alpha, a.beta,
+                       a.bsum, a.ckj, a.flags, a.lsq_scal, a.wbytes, a.xcode, a.xhat, a.alut, a.st};
+  const size_t cc[] = {c.wfrag, c.wf5, c.wg5, c.wx6, c.wgx, c.wcy, c.thi, c.tlo, c.mlo, c.mhi, c.coef, c.alpha, c.beta,
+                       c.bsum, c.ckj, c.flags, c.lsq_scal, c.wbytes, c.xcode, c.xhat, c.alut, c.st};
+  const size_t wa[] = {w0.gw_slab, w0.ga_slab, w0.gb_slab, w0.ss_slab, w0.qtab, w0.lsq_part, w0.gaq, w0.gapart, w0.wpart,
+                       w0.bpo, w0.gxu, w0.total};
+  const size_t wc[] = {w1.gw_slab, w1.ga_slab, w1.gb_slab, w1.ss_slab, w1.qtab, w1.lsq_part, w1.gaq, w1.gapart, w1.wpart,
+                       w1.bpo, w1.gxu, w1.total};
+  return std::equal(std::begin(ca), std::end(ca), cc) && c.total <= a.total &&
+         std::equal(std::begin(wa), std::end(wa), wc) && (r1.state == r0.state || r1.state == ST_NONE) &&
+         r0.wgx == r1.wgx && r0.wcy == r1.wcy && r0.wg5 == r1.wg5 && r0.wx6 == r1.wx6;
+}
 
 template <typename K>
 inline int set_lds(K kernel, size_t bytes) {
@@ -1170,25 +1247,24 @@ int launch_dense_bwd(const Geo& g, const uint8_t* ctx, const float* sw, const fl
                      const float* x = nullptr, const float* sa = nullptr);
 // cimq_part_bwd.hip: backward of layers outside the v7 / dense plans (the general kernels)
 int launch_bwd_general(const Geo& g, const uint8_t* ctx, const float* sw, const float* sa, const float* signed_act,
-                       const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, bool* lsq_fused);
+                       const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s);
 // cimq_part_bwd.hip: per-chunk sums of |ps * sw * sa| for the alpha_cim initialisation
 int launch_alpha_init_sums(const Geo& g, const uint8_t* ctx, const float* sw, const float* sa,
                            const float* signed_act, uint8_t* ws, hipStream_t s);
-// cimq_part_v7.hip: the v7 backward (grad_x v8 + grad_w v7) for one slice-pair shape
+// cimq_part_v7.hip: the v7 pair (grad_x v8 or gx5, grad_w v7 or gw5, as the Route says) for one slice-pair shape;
+// parts: bit 0 grad_x, bit 1 grad_w
 template <int NBW, int NBA>
 int launch_v7_n(const Geo& g, const Plan7& p, const uint8_t* ctx, const float* sw, const float* sa,
-                const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, bool lsq,
-                int parts);
+                const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, int parts);
 #define CIMQ_V7_SIG(NBW, NBA)                                                                              \
   int launch_v7_n<NBW, NBA>(const Geo& g, const Plan7& p, const uint8_t* ctx, const float* sw, const float* sa, \
-                            const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, bool lsq, \
-                            int parts)
+                            const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, int parts)
 // cimq_part_fused.hip: the fused backward (v9_plan)
 int launch_fused(const Geo& g, const Plan9& p, const uint8_t* ctx, const float* sw, const float* sa, const float* gout,
                  const float* x, float* gx, uint8_t* ws, hipStream_t s, bool lsq);
 int launch_c1(const Geo& g, const PlanC1& p, const uint8_t* ctx, const float* sw, const float* sa, const float* gout,
               const float* x, float* gx, uint8_t* ws, hipStream_t s, bool lsq);
-// cimq_part_r6.hip: the recompute backward (r6_bwd); dbg: the parity hook's state words into st_dbg instead
+// cimq_part_r6.hip: the recompute backward (CIMQ_ROUTE_R6); dbg: the parity hook's state words into st_dbg instead
 int launch_r6(const Geo& g, const PlanR6& p, const uint8_t* ctx, const float* sw, const float* sa, const float* sgn,
               const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, uint32_t* st_dbg = nullptr);
 extern template CIMQ_V7_SIG(2, 2);

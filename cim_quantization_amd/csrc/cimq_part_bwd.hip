@@ -53,9 +53,8 @@ int launch_gx(const Geo& g, const uint8_t* ctx, const float* sw, const float* sa
 template <int NBP, int FBMAX>
 int launch_bwd_all(const Geo& g, const uint8_t* ctx, const float* sw, const float* sa,
                    const float* signed_act, const float* gout, const float* x, float* gx, uint8_t* ws,
-                   hipStream_t s, bool* lsq_fused) {
+                   hipStream_t s) {
   (void)x;
-  *lsq_fused = false;
   CIMQ_TRY((launch_gx<NBP, FBMAX>(g, ctx, sw, sa, gout, gx, ws, s)));
   CIMQ_TRY((launch_gw<NBP, FBMAX, false>(g, ctx, sw, sa, signed_act, gout, ws, s)));
   return CIMQ_OK;
@@ -63,9 +62,9 @@ int launch_bwd_all(const Geo& g, const uint8_t* ctx, const float* sw, const floa
 
 template <int NBP>
 int dispatch_bwd(const Geo& g, const uint8_t* ctx, const float* sw, const float* sa, const float* signed_act,
-                 const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, bool* lsq_fused) {
-  if (g.FBT <= 4) return launch_bwd_all<NBP, 4>(g, ctx, sw, sa, signed_act, gout, x, gx, ws, s, lsq_fused);
-  return launch_bwd_all<NBP, 8>(g, ctx, sw, sa, signed_act, gout, x, gx, ws, s, lsq_fused);
+                 const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s) {
+  if (g.FBT <= 4) return launch_bwd_all<NBP, 4>(g, ctx, sw, sa, signed_act, gout, x, gx, ws, s);
+  return launch_bwd_all<NBP, 8>(g, ctx, sw, sa, signed_act, gout, x, gx, ws, s);
 }
 
 template <int NBP>
@@ -77,9 +76,9 @@ int dispatch_init(const Geo& g, const uint8_t* ctx, const float* sw, const float
 
 
 int launch_bwd_general(const Geo& g, const uint8_t* ctx, const float* sw, const float* sa, const float* signed_act,
-                       const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, bool* lsq_fused) {
-  if (g.NBP == 4) return dispatch_bwd<4>(g, ctx, sw, sa, signed_act, gout, x, gx, ws, s, lsq_fused);
-  return dispatch_bwd<8>(g, ctx, sw, sa, signed_act, gout, x, gx, ws, s, lsq_fused);
+                       const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s) {
+  if (g.NBP == 4) return dispatch_bwd<4>(g, ctx, sw, sa, signed_act, gout, x, gx, ws, s);
+  return dispatch_bwd<8>(g, ctx, sw, sa, signed_act, gout, x, gx, ws, s);
 }
 
 int launch_alpha_init_sums(const Geo& g, const uint8_t* ctx, const float* sw, const float* sa,

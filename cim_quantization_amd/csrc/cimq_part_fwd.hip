@@ -10,38 +10,29 @@ template <int NBP, int KS>
 int launch_fwd_v3(const Geo& g, const Plan3& p, uint8_t* ctx, const float* sw, const float* sa, float* out,
                   hipStream_t s, const ActQ* aq) {
   CtxLayout L = ctx_layout(g);
-  // compact state words when the v7 backward will read them
-  const bool cst = v7_plan(g).ok;
+  // CST, fixed at compile time: 0 per-k state words (the general backward's), else the compact ones the v7-plan
+  // backwards read -- nbw = nba = CST (2, 3), 8 the w8a8 planes, 9 the first conv, whose backward recomputes
+  // them; forward only (CIMQ_OPT_INFERENCE): the same instances without the state words, their bits and the
+  // backward words (10 + CST; 0 and 9 write no state as they are)
+  const int cst = route_of(g).cst;
   // OBM: 16-channel output blocks per block (register arrays sized for exactly that)
   const int obm = std::min(p.v.obm, g.OB16 <= 2 ? g.OB16 : 4);
-  // CST: compact state words with nbw = nba = CST fixed at compile time (v7_plan's slice pairs)
   void (*kern)(Geo, V3, const uint8_t*, const v4i*, Params, const float*, const float*, float*, uint8_t*,
                const float*, const float*, uint8_t*);
-  if (cst && g.inference) {
-    // forward only (CIMQ_OPT_INFERENCE): the same instances without the state words, their bits and the
-    // backward words (CSTA 10 + CST); the CST 0 instances below write no state as they are
-    if constexpr (NBP == 8) {
-      kern = c1_plan(g).ok ? cim_fwd_v3_kernel<8, KS, 9, 1> : cim_fwd_v3_kernel<8, KS, 18, 1>;
-    } else if (g.nbw == 2) {
-      kern = obm == 1 ? cim_fwd_v3_kernel<NBP, KS, 12, 1> : obm == 2 ? cim_fwd_v3_kernel<NBP, KS, 12, 2>
-                                                         : cim_fwd_v3_kernel<NBP, KS, 12, 4>;
-    } else {
-      kern = obm == 1 ? cim_fwd_v3_kernel<NBP, KS, 13, 1> : obm == 2 ? cim_fwd_v3_kernel<NBP, KS, 13, 2>
-                                                         : cim_fwd_v3_kernel<NBP, KS, 13, 4>;
-    }
-  } else if (!cst) {
-    kern = obm == 1 ? cim_fwd_v3_kernel<NBP, KS, 0, 1> : obm == 2 ? cim_fwd_v3_kernel<NBP, KS, 0, 2>
-                                                       : cim_fwd_v3_kernel<NBP, KS, 0, 4>;
-  } else if constexpr (NBP == 8) {
-    // v7_plan: w8a8 with one 16-channel block; the first conv's backward (c1_plan) recomputes the state
-    kern = c1_plan(g).ok ? cim_fwd_v3_kernel<8, KS, 9, 1> : cim_fwd_v3_kernel<8, KS, 8, 1>;
-  } else if (g.nbw == 2) {
-    kern = obm == 1 ? cim_fwd_v3_kernel<NBP, KS, 2, 1> : obm == 2 ? cim_fwd_v3_kernel<NBP, KS, 2, 2>
-                                                       : cim_fwd_v3_kernel<NBP, KS, 2, 4>;
+#define CIMQ_FWD3(CST) (obm == 1 ? cim_fwd_v3_kernel<NBP, KS, CST, 1> : obm == 2 ? cim_fwd_v3_kernel<NBP, KS, CST, 2> \
+                                                                     : cim_fwd_v3_kernel<NBP, KS, CST, 4>)
+  // (the instances in the order the code object has always had them: a kernel's place decides its addresses)
+  if (cst != 0 && g.inference) {
+    if constexpr (NBP == 8) kern = cst == 9 ? cim_fwd_v3_kernel<8, KS, 9, 1> : cim_fwd_v3_kernel<8, KS, 18, 1>;
+    else kern = cst == 12 ? CIMQ_FWD3(12) : CIMQ_FWD3(13);
+  } else if (cst == 0) {
+    kern = CIMQ_FWD3(0);
+  } else if constexpr (NBP == 8) {  // v7_plan: w8a8 with one 16-channel block
+    kern = cst == 9 ? cim_fwd_v3_kernel<8, KS, 9, 1> : cim_fwd_v3_kernel<8, KS, 8, 1>;
   } else {
-    kern = obm == 1 ? cim_fwd_v3_kernel<NBP, KS, 3, 1> : obm == 2 ? cim_fwd_v3_kernel<NBP, KS, 3, 2>
-                                                       : cim_fwd_v3_kernel<NBP, KS, 3, 4>;
+    kern = cst == 2 ? CIMQ_FWD3(2) : CIMQ_FWD3(3);
   }
+#undef CIMQ_FWD3
   // the fused activation quantiser's word table (after the kernel's other LDS)
   const size_t lds = p.lds_fwd + (aq ? (size_t)kActLutMax * 2 * 4 : 0);
   CIMQ_TRY(set_lds(kern, lds));
@@ -62,11 +53,8 @@ int launch_fwd(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, flo
   CtxLayout L = ctx_layout(g);
   const Plan3 p = v3_plan(g);
   if (p.ok && !DBG) {
-    if (aq) {
-      const Plan5 p5 = f5_plan(g);
-      // (cim_fwd5_kernel writes NCHW only: a forward-only Function call, [B, P, O], stays on cim_fwd_v3_kernel)
-      if (p5.ok && g.onchw) return launch_fwd5(g, p5, ctx, sw, sa, out, s, aq);
-    }
+    // (cim_fwd5_kernel writes NCHW only: a forward-only Function call, [B, P, O], stays on cim_fwd_v3_kernel)
+    if (aq && route_of(g).fwd == CIMQ_ROUTE_FWD5) return launch_fwd5(g, f5_plan(g), ctx, sw, sa, out, s, aq);
     if (g.KS == 1) return launch_fwd_v3<NBP, 1>(g, p, ctx, sw, sa, out, s, aq);
     return launch_fwd_v3<NBP, 2>(g, p, ctx, sw, sa, out, s, aq);
   }
@@ -91,8 +79,9 @@ int launch_fwd(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, flo
 
 int launch_fwd_any(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, int* ps_dbg,
                    float* adc_dbg, hipStream_t s, const ActQ* aq) {
-  if (aq && (!fwd_actq_ok(g) || ps_dbg)) return fail(CIMQ_EINVAL, "internal: fused activation quantiser off its plan");
-  if (dense_plan(g)) {
+  const Route r = route_of(g);
+  if (aq && (!r.actq || ps_dbg)) return fail(CIMQ_EINVAL, "internal: fused activation quantiser off its plan");
+  if (r.fwd == CIMQ_ROUTE_DENSE) {
     // the dense GEMM path (its state words feed the dense backward); the debug hook then reruns
     // the general kernel for the partial sums (same out values)
     CIMQ_TRY(launch_dense_fwd(g, ctx, sw, sa, out, s));

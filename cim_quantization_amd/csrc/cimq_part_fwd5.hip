@@ -9,9 +9,10 @@ int launch_fwd5(const Geo& g, const Plan5& p, uint8_t* ctx, const float* sw, con
                 hipStream_t s, const ActQ* aq) {
   if (!p.ok || !aq || !g.onchw) return fail(CIMQ_EINVAL, "internal: cim_fwd5 off its plan");
   CtxLayout L = ctx_layout(g);
+  const Route r = route_of(g);
   // the state words and ctx only where the backward reads them (not where cim_bwd_r6_kernel recomputes, and
   // not in a forward-only call, CIMQ_OPT_INFERENCE)
-  const bool wst = !r6_bwd(g) && !g.inference;
+  const bool wst = r.state != ST_NONE;
   auto kern = p.nob == 2 ? (wst ? cim_fwd5_kernel<2, true> : cim_fwd5_kernel<2, false>)
                          : (wst ? cim_fwd5_kernel<1, true> : cim_fwd5_kernel<1, false>);
   CIMQ_TRY(set_lds(kern, p.lds));
@@ -22,7 +23,7 @@ int launch_fwd5(const Geo& g, const Plan5& p, uint8_t* ctx, const float* sw, con
   dim3 grid(std::min(p.v.nmt, per_ob), ny);
   const int slot = prof_begin(KID_FWD_V7, g, s);
   F5 v = p.v;
-  v.codes = ctx_codes(g) ? 1 : 0;  // one code byte per ctx element (grad_w is cim_bwd_gw5_kernel)
+  v.codes = r.codes ? 1 : 0;  // one code byte per ctx element (grad_w is cim_bwd_gw5_kernel)
   hipLaunchKernelGGL(kern, grid, dim3(512 * p.nob), p.lds, s, g, v, reinterpret_cast<const v4i*>(wreg(g, ctx) + L.wf5),
                      params_of(g, ctx), sw, sa, aq->x, aq->signed_act, out,
                      reinterpret_cast<uint32_t*>(ctx + L.st), reinterpret_cast<uint32_t*>(ctx + L.xhat),

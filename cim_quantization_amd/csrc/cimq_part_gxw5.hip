@@ -40,7 +40,7 @@ int launch_gw5(const Geo& g, const PlanG5& p, const uint8_t* ctx, const float* g
   WsLayout W = ws_layout(g);
   if (W.nchunks_bwd != p.v.nchunks) return fail(CIMQ_EINVAL, "internal: cim_bwd_gw5 slab count mismatch");
   G5 v = p.v;
-  v.codes = ctx_codes(g) ? 1 : 0;  // the forward wrote code bytes (cim_fwd5_kernel on the module path)
+  v.codes = route_of(g).codes ? 1 : 0;  // the forward wrote code bytes (cim_fwd5_kernel on the module path)
   // the row-block split compiled in: 16 input channels (every block in input-channel block 0) and 32 (blocks 0 / 1)
   const int sp = !tune("GW5_SP8", 1) ? 0 : g.C == 16 ? 8 : (g.C == 32 && tune("GW5_SP78", 1)) ? 78 : 0;
 #define CIMQ_GW5_K(SS_, C_) (sp == 8 ? cim_bwd_gw5_kernel<SS_, C_, 8> : sp == 78 ? cim_bwd_gw5_kernel<SS_, C_, 78> \
@@ -81,7 +81,7 @@ int launch_gxw5(const Geo& g, const PlanX5& px, const PlanG5& pw, const uint8_t*
   WsLayout W = ws_layout(g);
   if (W.nchunks_bwd != pw.v.nchunks) return fail(CIMQ_EINVAL, "internal: cim_bwd_gxw5 slab count mismatch");
   G5 vw = pw.v;
-  vw.codes = ctx_codes(g) ? 1 : 0;  // the forward wrote code bytes (cim_fwd5_kernel on the module path)
+  vw.codes = route_of(g).codes ? 1 : 0;  // the forward wrote code bytes (cim_fwd5_kernel on the module path)
   // x5_plan: C = 16 -> one 16-channel input block (gw5's row-block split at 8), C = 32 -> two (splits 8 and 7)
   auto kern = px.v.CBN == 1 ? (vw.codes ? cim_bwd_gxw5_kernel<1, true, 8> : cim_bwd_gxw5_kernel<1, false, 8>)
                             : (vw.codes ? cim_bwd_gxw5_kernel<2, true, 78> : cim_bwd_gxw5_kernel<2, false, 78>);

@@ -1,5 +1,6 @@
 // cimq_part_v7.hip -- launch sequence of the v7 backward (cim_bwd_gx_v8_kernel + cim_bwd_gw_v7_kernel,
-// cimq_v7.hip) as a template over the slice-pair shape, instantiated for w2a2, w3a3 and w8a8 layers.
+// cimq_v7.hip) as a template over the slice-pair shape, instantiated for w2a2, w3a3 and w8a8 layers; gx5 / gw5
+// (cimq_part_gxw5.hip) take either role where the Route says so.
 // parts: bit 0 the grad_x kernel, bit 1 the grad_w kernel (CIMQ_LSQ_DEFER_GW launches them apart,
 // grad_w on the caller's second stream).  Own translation unit of libcimq.so.
 #include "cimq_host.h"
@@ -9,19 +10,17 @@ namespace cimq {
 
 template <int NBW, int NBA, int OBX>
 int launch_v7_nb(const Geo& g, const Plan7& p, const uint8_t* ctx, const float* sw, const float* sa,
-                 const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, bool lsq,
-                 int parts) {
+                 const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, int parts) {
   CtxLayout L = ctx_layout(g);
   WsLayout W = ws_layout(g);
+  const Route r = route_of(g);
+  const bool lsq = r.lsq_fused;
   Params pp = params_of(g, const_cast<uint8_t*>(ctx));
   const uint32_t* st = reinterpret_cast<const uint32_t*>(ctx + L.st);
-  const PlanX5 px5 = x5_plan(g);
-  if ((parts & 3) == 3 && px5.ok && lsq && g.SH == 1 && tune("GXW5", 1)) {
-    const PlanG5 pg5 = g5_plan(g);
-    if (pg5.ok) return launch_gxw5(g, px5, pg5, ctx, sw, sa, gout, x, gx, ws, s);  // both kernels, one grid
-  }
-  if ((parts & 1) && px5.ok && lsq) {
-    CIMQ_TRY(launch_gx5(g, px5, ctx, sw, sa, gout, x, gx, ws, s));
+  if ((parts & 3) == 3 && r.gxw5)  // both kernels, one grid
+    return launch_gxw5(g, x5_plan(g), g5_plan(g), ctx, sw, sa, gout, x, gx, ws, s);
+  if ((parts & 1) && r.gx == CIMQ_ROUTE_GX5) {
+    CIMQ_TRY(launch_gx5(g, x5_plan(g), ctx, sw, sa, gout, x, gx, ws, s));
   } else if (parts & 1) {
     const int np = p.v.NPART;
 #define CIMQ_GX8(L, S, N) cim_bwd_gx_v8_kernel<NBW, NBA, OBX, L, S, N>
@@ -42,8 +41,7 @@ int launch_v7_nb(const Geo& g, const Plan7& p, const uint8_t* ctx, const float* 
     CIMQ_TRY(check_hip("cim_bwd_gx_v8"));
   }
   if (parts & 2) {
-    const PlanG5 p5 = g5_plan(g);
-    if (p5.ok) return launch_gw5(g, p5, ctx, gout, ws, s);
+    if (r.gw == CIMQ_ROUTE_GW5) return launch_gw5(g, g5_plan(g), ctx, gout, ws, s);
     auto kern = g.SH == 1 ? cim_bwd_gw_v7_kernel<NBW, NBA, 1> : cim_bwd_gw_v7_kernel<NBW, NBA, 2>;
     CIMQ_TRY(set_lds(kern, p.lds_gw));
     const int slot = prof_begin(KID_GW_V7, g, s);
@@ -57,14 +55,13 @@ int launch_v7_nb(const Geo& g, const Plan7& p, const uint8_t* ctx, const float* 
 
 template <int NBW, int NBA>
 int launch_v7_n(const Geo& g, const Plan7& p, const uint8_t* ctx, const float* sw, const float* sa,
-                const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, bool lsq,
-                int parts) {
+                const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, int parts) {
   if constexpr (NBW * NBA > 10) {
-    return launch_v7_nb<NBW, NBA, 1>(g, p, ctx, sw, sa, gout, x, gx, ws, s, lsq, parts);  // v7_plan: OB16 == 1
+    return launch_v7_nb<NBW, NBA, 1>(g, p, ctx, sw, sa, gout, x, gx, ws, s, parts);  // v7_plan: OB16 == 1
   } else {
-    if (g.OB16 == 1) return launch_v7_nb<NBW, NBA, 1>(g, p, ctx, sw, sa, gout, x, gx, ws, s, lsq, parts);
-    if (g.OB16 == 2) return launch_v7_nb<NBW, NBA, 2>(g, p, ctx, sw, sa, gout, x, gx, ws, s, lsq, parts);
-    return launch_v7_nb<NBW, NBA, 4>(g, p, ctx, sw, sa, gout, x, gx, ws, s, lsq, parts);
+    if (g.OB16 == 1) return launch_v7_nb<NBW, NBA, 1>(g, p, ctx, sw, sa, gout, x, gx, ws, s, parts);
+    if (g.OB16 == 2) return launch_v7_nb<NBW, NBA, 2>(g, p, ctx, sw, sa, gout, x, gx, ws, s, parts);
+    return launch_v7_nb<NBW, NBA, 4>(g, p, ctx, sw, sa, gout, x, gx, ws, s, parts);
   }
 }
 

@@ -156,7 +156,7 @@ constexpr int kF5MaxGrp = 4;  // tile groups
 struct F5 {
   int lwo;                 // log2(Wo)
   int lwi;                 // log2(W)
-  int codes;               // 1: the ctx holds one code byte per element (ctx_codes: grad_w is cim_bwd_gw5_kernel)
+  int codes;               // 1: the ctx holds one code byte per element (Route::codes: grad_w is cim_bwd_gw5_kernel)
   int IPM;                 // images per 128-pixel m-tile (1: the m-tile is R output rows of one image)
   int R, RH, WP;           // output rows per image slot, patch rows (R-1)*SH + 3, patch row length W + 2
   int NCBP;                // channel blocks one patch holds (the widest group's span)
@@ -195,7 +195,7 @@ struct G5 {
   int lwo;     // log2(Wo)
   int lwi;     // log2(W)
   int codes;   // 1: the ctx holds one activation code byte per element (the forward was cim_fwd5_kernel with
-               // ctx_codes): expanded through the act word table, as the forward's staging does
+               // Route::codes): expanded through the act word table, as the forward's staging does
   int IPM;     // images per 128-pixel m-tile (1: the m-tile is R output rows of one image)
   int R, RH, WP;  // output rows per image slot, staged input rows R + 2, patch row length W + 2
   int nmt;     // M / 128
@@ -249,7 +249,7 @@ static_assert(2 * kR6T * 9 * 8 * 16 * 4 <= 3 * R6L::GPL, "r6 grad_alpha reductio
 
 // The ctx's code -> word table region (CtxLayout::alut, 1,280 bytes) also carries a format word at entry
 // kCalFlag: cim_fwd5_kernel writes kCodesMagic there when it stores one activation code byte per ctx element
-// (ctx_codes), and cim_bwd_gw5_kernel's code-byte instance checks it -- a ctx written in the other format
+// (Route::codes), and cim_bwd_gw5_kernel's code-byte instance checks it -- a ctx written in the other format
 // (a forward / backward planned differently, e.g. a tuning knob changed in between) yields NaN grad_w and
 // grad_alpha partials instead of silently reading words as codes.
 constexpr int kCalFlag = 300;

@@ -211,3 +211,57 @@ def test_chain_with_wide_alpha_dense_layers(cuda_device):
         assert torch.equal(a, b)
     _close(runs[1][1], runs[0][1])
     assert torch.isfinite(runs[1][1]).all()
+
+
+@pytest.mark.parametrize("recompute", [False, True])
+def test_skip_tail_then_backward_tail_equals_plain_backward(cuda_device, recompute):
+    """cimq_module_backward with CIMQ_LSQ_SKIP_TAIL followed by cimq_module_backward_tail, against the plain
+    cimq_module_backward on a second ctx / workspace: the same kernels in the same order, so grad_x and the four
+    parameter gradients agree bit for bit.  The smallest layer on the gx5 / gw5 route and, with
+    CIMQ_OPT_RECOMPUTE, on the r6 route (B = 2: the recompute backward leaves 2 slabs and 2 act-LSQ partials where
+    the state-word backward of the same shape leaves 16, so an epilogue planned for the other one reads slabs
+    nobody wrote)."""
+    import ctypes
+
+    import cim_quantization_amd._lib as L
+    import cim_quantization_amd._modules as my_nn
+    from cim_quantization_amd.functional import _CimModuleConv, _stream
+    dev = cuda_device
+    torch.manual_seed(11)
+    m = my_nn.Conv2dLSQCiM(16, 16, 3, 1, 1, bias=False, nbits_w=3, nbits_a=3, nbits_alpha=8, xbar=128, adcbits=1.5)
+    torch.nn.init.kaiming_normal_(m.weight)
+    m = m.to(dev).train()
+    gen = torch.Generator().manual_seed(12)
+    x = torch.randn(2, 16, 32, 32, generator=gen).relu().to(dev)
+    g = (torch.randn(2, 16, 32, 32, generator=gen) / 181.0).to(dev)
+    m(x)  # the initialising step: alpha_act, alpha_weight, alpha_cim
+    lib = L.load()
+
+    def run(split):
+        out, desc, lsq, sizes, (xc, wc, aa, aw, ac, bm, sg, cbuf), _ = _CimModuleConv._call(
+            x, m.weight, m.alpha_act, m.alpha_weight, m.alpha_cim, m.binary_mask, m.signed_act, m.stride, m.padding,
+            m.dilation, m.nbits_a, m.abitslice, m.nbits_w, m.wbitslice, m.adcbits, m.xbar, m.nbits_alpha,
+            recompute=recompute)
+        route = (ctypes.c_int * 3)()
+        L.check(lib.cimq_module_route(desc, route), "cimq_module_route")
+        assert tuple(L.ROUTE_NAMES[v] for v in route) == (("fwd5", "r6", "r6") if recompute else ("fwd5", "gx5", "gw5"))
+        ws = torch.empty(sizes.bwd_workspace_bytes, device=dev, dtype=torch.uint8)
+        gx, gw, gac = torch.empty_like(xc), torch.empty_like(wc), torch.empty_like(ac)
+        gaa, gaw = torch.empty(1, device=dev), torch.empty(1, device=dev)
+        q = L.make_lsq_desc(lsq.qn_w, lsq.qp_w, lsq.gscale_a, lsq.gscale_w, lsq.nbits_alpha,
+                            L.CIMQ_LSQ_SKIP_TAIL if split else 0)
+        L.check(lib.cimq_module_backward(desc, q, g.data_ptr(), xc.data_ptr(), wc.data_ptr(), aa.data_ptr(),
+                                         aw.data_ptr(), ac.data_ptr(), bm.data_ptr(), sg.data_ptr(), cbuf.data_ptr(),
+                                         gx.data_ptr(), gw.data_ptr(), gaa.data_ptr(), gaw.data_ptr(), gac.data_ptr(),
+                                         ws.data_ptr(), _stream()), "cimq_module_backward")
+        if split:
+            L.check(lib.cimq_module_backward_tail(desc, q, wc.data_ptr(), ac.data_ptr(), cbuf.data_ptr(), gw.data_ptr(),
+                                                  gaa.data_ptr(), gaw.data_ptr(), gac.data_ptr(), ws.data_ptr(),
+                                                  _stream()), "cimq_module_backward_tail")
+        torch.cuda.synchronize()
+        return gx, gw, gaa, gaw, gac
+
+    for name, a, b in zip(("grad_x", "grad_weight", "grad_alpha_act", "grad_alpha_weight", "grad_alpha_cim"),
+                          run(True), run(False)):
+        assert torch.isfinite(b).all() and b.abs().max() > 0, name
+        assert torch.equal(a, b), name

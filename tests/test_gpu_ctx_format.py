@@ -1,5 +1,5 @@
 """The ctx format word: where cim_fwd5_kernel stores one activation code byte per ctx element for
-cim_bwd_gw5_kernel (ctx_codes, the 16 / 32-channel w3a3 stride-1 module layers), it also writes kCodesMagic at
+cim_bwd_gw5_kernel (Route::codes, the 16 / 32-channel w3a3 stride-1 module layers), it also writes kCodesMagic at
 the code table's entry 300 (kCalFlag, csrc/cimq_types.h), and gw5 checks it.  A ctx whose format word is not the
 magic -- a forward and backward planned differently -- must give NaN parameter gradients, not gradients read
 from words taken as codes."""

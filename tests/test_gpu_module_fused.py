@@ -21,6 +21,8 @@ CASES = [
     dict(B=6, C=8, O=24, H=7, s=1, wb=4, ab=4, adc=4, xbar=64, bias=False),
     dict(B=5, C=16, O=16, H=12, s=1, wb=3, ab=3, adc=1, xbar=64, bias=False),
     dict(B=4, C=64, O=64, H=8, s=1, wb=3, ab=3, adc=1.5, xbar=128, bias=False),
+    # the fast forward (NCHW out) in front of the general backward ([B, P, O] grad_out): route v3 / general / general
+    dict(B=4, C=16, O=16, H=16, s=1, wb=4, ab=4, adc=4, xbar=64, bias=False),
 ]
 
 
