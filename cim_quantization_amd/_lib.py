@@ -13,7 +13,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CIMQ_LIB_PATH") or os.path.join(_HERE, "libcimq.so")
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 CIMQ_EINVAL = 1  # include/cimq.h error codes
 CIMQ_EUNSUPPORTED = 2
@@ -37,6 +37,7 @@ CIMQ_ADC_F_PS_INT8 = 0x100
 CIMQ_ADC_F_SHIFT_RANGE = 0x200
 CIMQ_OPT_RECOMPUTE = 1  # cimq_conv_desc.options (ABI 14)
 CIMQ_OPT_INFERENCE = 4  # forward only: nothing written that a backward would read (ABI 15; bit 2 is refused)
+CIMQ_EPI_RELU = 1  # cimq_epilogue.flags (ABI 16)
 
 # every symbol include/cimq.h declares
 EXPORTED_SYMBOLS = (
@@ -57,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "cimq_module_route",
     "cimq_module_shift_forward",
     "cimq_module_shift_backward",
+    "cimq_module_forward_epilogue",
     "cimq_alpha_init",
     "cimq_shift_forward",
     "cimq_shift_backward",
@@ -110,6 +112,13 @@ class LsqDesc(ctypes.Structure):
     _fields_ = [("qn_w", ctypes.c_float), ("qp_w", ctypes.c_float), ("gscale_a", ctypes.c_float),
                 ("gscale_w", ctypes.c_float), ("nbits_alpha", ctypes.c_int32), ("flags", ctypes.c_int32),
                 ("wprep", ctypes.c_void_p)]
+
+
+class Epilogue(ctypes.Structure):
+    """Mirror of ``cimq_epilogue`` (ABI 16)."""
+
+    _fields_ = [("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p), ("residual", ctypes.c_void_p),
+                ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
 class QConvDesc(ctypes.Structure):
@@ -194,6 +203,9 @@ def _bind(lib):
     lib.cimq_module_shift_forward.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(LsqDesc)] + [_VP] * 12
     lib.cimq_module_shift_backward.restype = ctypes.c_int
     lib.cimq_module_shift_backward.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(LsqDesc)] + [_VP] * 18
+    lib.cimq_module_forward_epilogue.restype = ctypes.c_int
+    lib.cimq_module_forward_epilogue.argtypes = ([ctypes.POINTER(ConvDesc), ctypes.POINTER(LsqDesc)] + [_VP] * 8 +
+                                                 [ctypes.POINTER(Epilogue)] + [_VP] * 4)
     lib.cimq_alpha_init.restype = ctypes.c_int
     lib.cimq_alpha_init.argtypes = [ctypes.POINTER(ConvDesc)] + [_VP] * 10
     lib.cimq_shift_forward.restype = ctypes.c_int
@@ -286,6 +298,15 @@ def make_lsq_desc(qn_w, qp_w, gscale_a, gscale_w, nbits_alpha, flags=0, wprep=No
     q.flags = int(flags)
     q.wprep = wprep
     return q
+
+
+def make_epilogue(scale, shift, residual=None, relu=False) -> Epilogue:
+    """``scale`` / ``shift`` / ``residual``: device addresses (``tensor.data_ptr()``), residual None for none."""
+    e = Epilogue()
+    e.scale, e.shift, e.residual = scale, shift, residual
+    e.flags = CIMQ_EPI_RELU if relu else 0
+    e.reserved = 0
+    return e
 
 
 def make_qconv_desc(B, C, H, W, O, KH, KW, stride, padding, dilation, groups, code_min, code_max,

@@ -18,7 +18,7 @@ import torch
 import torch.nn.functional as F
 
 from ..functional import (alpha_cim_init, cim_conv2d_lsq, cim_conv2d_lsq_shift, cim_module_conv,  # noqa: F401
-                          cim_module_shift_conv, get_adcless_cim_output, get_analog_partial_sums_autograd_ver2,
+                          cim_module_conv_epilogue, cim_module_shift_conv, get_adcless_cim_output, get_analog_partial_sums_autograd_ver2,
                           get_cim_output_signed, inference_call, inference_weights, lsq_quantize,
                           module_shift_supported, qconv2d)
 from ._quan_base import (_ActQ, _Conv2dQ, _Conv2dQCiM, _LinearQ, Qmodes, grad_scale,  # noqa: F401
@@ -196,6 +196,40 @@ class Conv2dLSQCiM(_Conv2dQCiM):
         if self.bias is not None:
             out = out + self.bias  # broadcasts over the last axis, as lsq.py:583
         return out
+
+    def fused_epilogue_ready(self, x):
+        """Whether ``forward_fused`` takes this layer for input ``x``: the steady-state library path (both
+        first-step initialisations done, a CiM ADC, ROCm tensors; the shift ADC where libcimq fuses it) and no
+        bias -- the reference's bias broadcasts over the last axis (lsq.py:583), so it is no per-channel term."""
+        flags = self._init_flags()
+        if not (self.fused and flags[0] and (flags[1] or self.alpha_cim is None) and self.adcbits != 0
+                and self.bias is None and torch.is_tensor(x) and x.is_cuda and self.weight.is_cuda):
+            return False
+        return self._shift_fused(x) if self.adc_shift else True
+
+    def forward_fused(self, x, scale, shift, residual=None, relu=False):
+        """Evaluation only: ``forward(x)`` with a per-channel affine (a folded BatchNorm: ``scale``, ``shift``,
+        [out_channels] fp32), an optional ``residual`` (the output's shape; made contiguous fp32 if it is not) and an
+        optional ReLU applied in the forward kernel's registers before the store -- bit for bit
+        ``relu(forward(x) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1) + residual)`` in that order of
+        operations (cim_module_conv_epilogue).  Uses the kept inference weight side exactly as ``forward`` does.
+        Raises where ``fused_epilogue_ready`` does not hold, or if the call could be differentiated."""
+        if not self.fused_epilogue_ready(x):
+            raise RuntimeError("Conv2dLSQCiM.forward_fused needs the steady-state library path (both first-step "
+                               "initialisations done, adcbits != 0, ROCm tensors) and bias=None")
+        if self.binary_mask.device != x.device:
+            self.binary_mask = self.binary_mask.to(x.device)
+        wprep = None
+        if not self.adc_shift:
+            self._last_x_shape = tuple(x.shape)
+            if not torch.is_grad_enabled() and not self.stochastic_quant:
+                wprep = self._inf_prep = inference_weights(self, x.shape, self._inf_prep)
+        return cim_module_conv_epilogue(
+            x, self.weight, self.alpha_act, self.alpha_weight, self.alpha_cim, self.binary_mask, self.signed_act,
+            self.stride, self.padding, self.dilation, self.nbits_a, self.abitslice, self.nbits_w, self.wbitslice,
+            self.adcbits, self.xbar, self.nbits_alpha, scale, shift, residual=residual, relu=relu,
+            beta_cim=self.beta_cim if self.adc_shift else None, stochastic=bool(self.stochastic_quant), wprep=wprep,
+            recompute=self.recompute_psum)
 
 
 class _HostFlags:

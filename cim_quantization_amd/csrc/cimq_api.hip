@@ -566,10 +566,19 @@ static int check_alpha(const Geo& g, LsqArgs* la, const float* alpha_cim, const 
 static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* x, const float* weight,
                                const float* alpha_act, const float* alpha_weight, const float* alpha_cim,
                                const float* beta_cim, const int8_t* binary_mask, const float* signed_act, float* out,
-                               void* ctx, void* ws, void* stream) {
+                               void* ctx, void* ws, void* stream, const Epi* ep = nullptr) {
   Geo g;
   LsqArgs la;
   CIMQ_TRY(module_geo(d, q, &g, &la, beta_cim != nullptr));
+  if (ep) {  // cimq_module_forward_epilogue: the residual has out's geometry
+    if (!g.inference) return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: a CIMQ_OPT_INFERENCE descriptor only");
+    if (ep->res && out) {
+      const uintptr_t r0 = reinterpret_cast<uintptr_t>(ep->res), o0 = reinterpret_cast<uintptr_t>(out);
+      const uintptr_t nb = (uintptr_t)g.M * g.O * 4;
+      if (r0 < o0 + nb && o0 < r0 + nb)
+        return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: residual overlaps out");
+    }
+  }
   if (!x || !weight || !alpha_act || !alpha_weight || !binary_mask || !signed_act || !out || !ctx || !ws)
     return fail(CIMQ_EINVAL, "null pointer argument");
   CIMQ_TRY(check_alpha(g, &la, alpha_cim, nullptr, false));
@@ -612,13 +621,14 @@ prepared:
   const ActQ aq{x, signed_act};
   // (the fast forward writes NCHW, g.onchw; the dense one's P = 1: NCHW is [B, P, O])
   if (r.fwd != CIMQ_ROUTE_GENERAL)
-    return launch_fwd_any(g, c, scal + 1, scal, out, nullptr, nullptr, s, r.actq ? &aq : nullptr);
+    return launch_fwd_any(g, c, scal + 1, scal, out, nullptr, nullptr, s, r.actq ? &aq : nullptr, ep);
   // general kernels write [B, P, O]; the module returns NCHW
   WsLayout W = ws_layout(g);
   float* bpo = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(ws) + W.bpo);
   CIMQ_TRY(launch_fwd_any(g, c, scal + 1, scal, bpo, nullptr, nullptr, s));
-  hipLaunchKernelGGL(bpo_to_nchw_kernel, dim3(std::min(cdiv((long long)g.M * g.O, 256), 8192)), dim3(256), 0, s,
-                     g, bpo, out);
+  const dim3 tgrid(std::min(cdiv((long long)g.M * g.O, 256), 8192));
+  if (ep) hipLaunchKernelGGL(bpo_to_nchw_epi_kernel, tgrid, dim3(256), 0, s, g, bpo, out, *ep);
+  else hipLaunchKernelGGL(bpo_to_nchw_kernel, tgrid, dim3(256), 0, s, g, bpo, out);
   return check_hip("bpo_to_nchw");
 }
 
@@ -657,6 +667,26 @@ int cimq_module_shift_forward(const cimq_conv_desc* d, const cimq_lsq_desc* q, c
   if (!beta_cim || !alpha_cim) return fail(CIMQ_EINVAL, "cimq_module_shift_forward needs alpha_cim and beta_cim");
   return module_forward_impl(d, q, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act,
                              out, ctx, ws, stream);
+}
+
+int cimq_module_forward_epilogue(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* x,
+                                 const float* weight, const float* alpha_act, const float* alpha_weight,
+                                 const float* alpha_cim, const float* beta_cim, const int8_t* binary_mask,
+                                 const float* signed_act, const cimq_epilogue* epi, float* out, void* ctx, void* ws,
+                                 void* stream) {
+  // (the descriptor-independent refusals first, before any other argument is looked at)
+  if (d && !(d->options & CIMQ_OPT_INFERENCE))
+    return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: a CIMQ_OPT_INFERENCE descriptor only (forward only)");
+  if (!epi || !epi->scale || !epi->shift)
+    return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: null epilogue, scale or shift");
+  if (epi->flags & ~CIMQ_EPI_RELU) return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: unknown flags 0x%x", epi->flags);
+  if (epi->reserved != 0) return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: reserved must be 0");
+  if (reinterpret_cast<uintptr_t>(epi->residual) % 16 != 0)
+    return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: residual must be 16-byte aligned");
+  if (beta_cim && !alpha_cim) return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: beta_cim needs alpha_cim");
+  const Epi ep{epi->scale, epi->shift, epi->residual, (epi->flags & CIMQ_EPI_RELU) ? 1 : 0};
+  return module_forward_impl(d, q, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act,
+                             out, ctx, ws, stream, &ep);
 }
 
 static int module_backward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* grad_out,

@@ -45,6 +45,24 @@ __device__ inline float slice_signed(float v, int k, int bs) {
   return slice_mag(pos, k, bs) - slice_mag(neg, k, bs);
 }
 
+// The output epilogue (Epi) on a value about to be stored: v * scale, + shift, + residual, ReLU, each one IEEE
+// fp32 operation in that order (what torch's mul, add, add, relu give on the stored tensor; a NaN stays NaN).
+// sc / sh are the lane's channel entries, read once by the caller; rv is read at the store's own address.
+__device__ inline float epi_val(float v, float sc, float sh, bool has_res, float rv, bool relu) {
+  float y = __fadd_rn(__fmul_rn(v, sc), sh);
+  if (has_res) y = __fadd_rn(y, rv);
+  if (relu) y = (y < 0.f) ? 0.f : y;
+  return y;
+}
+// ... on the four pixels of one channel a lane stores as a float4 at out + idx
+__device__ inline float4 epi_val4(const Epi& ep, float sc, float sh, size_t idx, float a0, float a1, float a2, float a3) {
+  const bool hr = ep.res != nullptr, rl = ep.relu != 0;
+  float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (hr) rv = *reinterpret_cast<const float4*>(ep.res + idx);
+  return make_float4(epi_val(a0, sc, sh, hr, rv.x, rl), epi_val(a1, sc, sh, hr, rv.y, rl),
+                     epi_val(a2, sc, sh, hr, rv.z, rl), epi_val(a3, sc, sh, hr, rv.w, rl));
+}
+
 // tensor.type(torch.int8): truncate toward zero, keep the low byte (wraps).  NaN -> 0.
 __device__ inline int to_i8_wrap(float v) {
   if (!(fabsf(v) < 2147483520.f)) return 0;

@@ -29,11 +29,15 @@ namespace cimq {
 // activation patch (f5_plan: NOB = 2 where OB16 is even, one 1024-thread block per CU)
 // WST: write the backward's state words and ctx (false where the module backward recomputes the partial sums,
 // cim_bwd_r6_kernel: the forward then writes only `out`, and its ADC epilogue skips the state-bit shifts)
-template <int NOB, bool WST>
+// EPI (forward only, with WST false): the output epilogue ep on the float4 about to be stored (epi_val4); the other
+// instances never read ep
+template <int NOB, bool WST, bool EPI = false>
 __global__ __attribute__((amdgpu_flat_work_group_size(512 * NOB, 512 * NOB), amdgpu_waves_per_eu(4, 4))) void cim_fwd5_kernel(
     Geo g, F5 v, const v4i* __restrict__ wf5, Params pp, const float* __restrict__ sw_p,
     const float* __restrict__ sa_p, const float* __restrict__ x, const float* __restrict__ sgn_p,
-    float* __restrict__ out, uint32_t* __restrict__ st, uint32_t* __restrict__ xcb, uint32_t* __restrict__ cal) {
+    float* __restrict__ out, uint32_t* __restrict__ st, uint32_t* __restrict__ xcb, uint32_t* __restrict__ cal,
+    Epi ep) {
+  static_assert(!(EPI && WST), "the epilogue instances are forward only");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int obl = wave >> 3, pw = wave & 7;  // this wave's output block within the block, its pixel group
@@ -281,7 +285,11 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512 * NOB, 512 * NOB), amd
     const int o = ob * 16 + r16;
     if (o < g.O) {
       const int bb = m0 / g.P, pq = m0 - bb * g.P;
-      *reinterpret_cast<float4*>(out + ((bb * g.O + o) * g.P + pq)) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+      const int oi = (bb * g.O + o) * g.P + pq;
+      if constexpr (EPI)
+        *reinterpret_cast<float4*>(out + oi) = epi_val4(ep, ep.scale[o], ep.shift[o], oi, acc[0], acc[1], acc[2], acc[3]);
+      else
+        *reinterpret_cast<float4*>(out + oi) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     }
   }
 }

@@ -1218,13 +1218,14 @@ inline void prof_end(int slot, hipStream_t s) {
 
 // ---- launchers defined in the cimq_part_*.hip translation units (compiled in parallel) ----
 // cimq_part_fwd.hip: the forward partial-sum kernels (v3 fast path or the general kernel;
-// the general kernel with ps_dbg / adc_dbg also writes every partial sum and ADC output)
+// the general kernel with ps_dbg / adc_dbg also writes every partial sum and ADC output).  ep: the output epilogue
+// of a forward-only call on the routes that store the module's output themselves (v3, fwd5, dense)
 int launch_fwd_any(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, int* ps_dbg,
                    float* adc_dbg, hipStream_t s,
-                   const ActQ* aq = nullptr);
+                   const ActQ* aq = nullptr, const Epi* ep = nullptr);
 // cimq_part_fwd5.hip: the w3a3 module forward on the slice-planar patch (f5_plan)
 int launch_fwd5(const Geo& g, const Plan5& p, uint8_t* ctx, const float* sw, const float* sa, float* out,
-                hipStream_t s, const ActQ* aq);
+                hipStream_t s, const ActQ* aq, const Epi* ep = nullptr);
 // cimq_part_gxw5.hip: grad_x (+ the fused act-LSQ backward) of the 16 -> 16-channel 32-wide layers (x5_plan)
 int launch_gx5(const Geo& g, const PlanX5& p, const uint8_t* ctx, const float* sw, const float* sa, const float* gout,
                const float* x, float* gx, uint8_t* ws, hipStream_t s);
@@ -1236,7 +1237,8 @@ int launch_gw5(const Geo& g, const PlanG5& p, const uint8_t* ctx, const float* g
 int launch_gxw5(const Geo& g, const PlanX5& px, const PlanG5& pw, const uint8_t* ctx, const float* sw, const float* sa,
                 const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s);
 // cimq_part_dense.hip: the dense path (dense_plan) -- forward, and grad_x + grad_w / grad_alpha slabs
-int launch_dense_fwd(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, hipStream_t s);
+int launch_dense_fwd(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, hipStream_t s,
+                     const Epi* ep = nullptr);
 // shift ADC on the fast path (cimq_part_shift.hip): grad_alpha / grad_beta from the forward's state words
 // (shift_stats_ok, above ws_layout; other layers take the general backward)
 int launch_shift_stats(const Geo& g, const uint8_t* ctx, const float* sw, const float* sa, const float* gout,

@@ -35,15 +35,21 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
                                                          const float* __restrict__ sw_p,
                                                          const float* __restrict__ sa_p, float* __restrict__ out,
                                                          uint8_t* __restrict__ st, const float* __restrict__ xin,
-                                                         const float* __restrict__ sgn_p, uint8_t* __restrict__ xcb) {
+                                                         const float* __restrict__ sgn_p, uint8_t* __restrict__ xcb,
+                                                         Epi ep) {
   // CSTA 9: the w8a8 fast path of CST 8 without the state words (cimq_c1.hip recomputes them)
   // CSTA 12 / 13 / 18: CST 2 / 3 / 8 forward only (CIMQ_OPT_INFERENCE) -- no state words, none of their bits on
   // either ADC path, and no backward words through xcb.  (CST 0 writes no state as it is.)  Encoded in CSTA so
   // that the training instances keep their symbols and their code.
   // xin (module path, NBP 4): the activation quantiser fused into the row staging (stage_rows_q)
-  constexpr int CST = CSTA == 9 ? 8 : CSTA >= 10 ? CSTA - 10 : CSTA;
-  constexpr bool WST = CSTA < 9;
-  constexpr bool INF = CSTA >= 10;
+  // CSTA 20 + s, s one of the stateless 0 / 9 / 12 / 13 / 18: the same with the output epilogue ep on the float4
+  // about to be stored (cimq_module_forward_epilogue, NCHW only); no other instance reads ep
+  constexpr bool EPI = CSTA >= 20;
+  constexpr int CSTB = EPI ? CSTA - 20 : CSTA;
+  static_assert(!EPI || CSTB == 0 || CSTB == 9 || CSTB >= 10, "the epilogue instances are forward only");
+  constexpr int CST = CSTB == 9 ? 8 : CSTB >= 10 ? CSTB - 10 : CSTB;
+  constexpr bool WST = CSTB < 9;
+  constexpr bool INF = CSTB >= 10;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int og = blockIdx.y;
   const int NOB = min(OBM, g.OB16);
@@ -465,8 +471,17 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
         if (g.onchw) {
           const int m4 = mt * 64 + wave * 16 + 4 * g4;  // M < 2^24 (v3_plan)
           const int bb = fdiv(m4, g.P, inv_p), pq = m4 - bb * g.P;
-          *reinterpret_cast<float4*>(out + ((size_t)bb * g.O + o) * g.P + pq) =
-              make_float4(acc[ob][0], acc[ob][1], acc[ob][2], acc[ob][3]);
+          const size_t oi = ((size_t)bb * g.O + o) * g.P + pq;
+          if constexpr (EPI) {
+            // (the table index through an opaque copy: the two 64-bit entry addresses, invariant over the m-tiles,
+            // would otherwise be kept in 4 VGPRs per output block across the whole loop -- a wave per SIMD in the
+            // OBM 4 instances)
+            int oe = o;
+            asm volatile("" : "+v"(oe));
+            *reinterpret_cast<float4*>(out + oi) =
+                epi_val4(ep, ep.scale[oe], ep.shift[oe], oi, acc[ob][0], acc[ob][1], acc[ob][2], acc[ob][3]);
+          } else
+            *reinterpret_cast<float4*>(out + oi) = make_float4(acc[ob][0], acc[ob][1], acc[ob][2], acc[ob][3]);
         }
       }
     }

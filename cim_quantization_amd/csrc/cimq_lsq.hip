@@ -369,6 +369,17 @@ __global__ void bpo_to_nchw_kernel(Geo g, const float* __restrict__ src, float* 
     dst[e] = src[(b * g.P + p) * g.O + o];
   }
 }
+// ... with the output epilogue of cimq_module_forward_epilogue on the element about to be stored (the general route's
+// forward-only call; a lane's elements are scalar stores, so its table entries and residual are scalar reads)
+__global__ void bpo_to_nchw_epi_kernel(Geo g, const float* __restrict__ src, float* __restrict__ dst, Epi ep) {
+  const size_t n = (size_t)g.M * g.O;
+  const bool hr = ep.res != nullptr, rl = ep.relu != 0;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+    const size_t p = e % g.P, bo = e / g.P;
+    const size_t o = bo % g.O, b = bo / g.O;
+    dst[e] = epi_val(src[(b * g.P + p) * g.O + o], ep.scale[o], ep.shift[o], hr, hr ? ep.res[e] : 0.f, rl);
+  }
+}
 __global__ void nchw_to_bpo_kernel(Geo g, const float* __restrict__ src, float* __restrict__ dst) {
   const size_t n = (size_t)g.M * g.O;
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {

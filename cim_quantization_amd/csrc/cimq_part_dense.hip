@@ -69,6 +69,32 @@ __device__ inline void adc_ps_out(int ps, int4 pv, float cf, float& acc) {
       : [ps] "v"(ps), [t] "v"(t), [thi] "v"(pv.x), [tlo] "v"(pv.y), [cf] "v"(cf));
 }
 
+// The output epilogue (Epi, epi_val's operations in its order) in place on the four rows a lane is about to store,
+// channel o, elements i0 + r * pitch.  The table entries and the residual values pass through ONE register, one load
+// in flight at a time (the compiler barriers): the store sits at these kernels' register peak, and the six
+// registers of the straightforward form cost several instances a wave per SIMD.
+__device__ inline void epi_rows4(const Epi& ep, int o, size_t i0, int pitch, float (&acc)[4]) {
+  float t = ep.scale[o];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) acc[r] = __fmul_rn(acc[r], t);
+  asm volatile("" ::: "memory");
+  t = ep.shift[o];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) acc[r] = __fadd_rn(acc[r], t);
+  if (ep.res) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      asm volatile("" ::: "memory");
+      t = ep.res[i0 + (size_t)r * pitch];
+      acc[r] = __fadd_rn(acc[r], t);
+    }
+  }
+  if (ep.relu) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = (acc[r] < 0.f) ? 0.f : acc[r];
+  }
+}
+
 // bit b of a 16-bit plane -> bit 2b
 __device__ inline uint32_t spread16(uint32_t x) {
   x &= 0xFFFFu;
@@ -82,11 +108,12 @@ __device__ inline uint32_t spread16(uint32_t x) {
 // forward: block = 64 rows x 64 channels, wave w = rows 16w..16w+15 x four 16-channel blocks (in turn)
 // ---------------------------------------------------------------------------------------------
 // WST false (the forward-only instances): no state planes, none of their bits
-template <int NBW, int NBA, int KS, bool LIT, bool WST = true>
+// EPI (forward only): the output epilogue ep on each value about to be stored (P = 1: out is NCHW as it is)
+template <int NBW, int NBA, int KS, bool LIT, bool WST = true, bool EPI = false>
 __device__ inline void dense_fwd_body(const Geo& g, const uint8_t* __restrict__ xcf, const v4i* __restrict__ wfrag,
                                       const Params& pp, float sw, float sa, float* __restrict__ out,
                                       uint2* __restrict__ st, int4* prm, float* cfl, float4* accs, int m0,
-                                      int og) {
+                                      int og, const Epi& ep) {
   constexpr int NKJ = NBW * NBA;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r16 = lane & 15, g4 = lane >> 4;
@@ -197,6 +224,7 @@ __device__ inline void dense_fwd_body(const Geo& g, const uint8_t* __restrict__ 
       if (i + 1 < g.T) {
         acc_l[ob * 64] = make_float4(acc[0], acc[1], acc[2], acc[3]);
       } else {
+        if constexpr (EPI) epi_rows4(ep, o, ((size_t)m0 + wave * 16 + 4 * g4) * g.O + o, g.O, acc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) out[((size_t)m0 + wave * 16 + 4 * g4 + r) * g.O + o] = acc[r];
       }
@@ -208,19 +236,20 @@ __device__ inline void dense_fwd_body(const Geo& g, const uint8_t* __restrict__ 
 // literal-ADC flag (dense_fwd_lit_kernel then does the work).
 // KSA (the three forward kernels): the K-steps per tile KS = KSA & 3; KSA >= 4 is the forward-only instance
 // (CIMQ_OPT_INFERENCE: no state planes through st) -- encoded there so that the training instances keep their
-// symbols and their code
+// symbols and their code; KSA >= 8 (12 + KS) is the forward-only instance with the output epilogue ep
 template <int NBW, int NBA, int KSA>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void dense_fwd_kernel(
     Geo g, const uint8_t* __restrict__ xcf, const v4i* __restrict__ wfrag, Params pp, const float* __restrict__ sw_p,
-    const float* __restrict__ sa_p, float* __restrict__ out, uint2* __restrict__ st) {
+    const float* __restrict__ sa_p, float* __restrict__ out, uint2* __restrict__ st, Epi ep) {
   constexpr int KS = KSA & 3;
   constexpr bool WST = KSA < 4;
+  constexpr bool EPI = KSA >= 8;
   __shared__ int4 prm[NBW * NBA * 64];  // this tile's ADC / STE thresholds, [j][k][64 channels]
   __shared__ float cfl[NBW * NBA * 64];
   __shared__ float4 accs[4 * 4 * 64];
   if (__builtin_amdgcn_readfirstlane(pp.flags[0]) != 0) return;
-  dense_fwd_body<NBW, NBA, KS, false, WST>(g, xcf, wfrag, pp, 0.f, 0.f, out, st, prm, cfl, accs, blockIdx.x * 64,
-                                      blockIdx.y);
+  dense_fwd_body<NBW, NBA, KS, false, WST, EPI>(g, xcf, wfrag, pp, 0.f, 0.f, out, st, prm, cfl, accs, blockIdx.x * 64,
+                                           blockIdx.y, ep);
 }
 
 // The threshold path on 128 x 64 tiles (512 threads, wave w = rows 16w..16w+15): the weight fragments
@@ -232,9 +261,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void d
 template <int NBW, int NBA, int KSA>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void dense_fwd8_kernel(
     Geo g, const uint8_t* __restrict__ xcf, const v4i* __restrict__ wfrag, Params pp, float* __restrict__ out,
-    uint2* __restrict__ st) {
+    uint2* __restrict__ st, Epi ep) {
   constexpr int KS = KSA & 3;
   constexpr bool WST = KSA < 4;
+  constexpr bool EPI = KSA >= 8;
   constexpr int NKJ = NBW * NBA;
   constexpr int NWH = KS * NBW * 2 * 64;  // v4i of one half's weight fragments
   __shared__ int4 prm[NKJ * 64];          // [j][k][64 channels]: thi, tlo, mlo, span
@@ -341,6 +371,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void d
       if (i + 1 < g.T) {
         acc_l[ob * 64] = make_float4(acc[0], acc[1], acc[2], acc[3]);
       } else {
+        if constexpr (EPI) epi_rows4(ep, o, ((size_t)m0 + wave * 16 + 4 * g4) * g.O + o, g.O, acc);
 #pragma unroll
         for (int r = 0; r < 4; ++r) out[((size_t)m0 + wave * 16 + 4 * g4 + r) * g.O + o] = acc[r];
       }
@@ -355,15 +386,17 @@ __global__ __launch_bounds__(256) void dense_fwd_lit_kernel(Geo g, const uint8_t
                                                             const v4i* __restrict__ wfrag, Params pp,
                                                             const float* __restrict__ sw_p,
                                                             const float* __restrict__ sa_p, float* __restrict__ out,
-                                                            uint2* __restrict__ st) {
+                                                            uint2* __restrict__ st, Epi ep) {
   constexpr int KS = KSA & 3;
   constexpr bool WST = KSA < 4;
+  constexpr bool EPI = KSA >= 8;
   __shared__ float4 accs[4 * 4 * 64];
   if (__builtin_amdgcn_readfirstlane(pp.flags[0]) == 0) return;
   const float sw = *sw_p, sa = *sa_p;
   const int nm = g.M / 64, ntile = nm * (g.O / 64);
   for (int t = blockIdx.x; t < ntile; t += gridDim.x)
-    dense_fwd_body<NBW, NBA, KS, true, WST>(g, xcf, wfrag, pp, sw, sa, out, st, nullptr, nullptr, accs, (t % nm) * 64, t / nm);
+    dense_fwd_body<NBW, NBA, KS, true, WST, EPI>(g, xcf, wfrag, pp, sw, sa, out, st, nullptr, nullptr, accs, (t % nm) * 64,
+                                                 t / nm, ep);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -681,29 +714,36 @@ __global__ __launch_bounds__(512) void dense_gw_kernel(Geo g, int rows_per_chunk
 // launchers
 // ---------------------------------------------------------------------------------------------
 template <int NBW, int NBA>
-int launch_dense_fwd_n(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, hipStream_t s) {
+int launch_dense_fwd_n(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, hipStream_t s,
+                       const Epi* ep) {
   CtxLayout L = ctx_layout(g);
-  // forward only (CIMQ_OPT_INFERENCE): the instances that write no state planes (KSA = 4 + KS)
+  // forward only (CIMQ_OPT_INFERENCE): the instances that write no state planes (KSA = 4 + KS), or those with
+  // the output epilogue as well (KSA = 12 + KS)
   const bool inf = g.inference != 0;
+  if (ep && (!inf || g.P != 1)) return fail(CIMQ_EINVAL, "internal: output epilogue off the forward-only dense path");
+  const Epi e = ep ? *ep : Epi{};
   auto klit = g.KS == 1 ? (inf ? dense_fwd_lit_kernel<NBW, NBA, 5> : dense_fwd_lit_kernel<NBW, NBA, 1>)
                         : (inf ? dense_fwd_lit_kernel<NBW, NBA, 6> : dense_fwd_lit_kernel<NBW, NBA, 2>);
+  if (ep) klit = g.KS == 1 ? dense_fwd_lit_kernel<NBW, NBA, 13> : dense_fwd_lit_kernel<NBW, NBA, 14>;
   const uint8_t* wr = wreg(g, ctx);
   uint2* st = reinterpret_cast<uint2*>(ctx + L.st);
   const int slot = prof_begin(KID_FWD, g, s);
   if (tune("DENSE_FWD8", 1)) {  // 128-row blocks, weight side staged once per block (dense_plan: M % 128 == 0)
     auto kern = g.KS == 1 ? (inf ? dense_fwd8_kernel<NBW, NBA, 5> : dense_fwd8_kernel<NBW, NBA, 1>)
                           : (inf ? dense_fwd8_kernel<NBW, NBA, 6> : dense_fwd8_kernel<NBW, NBA, 2>);
+    if (ep) kern = g.KS == 1 ? dense_fwd8_kernel<NBW, NBA, 13> : dense_fwd8_kernel<NBW, NBA, 14>;
     hipLaunchKernelGGL(kern, dim3(g.M / 128, g.O / 64), dim3(512), 0, s, g, ctx + L.xcode,
-                       reinterpret_cast<const v4i*>(wr + L.wfrag), params_of(g, ctx), out, st);
+                       reinterpret_cast<const v4i*>(wr + L.wfrag), params_of(g, ctx), out, st, e);
   } else {
     auto kern = g.KS == 1 ? (inf ? dense_fwd_kernel<NBW, NBA, 5> : dense_fwd_kernel<NBW, NBA, 1>)
                           : (inf ? dense_fwd_kernel<NBW, NBA, 6> : dense_fwd_kernel<NBW, NBA, 2>);
+    if (ep) kern = g.KS == 1 ? dense_fwd_kernel<NBW, NBA, 13> : dense_fwd_kernel<NBW, NBA, 14>;
     hipLaunchKernelGGL(kern, dim3(g.M / 64, g.O / 64), dim3(256), 0, s, g, ctx + L.xcode,
-                       reinterpret_cast<const v4i*>(wr + L.wfrag), params_of(g, ctx), sw, sa, out, st);
+                       reinterpret_cast<const v4i*>(wr + L.wfrag), params_of(g, ctx), sw, sa, out, st, e);
   }
   prof_end(slot, s);
   hipLaunchKernelGGL(klit, dim3(32), dim3(256), 0, s, g, ctx + L.xcode, reinterpret_cast<const v4i*>(wr + L.wfrag),
-                     params_of(g, ctx), sw, sa, out, st);
+                     params_of(g, ctx), sw, sa, out, st, e);
   return check_hip("dense_fwd");
 }
 
@@ -742,8 +782,9 @@ int launch_dense_bwd_n(const Geo& g, const uint8_t* ctx, const float* sw, const 
     default: return fail(CIMQ_EUNSUPPORTED, "dense path: no instance for nbw=%d nba=%d", g.nbw, g.nba); \
   }
 
-int launch_dense_fwd(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, hipStream_t s) {
-  CIMQ_DENSE_SEL(launch_dense_fwd_n, g, ctx, sw, sa, out, s)
+int launch_dense_fwd(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, hipStream_t s,
+                     const Epi* ep) {
+  CIMQ_DENSE_SEL(launch_dense_fwd_n, g, ctx, sw, sa, out, s, ep)
 }
 
 int launch_dense_bwd(const Geo& g, const uint8_t* ctx, const float* sw, const float* gout, float* gx, uint8_t* ws,

@@ -8,21 +8,32 @@ namespace cimq {
 
 template <int NBP, int KS>
 int launch_fwd_v3(const Geo& g, const Plan3& p, uint8_t* ctx, const float* sw, const float* sa, float* out,
-                  hipStream_t s, const ActQ* aq) {
+                  hipStream_t s, const ActQ* aq, const Epi* ep = nullptr) {
   CtxLayout L = ctx_layout(g);
   // CST, fixed at compile time: 0 per-k state words (the general backward's), else the compact ones the v7-plan
   // backwards read -- nbw = nba = CST (2, 3), 8 the w8a8 planes, 9 the first conv, whose backward recomputes
   // them; forward only (CIMQ_OPT_INFERENCE): the same instances without the state words, their bits and the
-  // backward words (10 + CST; 0 and 9 write no state as they are)
+  // backward words (10 + CST; 0 and 9 write no state as they are); with an output epilogue (ep, forward only, NCHW)
+  // 20 + that
   const int cst = route_of(g).cst;
   // OBM: 16-channel output blocks per block (register arrays sized for exactly that)
-  const int obm = std::min(p.v.obm, g.OB16 <= 2 ? g.OB16 : 4);
+  int obm = std::min(p.v.obm, g.OB16 <= 2 ? g.OB16 : 4);
+  // (the w2a2 four-block instances sit at a VGPR step -- 127 and 160 -- and the epilogue's residual float4 would
+  // cost them a wave per SIMD: with an epilogue those layers run the two-block instances, twice the blocks in y;
+  // the plan's LDS figures, made for four blocks, cover two)
+  if (ep && route_of(g).cst == 12 && obm == 4) obm = 2;
   void (*kern)(Geo, V3, const uint8_t*, const v4i*, Params, const float*, const float*, float*, uint8_t*,
-               const float*, const float*, uint8_t*);
+               const float*, const float*, uint8_t*, Epi);
 #define CIMQ_FWD3(CST) (obm == 1 ? cim_fwd_v3_kernel<NBP, KS, CST, 1> : obm == 2 ? cim_fwd_v3_kernel<NBP, KS, CST, 2> \
                                                                      : cim_fwd_v3_kernel<NBP, KS, CST, 4>)
   // (the instances in the order the code object has always had them: a kernel's place decides its addresses)
-  if (cst != 0 && g.inference) {
+  if (ep) {
+    if (!g.inference || !g.onchw) return fail(CIMQ_EINVAL, "internal: output epilogue off the forward-only module path");
+    if (cst == 0) kern = CIMQ_FWD3(20);
+    else if constexpr (NBP == 8) kern = cst == 9 ? cim_fwd_v3_kernel<8, KS, 29, 1> : cim_fwd_v3_kernel<8, KS, 38, 1>;
+    else if (cst == 12) kern = obm == 1 ? cim_fwd_v3_kernel<NBP, KS, 32, 1> : cim_fwd_v3_kernel<NBP, KS, 32, 2>;
+    else kern = CIMQ_FWD3(33);
+  } else if (cst != 0 && g.inference) {
     if constexpr (NBP == 8) kern = cst == 9 ? cim_fwd_v3_kernel<8, KS, 9, 1> : cim_fwd_v3_kernel<8, KS, 18, 1>;
     else kern = cst == 12 ? CIMQ_FWD3(12) : CIMQ_FWD3(13);
   } else if (cst == 0) {
@@ -42,22 +53,25 @@ int launch_fwd_v3(const Geo& g, const Plan3& p, uint8_t* ctx, const float* sw, c
   const int slot = prof_begin(cst ? KID_FWD_V7 : KID_FWD, g, s);
   hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, g, p.v, ctx + L.xcode,
                      reinterpret_cast<const v4i*>(wreg(g, ctx) + L.wfrag), params_of(g, ctx), sw, sa, out, ctx + L.st,
-                     aq ? aq->x : nullptr, aq ? aq->signed_act : nullptr, aq ? ctx + L.xhat : nullptr);
+                     aq ? aq->x : nullptr, aq ? aq->signed_act : nullptr, aq ? ctx + L.xhat : nullptr,
+                     ep ? *ep : Epi{});
   prof_end(slot, s);
   return check_hip("cim_fwd_v3");
 }
 
 template <int NBP, bool DBG>
 int launch_fwd(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, int* ps_dbg,
-               float* adc_dbg, hipStream_t s, const ActQ* aq) {
+               float* adc_dbg, hipStream_t s, const ActQ* aq, const Epi* ep = nullptr) {
   CtxLayout L = ctx_layout(g);
   const Plan3 p = v3_plan(g);
   if (p.ok && !DBG) {
     // (cim_fwd5_kernel writes NCHW only: a forward-only Function call, [B, P, O], stays on cim_fwd_v3_kernel)
-    if (aq && route_of(g).fwd == CIMQ_ROUTE_FWD5) return launch_fwd5(g, f5_plan(g), ctx, sw, sa, out, s, aq);
-    if (g.KS == 1) return launch_fwd_v3<NBP, 1>(g, p, ctx, sw, sa, out, s, aq);
-    return launch_fwd_v3<NBP, 2>(g, p, ctx, sw, sa, out, s, aq);
+    if (aq && route_of(g).fwd == CIMQ_ROUTE_FWD5) return launch_fwd5(g, f5_plan(g), ctx, sw, sa, out, s, aq, ep);
+    if (g.KS == 1) return launch_fwd_v3<NBP, 1>(g, p, ctx, sw, sa, out, s, aq, ep);
+    return launch_fwd_v3<NBP, 2>(g, p, ctx, sw, sa, out, s, aq, ep);
   }
+  // (the general kernel writes [B, P, O]: the module's epilogue is bpo_to_nchw_epi_kernel's)
+  if (ep) return fail(CIMQ_EINVAL, "internal: output epilogue on the general forward kernel");
   if (p.ok) {
     // the debug forward is the general kernel; the fast one still fills the state words the
     // fast backward reads (same out values)
@@ -78,21 +92,22 @@ int launch_fwd(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, flo
 
 
 int launch_fwd_any(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, int* ps_dbg,
-                   float* adc_dbg, hipStream_t s, const ActQ* aq) {
+                   float* adc_dbg, hipStream_t s, const ActQ* aq, const Epi* ep) {
   const Route r = route_of(g);
   if (aq && (!r.actq || ps_dbg)) return fail(CIMQ_EINVAL, "internal: fused activation quantiser off its plan");
+  if (ep && (ps_dbg || !g.inference)) return fail(CIMQ_EINVAL, "internal: output epilogue off the forward-only path");
   if (r.fwd == CIMQ_ROUTE_DENSE) {
     // the dense GEMM path (its state words feed the dense backward); the debug hook then reruns
     // the general kernel for the partial sums (same out values)
-    CIMQ_TRY(launch_dense_fwd(g, ctx, sw, sa, out, s));
+    CIMQ_TRY(launch_dense_fwd(g, ctx, sw, sa, out, s, ep));
     if (!ps_dbg) return CIMQ_OK;
   }
   if (ps_dbg) {
     if (g.NBP == 4) return launch_fwd<4, true>(g, ctx, sw, sa, out, ps_dbg, adc_dbg, s, nullptr);
     return launch_fwd<8, true>(g, ctx, sw, sa, out, ps_dbg, adc_dbg, s, nullptr);
   }
-  if (g.NBP == 4) return launch_fwd<4, false>(g, ctx, sw, sa, out, nullptr, nullptr, s, aq);
-  return launch_fwd<8, false>(g, ctx, sw, sa, out, nullptr, nullptr, s, nullptr);
+  if (g.NBP == 4) return launch_fwd<4, false>(g, ctx, sw, sa, out, nullptr, nullptr, s, aq, ep);
+  return launch_fwd<8, false>(g, ctx, sw, sa, out, nullptr, nullptr, s, nullptr, ep);
 }
 
 }  // namespace cimq

@@ -6,15 +6,17 @@
 namespace cimq {
 
 int launch_fwd5(const Geo& g, const Plan5& p, uint8_t* ctx, const float* sw, const float* sa, float* out,
-                hipStream_t s, const ActQ* aq) {
+                hipStream_t s, const ActQ* aq, const Epi* ep) {
   if (!p.ok || !aq || !g.onchw) return fail(CIMQ_EINVAL, "internal: cim_fwd5 off its plan");
   CtxLayout L = ctx_layout(g);
   const Route r = route_of(g);
   // the state words and ctx only where the backward reads them (not where cim_bwd_r6_kernel recomputes, and
   // not in a forward-only call, CIMQ_OPT_INFERENCE)
   const bool wst = r.state != ST_NONE;
+  if (ep && wst) return fail(CIMQ_EINVAL, "internal: output epilogue on a forward that writes state");
   auto kern = p.nob == 2 ? (wst ? cim_fwd5_kernel<2, true> : cim_fwd5_kernel<2, false>)
                          : (wst ? cim_fwd5_kernel<1, true> : cim_fwd5_kernel<1, false>);
+  if (ep) kern = p.nob == 2 ? cim_fwd5_kernel<2, false, true> : cim_fwd5_kernel<1, false, true>;
   CIMQ_TRY(set_lds(kern, p.lds));
   // 4 waves per SIMD: two 512-thread blocks per CU (one output block each) or one 1024-thread block (two),
   // a grid-stride walk over the 128-pixel m-tiles; the output-block groups in y
@@ -27,7 +29,7 @@ int launch_fwd5(const Geo& g, const Plan5& p, uint8_t* ctx, const float* sw, con
   hipLaunchKernelGGL(kern, grid, dim3(512 * p.nob), p.lds, s, g, v, reinterpret_cast<const v4i*>(wreg(g, ctx) + L.wf5),
                      params_of(g, ctx), sw, sa, aq->x, aq->signed_act, out,
                      reinterpret_cast<uint32_t*>(ctx + L.st), reinterpret_cast<uint32_t*>(ctx + L.xhat),
-                     reinterpret_cast<uint32_t*>(ctx + L.alut));
+                     reinterpret_cast<uint32_t*>(ctx + L.alut), ep ? *ep : Epi{});
   prof_end(slot, s);
   return check_hip("cim_fwd5");
 }

@@ -59,6 +59,15 @@ struct Params {
   float* bsum;  // [Opad]: sum over (i, k, j) of beta * binary_mask (shift_fast forward)
 };
 
+// The output epilogue of cimq_module_forward_epilogue (cimq_epilogue, include/cimq.h), the last argument of the
+// forward kernels: only their epilogue instances (forward only, CIMQ_OPT_INFERENCE) read it.
+struct Epi {
+  const float* scale;  // [O]
+  const float* shift;  // [O]
+  const float* res;    // null, or the residual in out's layout (NCHW)
+  int relu;            // CIMQ_EPI_RELU
+};
+
 __host__ __device__ inline int pidx(const Geo& g, int i, int j, int k, int o) {
   return ((i * g.nba + j) * g.nbw + k) * g.Opad + o;
 }

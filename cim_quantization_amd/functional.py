@@ -844,6 +844,65 @@ def cim_module_shift_conv(x, weight, alpha_act, alpha_weight, alpha_cim, beta_ci
                                      xbar, nbits_alpha)
 
 
+def cim_module_conv_epilogue(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding,
+                             dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha, scale, shift,
+                             residual=None, relu=False, beta_cim=None, stochastic=False, wprep=None, recompute=False):
+    """cim_module_conv (``beta_cim`` None) or cim_module_shift_conv (``beta_cim`` given) of a call nothing can
+    differentiate, with a per-channel epilogue applied in the registers of the kernel that stores the output
+    (cimq_module_forward_epilogue, ABI 16): ``out = relu?(conv * scale[o] + shift[o] + residual?)``, each step one
+    IEEE fp32 operation in that order -- bit for bit what ``torch.relu(conv * scale.view(1, -1, 1, 1) +
+    shift.view(1, -1, 1, 1) + residual)`` gives on cim_module_conv's output.  ``scale`` / ``shift``: [O] fp32 device
+    tensors (a folded BatchNorm); ``residual``: NCHW like the output, made contiguous fp32 if it is not.  Forward
+    only: a call that could be differentiated raises RuntimeError."""
+    if not inference_call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, scale, shift, residual):
+        raise RuntimeError("cim_module_conv_epilogue is forward only: call it under torch.no_grad(), or with no "
+                           "argument that requires a gradient")
+    _require_device(x)
+    dev = x.device
+    B, C, H, W, O, KH, KW, st, pd = _geometry(x, weight, stride, padding, dilation)
+    if beta_cim is None:
+        desc, lsq = _module_descs(tuple(x.shape), weight, st, pd, dilation, nbits_a, abitslice, nbits_w, wbitslice,
+                                  adcbits, xbar, nbits_alpha, alpha_cim is not None, stochastic, recompute, True)
+    else:
+        desc, lsq = _shift_module_descs(tuple(x.shape), weight, st, pd, dilation, nbits_a, abitslice, nbits_w,
+                                        wbitslice, xbar, nbits_alpha)
+        desc.options |= _lib.CIMQ_OPT_INFERENCE
+    keep = None
+    if (beta_cim is None and wprep is not None and not stochastic and wprep.key == _prep_key(desc, lsq, x.shape)
+            and wprep.versions == _versions(weight, alpha_act, alpha_weight, alpha_cim, binary_mask)):
+        lsq.wprep = wprep.buf.data_ptr()
+        keep = wprep.buf
+    sizes = _lib.query_sizes(desc)
+    f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
+    xc, wc = f32(x), f32(weight)
+    aa, aw = f32(alpha_act).reshape(-1)[:1].contiguous(), f32(alpha_weight).reshape(-1)[:1].contiguous()
+    ac = None if alpha_cim is None else f32(alpha_cim)
+    bc = None if beta_cim is None else f32(beta_cim)
+    bm = binary_mask.to(device=dev, dtype=torch.int8).contiguous()
+    sg = f32(signed_act).reshape(-1)[:1].contiguous()
+    sc, sh = f32(scale).reshape(-1), f32(shift).reshape(-1)
+    if sc.numel() != O or sh.numel() != O:
+        raise ValueError(f"cim_module_conv_epilogue: scale / shift need {O} elements (one per output channel)")
+    Ho = (H + 2 * pd[0] - KH) // st[0] + 1
+    Wo = (W + 2 * pd[1] - KW) // st[1] + 1
+    rs = None
+    if residual is not None:
+        if tuple(residual.shape) != (B, O, Ho, Wo):
+            raise ValueError(f"cim_module_conv_epilogue: residual {tuple(residual.shape)} is not the output's "
+                             f"{(B, O, Ho, Wo)}")
+        rs = f32(residual)
+    out = torch.empty(B, O, Ho, Wo, device=dev, dtype=torch.float32)
+    cbuf = torch.empty(max(sizes.ctx_bytes, 1), device=dev, dtype=torch.uint8)
+    ws = torch.empty(max(sizes.fwd_workspace_bytes, 1), device=dev, dtype=torch.uint8)
+    epi = _lib.make_epilogue(sc.data_ptr(), sh.data_ptr(), None if rs is None else rs.data_ptr(), relu)
+    _lib.check(_lib.load().cimq_module_forward_epilogue(
+        desc, lsq, xc.data_ptr(), wc.data_ptr(), aa.data_ptr(), aw.data_ptr(), None if ac is None else ac.data_ptr(),
+        None if bc is None else bc.data_ptr(), bm.data_ptr(), sg.data_ptr(), ctypes.byref(epi), out.data_ptr(),
+        cbuf.data_ptr(), ws.data_ptr(), _stream()), "cimq_module_forward_epilogue")
+    del keep
+    return out
+
+
 def alpha_cim_init(x, w_q, sa, sw, binary_mask, signed_act, stride, padding, nbits_a, abitslice,
                    nbits_w, wbitslice, adcbits, xbar, num_xbars):
     """First-step alpha_cim initialisation on the device (lsq.py:557-563, 35-87)."""

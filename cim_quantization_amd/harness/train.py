@@ -42,6 +42,8 @@ def get_base_parser():
     p.add_argument("--start-epoch", default=0, type=int)
     p.add_argument("--max-steps", default=0, type=int, help="stop each epoch after this many steps (0: all)")
     p.add_argument("--max-val-steps", default=0, type=int)
+    p.add_argument("--fused-eval", action="store_true",
+                   help="validate with BatchNorm, residual add and ReLU folded into the CiM convs (harness.fuse)")
     return p
 
 
@@ -188,12 +190,18 @@ def train_epoch(loader, model, criterion, optimizer, epoch, hp, max_steps=0, log
     return loss_sum / max(seen, 1), top1 / max(seen, 1)
 
 
-def validate(loader, model, criterion, hp, max_steps=0):
+def validate(loader, model, criterion, hp, max_steps=0, fused=False):
     """main_lsq.py's validate(): top-1 / top-5 accuracy and mean loss in eval mode under no_grad.
     Nothing here selects the evaluation path: under no_grad every Conv2dLSQCiM runs libcimq's
     forward-only mode by itself (CIMQ_OPT_INFERENCE: same outputs, no backward state) and keeps its
-    prepared weight side across the batches, so the weights are quantised once per input shape."""
+    prepared weight side across the batches, so the weights are quantised once per input shape.
+    ``fused``: evaluate through harness.fuse.FusedEval instead (folded BatchNorm, residual add and ReLU in the
+    conv kernels' epilogue; not bit-identical to the BatchNorm path, see that module)."""
     model.eval()
+    if fused:
+        from .fuse import FusedEval
+        bare = model.module if isinstance(model, nn.parallel.DistributedDataParallel) else model
+        model = FusedEval(bare)
     seen, loss_sum, c1, c5 = 0, 0.0, 0.0, 0.0
     with torch.no_grad():
         for i, (x, y) in enumerate(loader):
@@ -243,7 +251,7 @@ def main(argv=None):
     val_loader = CifarLoader(xte, yte, batch, device, train=False)
     log = print if rank == 0 else (lambda *a, **k: None)
     if hp.evaluate:
-        acc1, acc5, _ = validate(val_loader, model, criterion, hp, args.max_val_steps)
+        acc1, acc5, _ = validate(val_loader, model, criterion, hp, args.max_val_steps, fused=args.fused_eval)
         log(f" * Acc@1 {acc1:.3f} Acc@5 {acc5:.3f}")
         return acc1
     for _ in range(args.start_epoch):
@@ -251,14 +259,14 @@ def main(argv=None):
     best = 0.0
     if rank == 0:
         os.makedirs(hp.log_name, exist_ok=True)
-    acc1, acc5, _ = validate(val_loader, model, criterion, hp, args.max_val_steps)  # main_lsq.py validates first
+    acc1, acc5, _ = validate(val_loader, model, criterion, hp, args.max_val_steps, fused=args.fused_eval)  # main_lsq.py validates first
     log(f"before training: val acc1 {acc1:.3f} acc5 {acc5:.3f}")
     acc1 = 0.0
     for epoch in range(args.start_epoch, hp.epochs):
         train_loader.set_epoch(epoch)
         loss, tacc = train_epoch(train_loader, model, criterion, optimizer, epoch, hp, args.max_steps, log)
         scheduler.step()
-        acc1, acc5, vloss = validate(val_loader, model, criterion, hp, args.max_val_steps)
+        acc1, acc5, vloss = validate(val_loader, model, criterion, hp, args.max_val_steps, fused=args.fused_eval)
         log(f"epoch {epoch}: train loss {loss:.4f} acc1 {tacc:.2f}  val acc1 {acc1:.3f} acc5 {acc5:.3f}")
         is_best = acc1 > best
         best = max(acc1, best)

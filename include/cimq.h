@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define CIMQ_ABI_VERSION 15
+#define CIMQ_ABI_VERSION 16
 
 /* status codes */
 #define CIMQ_OK 0
@@ -253,6 +253,34 @@ int cimq_module_shift_backward(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
                                const int8_t* binary_mask, const float* signed_act, const void* ctx, float* grad_x,
                                float* grad_weight, float* grad_alpha_act, float* grad_alpha_weight,
                                float* grad_alpha_cim, float* grad_beta_cim, void* ws, void* stream);
+
+/* cimq_epilogue.flags */
+#define CIMQ_EPI_RELU 1 /* y = (y < 0) ? 0 : y as the last step (a NaN stays NaN) */
+
+/* The output epilogue of cimq_module_forward_epilogue: per output channel o, with v the value
+ * cimq_module_forward stores at (b, o, h, w),
+ *   y = v * scale[o];  y = y + shift[o];  y = y + residual[b, o, h, w] (residual != NULL);  ReLU (CIMQ_EPI_RELU)
+ * each step one IEEE fp32 operation, in that order, no fused multiply-add: what torch's mul, add, add, relu give
+ * on the stored tensor.  A BatchNorm in evaluation mode folds into (scale, shift).  Since ABI 16. */
+typedef struct cimq_epilogue {
+  const float* scale;    /* [O] device */
+  const float* shift;    /* [O] device */
+  const float* residual; /* NULL, or [B, O, Ho, Wo] NCHW fp32, 16-byte aligned, not overlapping out */
+  int32_t flags;         /* CIMQ_EPI_* */
+  int32_t reserved;      /* 0 */
+} cimq_epilogue;
+
+/* cimq_module_forward (beta_cim NULL) or cimq_module_shift_forward (beta_cim given, by that call's rules) of a
+ * CIMQ_OPT_INFERENCE descriptor with ``epi`` applied in the registers of the kernel that stores ``out``: the same
+ * launches, the same buffers (cimq_query_sizes; no extra workspace), the same q->wprep rules, and ``out`` equal
+ * bit for bit to the epilogue's four operations run on cimq_module_forward's output.  CIMQ_EINVAL for a
+ * descriptor without CIMQ_OPT_INFERENCE, a NULL epi / scale / shift, unknown flag bits, a non-zero reserved, a
+ * residual that is not 16-byte aligned or that overlaps out.  Since ABI 16. */
+int cimq_module_forward_epilogue(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* x,
+                                 const float* weight, const float* alpha_act, const float* alpha_weight,
+                                 const float* alpha_cim, const float* beta_cim, const int8_t* binary_mask,
+                                 const float* signed_act, const cimq_epilogue* epi, float* out, void* ctx, void* ws,
+                                 void* stream);
 
 /* One layer of cimq_module_prepare: its descriptors (as the forward will receive them; the
  * lsq descriptor's wprep and flags are ignored here) and raw parameters, and its output buffer

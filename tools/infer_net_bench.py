@@ -1,0 +1,146 @@
+"""Whole-network evaluation A/B on the MI355X: the harness ResNet-20 with cfg2's settings (w3a3, the w8a8 first
+conv, xbar 128, 1.5-bit ADC) on a synthetic batch, eval mode under torch.no_grad(), in ONE process:
+
+  side A  model(x) -- ResNet.forward: every CiM conv a forward-only library call, then BatchNorm, the residual
+          add and ReLU as torch kernels;
+  side B  FusedEval(model)(x) -- each BatchNorm folded into a per-channel affine and, with the residual add and
+          the ReLU, applied in the conv kernel's registers (cimq_module_forward_epilogue).
+
+The two sides alternate (A, B, A again per round); a window is HIP events round ``passes`` forwards, sized to at
+least --window seconds; the second A window of a round gives the run-to-run spread.  Reports the time per
+forward of both sides, the spread, the device kernel launches of one forward of each (torch.profiler), the
+largest logit difference between the two (they are not bit-identical: harness/fuse.py) and
+torch.cuda.max_memory_allocated of one forward of each.
+
+    python tools/infer_net_bench.py [--batch 256] [--rounds 7] [--window 0.25]
+                                    [--out profiles/inference/infer_net_bench_B256.json]
+
+Needs the GPU: there is no CPU fallback and no number without a run.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+import bench  # noqa: E402
+from cim_quantization_amd import _lib  # noqa: E402
+from cim_quantization_amd._modules.lsq import Conv2dLSQCiM  # noqa: E402
+from cim_quantization_amd.harness import models  # noqa: E402
+from cim_quantization_amd.harness.fuse import FusedEval  # noqa: E402
+from cim_quantization_amd.harness.replace import ReplaceModuleTool  # noqa: E402
+
+
+def build_model(batch, dev):
+    torch.manual_seed(20)
+    model = models.resnet20()
+    ReplaceModuleTool(model, {"Conv2d": [Conv2dLSQCiM]}, True, nbits_w=3, nbits_a=3, nbits_alpha=8, wbitslice=1,
+                      abitslice=1, xbar=bench.XBAR, adcbits=bench.ADC, signed_xbar=True,
+                      stochastic_quant=False).replace()
+    model = model.to(dev).train()
+    x = torch.randn(batch, 3, 32, 32, generator=torch.Generator().manual_seed(21)).to(dev)
+    model(x)  # the first-step initialisation of every layer, and BatchNorm statistics that are not the defaults
+    model.eval()
+    return model, x
+
+
+def timed(fn, n):
+    """milliseconds per call of fn over n calls, between two HIP events"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def count_launches(fn):
+    """device kernels of one call of fn (and how many of them are libcimq's), or None without a profiler"""
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        names = [e.name for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
+        names = [n for n in names if not n.lower().startswith(("memcpy", "memset"))]
+        return {"kernels": len(names), "libcimq": sum("cimq::" in n for n in names)}
+    except Exception as e:  # noqa: BLE001 -- the count is a side figure: the timing does not depend on it
+        return {"error": f"{type(e).__name__}: {e}"}
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--window", type=float, default=0.25, help="seconds per timed window (at least 0.2)")
+    ap.add_argument("--no-launch-count", action="store_true")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("infer_net_bench: no ROCm device (there is no CPU fallback; nothing is measured)")
+    out_path = args.out or os.path.join(REPO, "profiles", "inference", f"infer_net_bench_B{args.batch}.json")
+    dev = torch.device("cuda:0")
+    model, x = build_model(args.batch, dev)
+    fused = FusedEval(model)
+    sides = {"A": lambda: model(x), "B": lambda: fused(x)}
+    with torch.no_grad():
+        ya, yb = sides["A"](), sides["B"]()
+        diff = {"max_abs_logit_difference": float((ya - yb).abs().max()), "max_abs_logit": float(ya.abs().max()),
+                "top1_agree": float((ya.argmax(1) == yb.argmax(1)).float().mean())}
+        del ya, yb
+        for fn in sides.values():
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        passes = max(1, int(max(args.window, 0.2) / (timed(sides["A"], 5) * 1e-3) + 1))
+        peak, launches = {}, {}
+        for key, fn in sides.items():
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            fn()
+            torch.cuda.synchronize()
+            peak[key] = {"max_memory_allocated": torch.cuda.max_memory_allocated(),
+                         "above_resident": torch.cuda.max_memory_allocated() - base}
+        tot = {"A": [], "B": [], "A2": []}
+        for _ in range(args.rounds):
+            for key in ("A", "B", "A2"):
+                tot[key].append(timed(sides[key[0]], passes) * 1e3)
+        if not args.no_launch_count:  # (after the timing: the profiler stays out of the windows)
+            for key, fn in sides.items():
+                launches[key] = count_launches(fn)
+    med = {k: statistics.median(v) for k, v in tot.items()}
+    spread = max(abs(a - b) for a, b in zip(tot["A"], tot["A2"]))
+    result = {
+        "workload": f"harness ResNet-20 evaluation forward (model(x) vs FusedEval(model)(x)), eval + no_grad, "
+                    f"B = {args.batch}, w3a3 (first conv w8a8), xbar {bench.XBAR}, adc {bench.ADC}, synthetic input",
+        "device": torch.cuda.get_device_name(0), "abi": _lib.ABI_VERSION,
+        "passes_per_window": passes, "rounds": args.rounds,
+        "forward_us": {k: round(v, 1) for k, v in med.items()},
+        "forward_us_windows": {k: [round(t, 1) for t in v] for k, v in tot.items()},
+        "spread_us": round(spread, 1),  # the largest |A - A2| of a round: the same code, the same call
+        "B_minus_A_us": round(med["B"] - med["A"], 1),
+        "B_not_above_A_by_more_than_spread": bool(med["B"] <= med["A"] + spread),
+        "kernel_launches_per_forward": launches,
+        "peak_memory_bytes": peak,
+        "fused_vs_batchnorm_path": diff,
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(json.dumps({k: result[k] for k in ("forward_us", "spread_us", "B_minus_A_us", "kernel_launches_per_forward",
+                                             "peak_memory_bytes", "fused_vs_batchnorm_path")}))
+    return result
+
+
+if __name__ == "__main__":
+    main()
