@@ -191,8 +191,10 @@ class Conv2dLSQCiM(_Conv2dQCiM):
             out = cim_conv2d_lsq(x, w_q, sa, sw, alpha_q, self.binary_mask, self.signed_act, self.stride,
                                  self.padding, self.dilation, self.nbits_a, self.abitslice, self.nbits_w,
                                  self.wbitslice, self.adcbits, self.xbar, bool(self.stochastic_quant))
-        fold_x = int((x.shape[-1] - self.weight.shape[-1] + 2 * self.padding[0]) / self.stride[0] + 1)
-        out = out.transpose(1, 2).view(x.shape[0], self.out_channels, fold_x, fold_x)  # lsq.py:580-581
+        # lsq.py:123's fold_x, per axis (the same number twice for the reference's square layers)
+        ho = (x.shape[-2] - self.weight.shape[-2] + 2 * self.padding[0]) // self.stride[0] + 1
+        wo = (x.shape[-1] - self.weight.shape[-1] + 2 * self.padding[1]) // self.stride[1] + 1
+        out = out.transpose(1, 2).view(x.shape[0], self.out_channels, ho, wo)         # lsq.py:580-581
         if self.bias is not None:
             out = out + self.bias  # broadcasts over the last axis, as lsq.py:583
         return out

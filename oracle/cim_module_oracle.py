@@ -145,8 +145,9 @@ class OracleConv2dLSQCiM(torch.nn.Conv2d):
                                           self.nbits_a, self.abitslice, self.nbits_w, self.wbitslice,
                                           self.adcbits, self.xbar, self.binary_mask, alpha_q, sw, sa,
                                           self.stochastic_quant, self.signed_act)
-        fx = int((x_q.shape[-1] - self.weight.shape[-1] + 2 * self.padding[0]) / self.stride[0] + 1)
-        out = out.transpose(1, 2).view(x_q.shape[0], self.out_channels, fx, fx)
+        ho = co.out_size(x_q.shape[2], self.weight.shape[2], self.padding[0], self.stride[0])
+        wo = co.out_size(x_q.shape[3], self.weight.shape[3], self.padding[1], self.stride[1])
+        out = out.transpose(1, 2).view(x_q.shape[0], self.out_channels, ho, wo)
         if self.bias is not None:
             out = out + self.bias
         return out

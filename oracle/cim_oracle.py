@@ -17,8 +17,8 @@ inputs, asserts this oracle agrees, and commits the vectors under ``tests/golden
 
 Layout conventions (all identical to the reference):
   x           [B, C, H, W]  fp32 (NCHW)
-  weight      [O, C, k, k]  fp32
-  unfold      [B, P, K]     P = Ho*Wo, K = C*k*k, f = c*k*k + kh*k + kw
+  weight      [O, C, kh, kw] fp32
+  unfold      [B, P, K]     P = Ho*Wo, K = C*kh*kw, f = (c*kh + i)*kw + j
   ps (fp16)   [B, T, nbw, nba, P, O]
   alpha_cim   [1, T, nbw, nba, 1, O]
   out         [B, P, O]
@@ -126,34 +126,46 @@ def out_size(h: int, k: int, pad: int, stride: int) -> int:
     return (h + 2 * pad - k) // stride + 1
 
 
-def unfold(x: np.ndarray, k: int, padding, stride) -> np.ndarray:
-    """im2col: [B,C,H,W] -> [B, P, C*k*k] (rows = output pixels, row-major)."""
+def _kernel_hw(k):
+    """``k`` as (kh, kw): an int means a square kernel."""
+    if isinstance(k, (int, np.integer)):
+        return int(k), int(k)
+    kh, kw = k
+    return int(kh), int(kw)
+
+
+def unfold(x: np.ndarray, k, padding, stride) -> np.ndarray:
+    """im2col: [B,C,H,W] -> [B, P, C*kh*kw] (rows = output pixels, row-major).
+    ``k`` is an int or (kh, kw)."""
     b, c, h, w = x.shape
+    kh_, kw_ = _kernel_hw(k)
     ph, pw = padding
     sh, sw_ = stride
-    ho, wo = out_size(h, k, ph, sh), out_size(w, k, pw, sw_)
+    ho, wo = out_size(h, kh_, ph, sh), out_size(w, kw_, pw, sw_)
     xp = np.zeros((b, c, h + 2 * ph, w + 2 * pw), dtype=x.dtype)
     xp[:, :, ph:ph + h, pw:pw + w] = x
-    cols = np.empty((b, c, k, k, ho, wo), dtype=x.dtype)
-    for kh in range(k):
-        for kw in range(k):
+    cols = np.empty((b, c, kh_, kw_, ho, wo), dtype=x.dtype)
+    for kh in range(kh_):
+        for kw in range(kw_):
             cols[:, :, kh, kw] = xp[:, :, kh:kh + sh * (ho - 1) + 1:sh, kw:kw + sw_ * (wo - 1) + 1:sw_]
-    return cols.reshape(b, c * k * k, ho * wo).transpose(0, 2, 1)
+    return cols.reshape(b, c * kh_ * kw_, ho * wo).transpose(0, 2, 1)
 
 
-def fold(cols: np.ndarray, hw, k: int, padding, stride) -> np.ndarray:
-    """col2im: [B, C*k*k, P] -> [B,C,H,W], summing overlapping patches."""
+def fold(cols: np.ndarray, hw, k, padding, stride) -> np.ndarray:
+    """col2im: [B, C*kh*kw, P] -> [B,C,H,W], summing overlapping patches.
+    ``k`` is an int or (kh, kw)."""
     b, kk, p = cols.shape
     h, w = hw
+    kh_, kw_ = _kernel_hw(k)
     ph, pw = padding
     sh, sw_ = stride
-    c = kk // (k * k)
-    ho, wo = out_size(h, k, ph, sh), out_size(w, k, pw, sw_)
+    c = kk // (kh_ * kw_)
+    ho, wo = out_size(h, kh_, ph, sh), out_size(w, kw_, pw, sw_)
     assert ho * wo == p
-    cv = cols.reshape(b, c, k, k, ho, wo)
+    cv = cols.reshape(b, c, kh_, kw_, ho, wo)
     xp = np.zeros((b, c, h + 2 * ph, w + 2 * pw), dtype=cols.dtype)
-    for kh in range(k):
-        for kw in range(k):
+    for kh in range(kh_):
+        for kw in range(kw_):
             xp[:, :, kh:kh + sh * (ho - 1) + 1:sh, kw:kw + sw_ * (wo - 1) + 1:sw_] += cv[:, :, kh, kw]
     return xp[:, :, ph:ph + h, pw:pw + w]
 
@@ -268,12 +280,10 @@ def cim_forward(x_q, w_q, stride, padding, dilation, act_bits, act_bs, w_bits, w
     ctx = CimCtx()
     ctx.x_int8 = to_int8(x_int)                                      # :99
     nbw, nba = int(w_bits / w_bs), int(act_bits / act_bs)            # :115-117
-    O, C, k = w_int.shape[0], w_int.shape[1], w_int.shape[2]
-    fold_x = int((x_int.shape[-1] - w_int.shape[-1] + 2 * padding[0]) / stride[0] + 1)  # :123
+    O, C, k = w_int.shape[0], w_int.shape[1], tuple(w_int.shape[2:])
     qn, qp = adc_range(adc_bits)
     x_unf = unfold(x_int, k, padding, stride)                        # :141
     B, P, K = x_unf.shape
-    assert P == fold_x * fold_x, "reference assumes square outputs"
     if float(np.asarray(signed_act).reshape(-1)[0]) != 0:            # :146-149
         xs = slicing_signed(x_unf, act_bits, act_bs).transpose(1, 0, 2, 3)
     else:
@@ -307,7 +317,7 @@ def cim_forward(x_q, w_q, stride, padding, dilation, act_bits, act_bs, w_bits, w
 def cim_backward(ctx: CimCtx, grad_out: np.ndarray, absolute: bool = False):
     """``get_cim_output_signed.backward`` (lsq.py:244-386).
 
-    Returns (grad_x [B,C,H,W], grad_w [O,C,k,k], grad_alpha [1,T,nbw,nba,1,O] or None);
+    Returns (grad_x [B,C,H,W], grad_w [O,C,kh,kw], grad_alpha [1,T,nbw,nba,1,O] or None);
     with the scale/shift option (ctx.beta) also grad_beta as a fourth element.
     ``absolute=True`` re-runs the same contraction in fp64 on |operands|, giving the
     per-element sum of |terms| that the parity tolerances are scaled by."""
@@ -383,7 +393,7 @@ def cim_backward(ctx: CimCtx, grad_out: np.ndarray, absolute: bool = False):
         gw[i] = gw[i] / dt((2 ** m["w_bs"]) ** i)
     gw = gw.mean(axis=0, dtype=dt).astype(dt)                                    # :366
     C, k = m["C"], m["k"]
-    gw = np.ascontiguousarray(gw.T).reshape(O, C, k, k)                          # :369
+    gw = np.ascontiguousarray(gw.T).reshape(O, C, *k)                            # :369
     gi = gi.sum(axis=1)                                                          # :372
     for i in range(1, nba):                                                      # :373-374
         gi[:, i] = gi[:, i] / dt((2 ** m["act_bs"]) ** i)
@@ -406,7 +416,7 @@ def analog_partial_sums(x_q, w_q, stride, padding, act_bits, act_bs, w_bits, w_b
     w_int = (np.asarray(w_q, F32) / sw).astype(F32)
     x_int = (np.asarray(x_q, F32) / sa).astype(F32)
     nbw, nba = int(w_bits / w_bs), int(act_bits / act_bs)
-    O, k = w_int.shape[0], w_int.shape[2]
+    O, k = w_int.shape[0], tuple(w_int.shape[2:])
     x_unf = unfold(x_int, k, padding, stride)
     B, P, K = x_unf.shape
     xs = slicing_act(x_unf, act_bits, act_bs).transpose(1, 0, 2, 3)

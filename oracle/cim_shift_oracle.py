@@ -52,7 +52,7 @@ def shift_forward(x_int, w_int, stride, padding, act_bits, act_bs, w_bits, w_bs,
     x_int = np.asarray(x_int, F32)
     w_int = np.asarray(w_int, F32)
     nbw, nba = int(w_bits / w_bs), int(act_bits / act_bs)
-    O, C, k = w_int.shape[0], w_int.shape[1], w_int.shape[2]
+    O, C, k = w_int.shape[0], w_int.shape[1], tuple(w_int.shape[2:])
     qn, qp = adc_range_shift(adc_bits)
     x_unf = co.unfold(x_int, k, padding, stride)                           # :379
     B, P, K = x_unf.shape
@@ -135,7 +135,7 @@ def shift_backward(ctx: ShiftCtx, grad_out, absolute=False):
     for i in range(1, nbw):
         gw[i] = gw[i] / dt((2 ** m["w_bs"]) ** i)
     gw = gw.mean(axis=0, dtype=dt)                                          # :527
-    gw = np.ascontiguousarray(gw.T).reshape(O, m["C"], m["k"], m["k"])      # :530
+    gw = np.ascontiguousarray(gw.T).reshape(O, m["C"], *m["k"])            # :530
     gi = gi.sum(axis=1)                                                     # :533
     for i in range(1, nbw):                                                 # :534-535 (bound nbw)
         gi[:, i] = gi[:, i] / dt((2 ** m["act_bs"]) ** i)

@@ -29,9 +29,21 @@ def _dev(a, dev, grad=False):
     return t.requires_grad_(True) if grad else t
 
 
+def _pair(v):
+    return (v, v) if isinstance(v, int) else tuple(v)
+
+
+def _geometry(cfg):
+    """(H, W, kh, kw, stride, padding) of a case: ``W``, ``kh`` / ``kw`` and (sh, sw) / (ph, pw) pairs in ``s`` /
+    ``p`` are optional and default to the square meaning of ``H``, ``k``, ``s``, ``p``."""
+    H = cfg["H"]
+    return (H, cfg.get("W", H), cfg.get("kh", cfg.get("k")), cfg.get("kw", cfg.get("k")), _pair(cfg["s"]),
+            _pair(cfg["p"]))
+
+
 def run_hip_function(dev, cfg, inp, backward=True):
     F = _fn()
-    st, pd = (cfg["s"], cfg["s"]), (cfg["p"], cfg["p"])
+    _, _, _, _, st, pd = _geometry(cfg)
     x = _dev(inp["x_q"], dev, True)
     w = _dev(inp["w_q"], dev, True)
     a = None if inp.get("alpha_q") is None else _dev(inp["alpha_q"], dev, True)
@@ -130,23 +142,24 @@ RANDOM_CASES = [
 
 def _random_inputs(cfg, seed):
     rng = np.random.default_rng(seed)
-    B, C, O, H, k = cfg["B"], cfg["C"], cfg["O"], cfg["H"], cfg["k"]
+    B, C, O = cfg["B"], cfg["C"], cfg["O"]
+    H, W, kh, kw, st, pd = _geometry(cfg)
     qp_a = 2 ** cfg["ab"] - 1
     qn_w, qp_w = co.lsq_weight_params(cfg["wb"])
     sa = np.array([cfg.get("sa", rng.uniform(0.05, 0.4))], np.float32)
     sw = np.array([cfg.get("sw", rng.uniform(0.01, 0.3))], np.float32)
-    r = rng.integers(0, qp_a + 1, size=(B, C, H, H)).astype(np.float32)
+    r = rng.integers(0, qp_a + 1, size=(B, C, H, W)).astype(np.float32)
     r[rng.random(r.shape) < 0.35] = 0
     x_q = (r * sa).astype(np.float32)
-    w_q = (rng.integers(qn_w, qp_w + 1, size=(O, C, k, k)).astype(np.float32) * sw).astype(np.float32)
+    w_q = (rng.integers(qn_w, qp_w + 1, size=(O, C, kh, kw)).astype(np.float32) * sw).astype(np.float32)
     nbw, nba = cfg["wb"] // cfg["wbs"], cfg["ab"] // cfg["abs"]
-    T = math.ceil(C * k * k / cfg["xbar"])
+    T = math.ceil(C * kh * kw / cfg["xbar"])
     alpha_q = None
     if cfg["adc"] in (1, 1.5):
         a = (rng.random((1, T, nbw, nba, 1, O)) * 4 + 0.2).astype(np.float32) * np.float32(sw[0] * sa[0])
         alpha_q = co.alpha_quantize(a, 8)
-    ho = co.out_size(H, k, cfg["p"], cfg["s"])
-    g = rng.standard_normal((B, ho * ho, O)).astype(np.float32)
+    ho, wo = co.out_size(H, kh, pd[0], st[0]), co.out_size(W, kw, pd[1], st[1])
+    g = rng.standard_normal((B, ho * wo, O)).astype(np.float32)
     return dict(x_q=x_q, w_q=w_q, sa=sa, sw=sw, alpha_q=alpha_q, grad=g,
                 binary_mask=co.make_binary_mask(nbw, nba, cfg["wbs"], cfg["abs"]),
                 signed_act=np.array([float(cfg["signed"])], np.float32))
@@ -332,11 +345,16 @@ FULL = [
 
 @pytest.mark.parametrize("idx", range(len(FULL)))
 def test_fullsize_sampled_images_and_properties(cuda_device, idx):
+    _sampled_images_and_properties(cuda_device, FULL[idx], 9100 + idx)
+
+
+def _sampled_images_and_properties(cuda_device, cfg, seed):
+    """A batch too large for the full-batch oracle: determinism of the forward, linearity of the backward in
+    grad_out on the whole batch, and images 0 and B - 1 against the oracle."""
     F = _fn()
-    cfg = FULL[idx]
-    inp = _random_inputs(cfg, 9100 + idx)
+    inp = _random_inputs(cfg, seed)
     dev = cuda_device
-    st, pd = (cfg["s"], cfg["s"]), (cfg["p"], cfg["p"])
+    _, _, _, _, st, pd = _geometry(cfg)
 
     def run(g_np):
         x = _dev(inp["x_q"], dev, True)

@@ -69,22 +69,34 @@ def test_linear_vs_reference(cuda_device, name):
     assert abs(lin.alpha.grad.item() - float(z["ref_grad_alpha_w"][0])) <= 1e-5 * float(z["ref_abs_alpha_w"])
 
 
-@pytest.mark.parametrize("B,C,O,H,k,s,na,nw,signed", [
-    (32, 64, 64, 16, 3, 1, 4, 4, False),   # a ResNet-56 stage-3 shape, 4-bit
-    (16, 16, 32, 32, 3, 2, 8, 3, False),   # unsigned 8-bit codes: the two-MFMA split
-    (16, 3, 16, 32, 3, 1, 8, 8, True),     # signed first layer
-    (64, 128, 96, 8, 1, 1, 3, 4, False),   # 1x1
-])
-def test_act_conv_vs_oracle_larger(cuda_device, B, C, O, H, k, s, na, nw, signed):
+# (B, C, O, H, W, k, s, p, na, nw, signed): W None for H, p None for k // 2; k / s / p ints or (h, w) pairs
+_LARGER = [
+    (32, 64, 64, 16, None, 3, 1, None, 4, 4, False),   # a ResNet-56 stage-3 shape, 4-bit
+    (16, 16, 32, 32, None, 3, 2, None, 8, 3, False),   # unsigned 8-bit codes: the two-MFMA split
+    (16, 3, 16, 32, None, 3, 1, None, 8, 8, True),     # signed first layer
+    (64, 128, 96, 8, None, 1, 1, None, 3, 4, False),   # 1x1
+    (8, 16, 32, 8, 32, 3, 1, None, 4, 4, False),                # a rectangular image
+    (8, 16, 16, 9, 14, (3, 2), (2, 1), (1, 0), 4, 4, False),    # ... with a 3 x 2 kernel, stride (2, 1), pad (1, 0)
+]
+_LARGER_IDS = ["32-64-64-16-3-1-4-4-False", "16-16-32-32-3-2-8-3-False", "16-3-16-32-3-1-8-8-True",
+               "64-128-96-8-1-1-3-4-False", "rect-8x32", "rect-9x14-k3x2-s21-p10"]
+
+
+@pytest.mark.parametrize("B,C,O,H,W,k,s,p,na,nw,signed", _LARGER, ids=_LARGER_IDS)
+def test_act_conv_vs_oracle_larger(cuda_device, B, C, O, H, W, k, s, p, na, nw, signed):
     from cim_quantization_amd._modules.lsq import ActLSQ, Conv2dLSQ
+    pair = lambda v: (v, v) if isinstance(v, int) else tuple(v)  # noqa: E731
+    W = H if W is None else W
+    (kh, kw), st = pair(k), pair(s)
+    pd = (kh // 2, kw // 2) if p is None else pair(p)
     g = torch.Generator().manual_seed(B * 1000 + C)
-    x = torch.randn(B, C, H, H, generator=g)
+    x = torch.randn(B, C, H, W, generator=g)
     if not signed:
         x = x.clamp_min(0)
-    w = torch.randn(O, C, k, k, generator=g) * 0.1
+    w = torch.randn(O, C, kh, kw, generator=g) * 0.1
     gout = None
     act = ActLSQ(nbits_a=na).to(cuda_device).train()
-    conv = Conv2dLSQ(C, O, k, stride=s, padding=k // 2, bias=False, nbits_w=nw).to(cuda_device).train()
+    conv = Conv2dLSQ(C, O, (kh, kw), stride=st, padding=pd, bias=False, nbits_w=nw).to(cuda_device).train()
     with torch.no_grad():
         conv.weight.copy_(w)
     xd = x.to(cuda_device).requires_grad_(True)
@@ -92,7 +104,7 @@ def test_act_conv_vs_oracle_larger(cuda_device, B, C, O, H, k, s, na, nw, signed
     gout = torch.randn(y.shape, generator=g)
     y.backward(gout.to(cuda_device))
     o = po.act_conv_chain(x.numpy(), act.alpha.item(), na, bool(act.signed.item()), w.numpy(), conv.alpha.item(), nw,
-                          None, (s, s), (k // 2, k // 2), gout.numpy())
+                          None, st, pd, gout.numpy())
     np.testing.assert_array_equal(y.detach().cpu().numpy(), o["y"])
     assert normwise_err(xd.grad.cpu().numpy(), o["grad_x"]) < 1e-5
     assert normwise_err(conv.weight.grad.cpu().numpy(), o["grad_weight"]) < 1e-5

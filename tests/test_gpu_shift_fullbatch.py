@@ -61,17 +61,18 @@ def _scalar_terms(x, g_xq, s, qn, qp, gscale):
     return gscale * (np.abs(g * r).sum() + np.abs(np.where(inside, g * float(s), 0) * y / float(s)).sum())
 
 
-def _build(dev, C, O, H, s, bits, B, seed, signed, shift=True):
+def _build(dev, C, O, H, s, bits, B, seed, signed, shift=True, W=None, xbar=64):
     """The MI355X module and the oracle module with identical weights and step sizes; alpha_cim from
     the reference's data-driven init (lsq.py:557-563) on a few images, spread so codes vary; beta a
-    fraction of alpha of either sign."""
+    fraction of alpha of either sign.  ``W``: the image width where it is not H; ``xbar``: the tile rows."""
     import cim_quantization_amd._modules as my_nn
     rng = np.random.default_rng(seed)
-    m = my_nn.Conv2dLSQCiM(C, O, (3, 3), (s, s), (1, 1), (1, 1), bias=False, **_kw(bits, shift=shift)).to(dev)
-    om = cmo.OracleConv2dLSQCiM(C, O, (3, 3), (s, s), (1, 1), (1, 1), bias=False, **_kw(bits, shift=shift))
+    W = H if W is None else W
+    m = my_nn.Conv2dLSQCiM(C, O, (3, 3), (s, s), (1, 1), (1, 1), bias=False, **_kw(bits, xbar, shift)).to(dev)
+    om = cmo.OracleConv2dLSQCiM(C, O, (3, 3), (s, s), (1, 1), (1, 1), bias=False, **_kw(bits, xbar, shift))
     om.debug_retain = True
     w = (rng.standard_normal((O, C, 3, 3)) * math.sqrt(2.0 / (9 * C))).astype(np.float32)
-    x = rng.standard_normal((B, C, H, H)).astype(np.float32)
+    x = rng.standard_normal((B, C, H, W)).astype(np.float32)
     if not signed:
         x = np.maximum(x, 0)
     qp_a, (qn_w, qp_w) = 2 ** bits - 1, co.lsq_weight_params(bits)
@@ -81,7 +82,7 @@ def _build(dev, C, O, H, s, bits, B, seed, signed, shift=True):
     sw0 = co.grad_scale_value(np.array([aw], np.float32), 1.0 / math.sqrt(w.size * qp_w))
     xq0, _ = co.lsq_quantize(x[:2], sa0, 0, qp_a)
     wq0, _ = co.lsq_quantize(w, sw0, qn_w, qp_w)
-    ac = co.alpha_cim_init(xq0, wq0, (s, s), (1, 1), bits, 1, bits, 1, 64, sw0, sa0, 1.5)
+    ac = co.alpha_cim_init(xq0, wq0, (s, s), (1, 1), bits, 1, bits, 1, xbar, sw0, sa0, 1.5)
     ac = (ac * (0.6 + 0.8 * rng.random(ac.shape))).astype(np.float32)
     bc = (ac * (rng.random(ac.shape) - 0.5)).astype(np.float32)
     for mod in (m, om):
@@ -97,8 +98,8 @@ def _build(dev, C, O, H, s, bits, B, seed, signed, shift=True):
             mod.signed_act.fill_(1 if signed else 0)
         mod._state_cache = None
         mod.train()
-    ho = (H + 2 - 3) // s + 1
-    g = (rng.standard_normal((B, O, ho, ho)) / math.sqrt(B * O * ho * ho)).astype(np.float32)
+    ho, wo = (H + 2 - 3) // s + 1, (W + 2 - 3) // s + 1
+    g = (rng.standard_normal((B, O, ho, wo)) / math.sqrt(B * O * ho * wo)).astype(np.float32)
     return m, om, x, w, g, qp_a, qn_w, qp_w
 
 
@@ -114,8 +115,8 @@ def _run(m, x, g, dev):
                 gaa=m.alpha_act.grad.clone(), gaw=m.alpha_weight.grad.clone())
 
 
-def _check(dev, monkeypatch, C, O, H, s, bits, B, seed, signed, repeat=True, shift=True):
-    m, om, x, w, g, qp_a, qn_w, qp_w = _build(dev, C, O, H, s, bits, B, seed, signed, shift)
+def _check(dev, monkeypatch, C, O, H, s, bits, B, seed, signed, repeat=True, shift=True, W=None, xbar=64):
+    m, om, x, w, g, qp_a, qn_w, qp_w = _build(dev, C, O, H, s, bits, B, seed, signed, shift, W, xbar)
     r1 = _run(m, x, g, dev)
     if repeat:
         r2 = _run(m, x, g, dev)
@@ -126,12 +127,12 @@ def _check(dev, monkeypatch, C, O, H, s, bits, B, seed, signed, repeat=True, shi
     oout = om(ox)
     oout.backward(torch.from_numpy(g))
     c = box["c"]
-    ho = g.shape[-1]
-    g_bpo = np.ascontiguousarray(g.reshape(B, O, ho * ho).transpose(0, 2, 1))
+    ho, wo = g.shape[-2:]
+    g_bpo = np.ascontiguousarray(g.reshape(B, O, ho * wo).transpose(0, 2, 1))
     terms = co.cim_backward(c, g_bpo, absolute=True)
     ax, aw, aa = terms[:3]
     bm = np.abs(om.binary_mask.numpy().astype(np.float64))
-    out_terms = (np.abs(c.adc.astype(np.float64)) * bm).sum(axis=(1, 2, 3)).transpose(0, 2, 1).reshape(B, O, ho, ho)
+    out_terms = (np.abs(c.adc.astype(np.float64)) * bm).sum(axis=(1, 2, 3)).transpose(0, 2, 1).reshape(B, O, ho, wo)
     np_ = lambda t: t.detach().cpu().numpy()  # noqa: E731
     assert rel_err(np_(r1["out"]), np_(oout), out_terms) < 1e-6, "out"
     assert rel_err(np_(r1["gx"]), np_(ox.grad), ax) < 1e-5, "grad_x"
