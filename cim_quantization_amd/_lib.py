@@ -14,6 +14,7 @@ import threading
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CIMQ_LIB_PATH") or os.path.join(_HERE, "libcimq.so")
 ABI_VERSION = 16
+ABI_MINOR = 1  # CIMQ_ABI_MINOR: activation codes (cimq_act_codes, cimq_module_forward_codes)
 
 CIMQ_EINVAL = 1  # include/cimq.h error codes
 CIMQ_EUNSUPPORTED = 2
@@ -38,10 +39,12 @@ CIMQ_ADC_F_SHIFT_RANGE = 0x200
 CIMQ_OPT_RECOMPUTE = 1  # cimq_conv_desc.options (ABI 14)
 CIMQ_OPT_INFERENCE = 4  # forward only: nothing written that a backward would read (ABI 15; bit 2 is refused)
 CIMQ_EPI_RELU = 1  # cimq_epilogue.flags (ABI 16)
+CIMQ_CODES_NO_FLOAT = 1  # cimq_act_codes.flags (ABI 16, minor 1)
 
 # every symbol include/cimq.h declares
 EXPORTED_SYMBOLS = (
     "cimq_abi_version",
+    "cimq_abi_minor",
     "cimq_last_error",
     "cimq_query_sizes",
     "cimq_forward",
@@ -59,6 +62,8 @@ EXPORTED_SYMBOLS = (
     "cimq_module_shift_forward",
     "cimq_module_shift_backward",
     "cimq_module_forward_epilogue",
+    "cimq_module_codes_supported",
+    "cimq_module_forward_codes",
     "cimq_alpha_init",
     "cimq_shift_forward",
     "cimq_shift_backward",
@@ -121,6 +126,14 @@ class Epilogue(ctypes.Structure):
                 ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class ActCodes(ctypes.Structure):
+    """Mirror of ``cimq_act_codes`` (ABI 16, minor 1)."""
+
+    _fields_ = [("x_codes", ctypes.c_void_p), ("out_codes", ctypes.c_void_p), ("out_alpha_act", ctypes.c_void_p),
+                ("out_gscale_a", ctypes.c_float), ("out_qp", ctypes.c_float), ("flags", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
 class QConvDesc(ctypes.Structure):
     """Mirror of ``cimq_qconv_desc``."""
 
@@ -170,6 +183,8 @@ class CimqError(RuntimeError):
 def _bind(lib):
     lib.cimq_abi_version.restype = ctypes.c_int
     lib.cimq_abi_version.argtypes = []
+    lib.cimq_abi_minor.restype = ctypes.c_int
+    lib.cimq_abi_minor.argtypes = []
     lib.cimq_last_error.restype = ctypes.c_char_p
     lib.cimq_last_error.argtypes = []
     lib.cimq_query_sizes.restype = ctypes.c_int
@@ -206,6 +221,13 @@ def _bind(lib):
     lib.cimq_module_forward_epilogue.restype = ctypes.c_int
     lib.cimq_module_forward_epilogue.argtypes = ([ctypes.POINTER(ConvDesc), ctypes.POINTER(LsqDesc)] + [_VP] * 8 +
                                                  [ctypes.POINTER(Epilogue)] + [_VP] * 4)
+    lib.cimq_module_codes_supported.restype = ctypes.c_int
+    lib.cimq_module_codes_supported.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_int),
+                                                ctypes.POINTER(ctypes.c_int)]
+    lib.cimq_module_forward_codes.restype = ctypes.c_int
+    lib.cimq_module_forward_codes.argtypes = ([ctypes.POINTER(ConvDesc), ctypes.POINTER(LsqDesc),
+                                               ctypes.POINTER(ActCodes)] + [_VP] * 8 +
+                                              [ctypes.POINTER(Epilogue)] + [_VP] * 4)
     lib.cimq_alpha_init.restype = ctypes.c_int
     lib.cimq_alpha_init.argtypes = [ctypes.POINTER(ConvDesc)] + [_VP] * 10
     lib.cimq_shift_forward.restype = ctypes.c_int
@@ -307,6 +329,25 @@ def make_epilogue(scale, shift, residual=None, relu=False) -> Epilogue:
     e.flags = CIMQ_EPI_RELU if relu else 0
     e.reserved = 0
     return e
+
+
+def make_act_codes(x_codes=None, out_codes=None, out_alpha_act=None, out_gscale_a=0.0, out_qp=0.0,
+                   no_float=False) -> ActCodes:
+    """``x_codes`` / ``out_codes`` / ``out_alpha_act``: device addresses (``tensor.data_ptr()``) or None."""
+    io = ActCodes()
+    io.x_codes, io.out_codes, io.out_alpha_act = x_codes, out_codes, out_alpha_act
+    io.out_gscale_a, io.out_qp = out_gscale_a, out_qp
+    io.flags = CIMQ_CODES_NO_FLOAT if no_float else 0
+    io.reserved = 0
+    return io
+
+
+def codes_supported(desc):
+    """(in_ok, out_ok) of cimq_module_codes_supported for ``desc``."""
+    a, b = ctypes.c_int(0), ctypes.c_int(0)
+    check(load().cimq_module_codes_supported(ctypes.byref(desc), ctypes.byref(a), ctypes.byref(b)),
+          "cimq_module_codes_supported")
+    return bool(a.value), bool(b.value)
 
 
 def make_qconv_desc(B, C, H, W, O, KH, KW, stride, padding, dilation, groups, code_min, code_max,

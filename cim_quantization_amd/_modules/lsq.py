@@ -18,7 +18,7 @@ import torch
 import torch.nn.functional as F
 
 from ..functional import (alpha_cim_init, cim_conv2d_lsq, cim_conv2d_lsq_shift, cim_module_conv,  # noqa: F401
-                          cim_module_conv_epilogue, cim_module_shift_conv, get_adcless_cim_output, get_analog_partial_sums_autograd_ver2,
+                          act_codes_of, cim_module_conv_codes, cim_module_conv_epilogue, cim_module_shift_conv, get_adcless_cim_output, get_analog_partial_sums_autograd_ver2,
                           get_cim_output_signed, inference_call, inference_weights, lsq_quantize,
                           module_shift_supported, qconv2d)
 from ._quan_base import (_ActQ, _Conv2dQ, _Conv2dQCiM, _LinearQ, Qmodes, grad_scale,  # noqa: F401
@@ -209,13 +209,58 @@ class Conv2dLSQCiM(_Conv2dQCiM):
             return False
         return self._shift_fused(x) if self.adc_shift else True
 
-    def forward_fused(self, x, scale, shift, residual=None, relu=False):
+    def _code_quant(self, numel):
+        """(alpha_act, gscale_a, Qp) of this layer's activation quantiser for an input of ``numel`` elements: what
+        a producer needs to write this layer's codes (cim_module_conv_codes' ``out_quant``)."""
+        qp_a = float(_act_range(self.nbits_a)[1])
+        return self.alpha_act, 1.0 / math.sqrt(numel * qp_a), qp_a
+
+    def act_codes(self, y):
+        """The activation codes of an fp32 tensor ``y`` entering this layer, in torch (the twin of the codes
+        libcimq writes and reads, include/cimq.h cimq_act_codes): ``rint(clamp(y / sa, 0, Qp))`` as uint8 with
+        sa the step size ``forward`` computes for an input of y's size, and Qp + 1 where y is NaN.  Computed on
+        y's device; move y to the host first where the division must be IEEE."""
+        return act_codes_of(y, *self._code_quant(y.numel()))
+
+    def _codes_desc(self, shape):
+        key = tuple(shape)
+        hit = getattr(self, "_codes_ok", None)
+        if hit is None or hit[0] != key:
+            from .. import _lib
+            from ..functional import _module_descs, _shift_module_descs
+            # (a query of the route alone: never the stochastic form, which would draw a seed)
+            if self.adc_shift:
+                desc, _ = _shift_module_descs(key, self.weight, self.stride, self.padding, self.dilation, self.nbits_a,
+                                              self.abitslice, self.nbits_w, self.wbitslice, self.xbar, self.nbits_alpha)
+            else:
+                desc, _ = _module_descs(key, self.weight, self.stride, self.padding, self.dilation, self.nbits_a,
+                                        self.abitslice, self.nbits_w, self.wbitslice, self.adcbits, self.xbar,
+                                        self.nbits_alpha, self.alpha_cim is not None, False, self.recompute_psum, True)
+            desc.options |= _lib.CIMQ_OPT_INFERENCE
+            hit = self._codes_ok = (key, _lib.codes_supported(desc))
+        return hit[1]
+
+    def codes_ready(self, x):
+        """``(in_ok, out_ok)``: whether ``forward_fused`` takes this layer's input ``x`` as codes (a
+        ``torch.uint8`` x), and whether it can write its output as codes (``out_quant``) -- ``fused_epilogue_ready``
+        and what cimq_module_codes_supported answers for x's shape (cached per shape).  ``x``: the input as fp32
+        or as codes; only its shape and device matter."""
+        if not self.fused_epilogue_ready(x):
+            return False, False
+        return self._codes_desc(x.shape)
+
+    def forward_fused(self, x, scale, shift, residual=None, relu=False, *, out_quant=None, keep_float=True):
         """Evaluation only: ``forward(x)`` with a per-channel affine (a folded BatchNorm: ``scale``, ``shift``,
         [out_channels] fp32), an optional ``residual`` (the output's shape; made contiguous fp32 if it is not) and an
         optional ReLU applied in the forward kernel's registers before the store -- bit for bit
         ``relu(forward(x) * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1) + residual)`` in that order of
         operations (cim_module_conv_epilogue).  Uses the kept inference weight side exactly as ``forward`` does.
-        Raises where ``fused_epilogue_ready`` does not hold, or if the call could be differentiated."""
+        Raises where ``fused_epilogue_ready`` does not hold, or if the call could be differentiated.
+        Activation codes (cim_module_conv_codes; without them the call is the one above, unchanged): a
+        ``torch.uint8`` ``x`` is this layer's input as codes (``act_codes``), and the output is bit for bit that of
+        any fp32 input with those codes; ``out_quant=next_conv`` also returns the output's codes for that layer,
+        written by the kernel that stores the output -- ``(output, codes)``, or with ``keep_float=False`` the codes
+        alone.  ``codes_ready`` says which of the two this layer supports."""
         if not self.fused_epilogue_ready(x):
             raise RuntimeError("Conv2dLSQCiM.forward_fused needs the steady-state library path (both first-step "
                                "initialisations done, adcbits != 0, ROCm tensors) and bias=None")
@@ -226,12 +271,26 @@ class Conv2dLSQCiM(_Conv2dQCiM):
             self._last_x_shape = tuple(x.shape)
             if not torch.is_grad_enabled() and not self.stochastic_quant:
                 wprep = self._inf_prep = inference_weights(self, x.shape, self._inf_prep)
-        return cim_module_conv_epilogue(
+        if x.dtype != torch.uint8 and out_quant is None:
+            if not keep_float:
+                raise ValueError("Conv2dLSQCiM.forward_fused: keep_float=False needs out_quant")
+            return cim_module_conv_epilogue(
+                x, self.weight, self.alpha_act, self.alpha_weight, self.alpha_cim, self.binary_mask, self.signed_act,
+                self.stride, self.padding, self.dilation, self.nbits_a, self.abitslice, self.nbits_w, self.wbitslice,
+                self.adcbits, self.xbar, self.nbits_alpha, scale, shift, residual=residual, relu=relu,
+                beta_cim=self.beta_cim if self.adc_shift else None, stochastic=bool(self.stochastic_quant),
+                wprep=wprep, recompute=self.recompute_psum)
+        oq = None
+        if out_quant is not None:
+            ho = (x.shape[-2] - self.weight.shape[-2] + 2 * self.padding[0]) // self.stride[0] + 1
+            wo = (x.shape[-1] - self.weight.shape[-1] + 2 * self.padding[1]) // self.stride[1] + 1
+            oq = out_quant._code_quant(x.shape[0] * self.out_channels * ho * wo)
+        return cim_module_conv_codes(
             x, self.weight, self.alpha_act, self.alpha_weight, self.alpha_cim, self.binary_mask, self.signed_act,
             self.stride, self.padding, self.dilation, self.nbits_a, self.abitslice, self.nbits_w, self.wbitslice,
             self.adcbits, self.xbar, self.nbits_alpha, scale, shift, residual=residual, relu=relu,
             beta_cim=self.beta_cim if self.adc_shift else None, stochastic=bool(self.stochastic_quant), wprep=wprep,
-            recompute=self.recompute_psum)
+            recompute=self.recompute_psum, out_quant=oq, keep_float=keep_float)
 
 
 class _HostFlags:

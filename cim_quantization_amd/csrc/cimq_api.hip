@@ -143,6 +143,7 @@ int launch_reduce_slab(const Geo& g, const uint8_t* ctx, uint8_t* ws, size_t sla
 extern "C" {
 
 int cimq_abi_version(void) { return CIMQ_ABI_VERSION; }
+int cimq_abi_minor(void) { return CIMQ_ABI_MINOR; }
 
 const char* cimq_last_error(void) { return g_last_error.c_str(); }
 
@@ -563,6 +564,27 @@ static int check_alpha(const Geo& g, LsqArgs* la, const float* alpha_cim, const 
   return CIMQ_OK;
 }
 
+// The host refusals of an output epilogue that need no geometry, shared by cimq_module_forward_epilogue and
+// cimq_module_forward_codes (who: the entry point's name in the message)
+static const char who_epi[] = "cimq_module_forward_epilogue";
+static int check_forward_only(const char* who, const cimq_conv_desc* d) {
+  if (d && !(d->options & CIMQ_OPT_INFERENCE))
+    return fail(CIMQ_EINVAL, "%s: a CIMQ_OPT_INFERENCE descriptor only (forward only)", who);
+  return CIMQ_OK;
+}
+static int check_epilogue(const char* who, const cimq_epilogue* epi, const float* alpha_cim, const float* beta_cim) {
+  if (!epi || !epi->scale || !epi->shift) return fail(CIMQ_EINVAL, "%s: null epilogue, scale or shift", who);
+  if (epi->flags & ~CIMQ_EPI_RELU) return fail(CIMQ_EINVAL, "%s: unknown flags 0x%x", who, epi->flags);
+  if (epi->reserved != 0) return fail(CIMQ_EINVAL, "%s: reserved must be 0", who);
+  if (reinterpret_cast<uintptr_t>(epi->residual) % 16 != 0)
+    return fail(CIMQ_EINVAL, "%s: residual must be 16-byte aligned", who);
+  if (beta_cim && !alpha_cim) return fail(CIMQ_EINVAL, "%s: beta_cim needs alpha_cim", who);
+  return CIMQ_OK;
+}
+
+// a clamp maximum that codes can carry: an integer in [1, 254], so that the NaN code Qp + 1 fits a byte
+static bool codes_qp_ok(float qp) { return qp >= 1.f && qp <= 254.f && qp == (float)(int)qp; }
+
 static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* x, const float* weight,
                                const float* alpha_act, const float* alpha_weight, const float* alpha_cim,
                                const float* beta_cim, const int8_t* binary_mask, const float* signed_act, float* out,
@@ -579,7 +601,30 @@ static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
         return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: residual overlaps out");
     }
   }
-  if (!x || !weight || !alpha_act || !alpha_weight || !binary_mask || !signed_act || !out || !ctx || !ws)
+  const uint8_t* xq = ep ? ep->xq : nullptr;  // cimq_module_forward_codes: the input as codes, x ignored
+  uint8_t* oq = ep ? ep->oq : nullptr;        // ... the output's codes; with nofloat, out is not written
+  if (xq || oq) {
+    const Route rc = route_of(g);
+    if (xq && !codes_qp_ok(g.lsq_qp))
+      return fail(CIMQ_EUNSUPPORTED, "cimq_module_forward_codes: x_codes needs an integer lsq_qp in [1, 254] (it is %g)",
+                  (double)g.lsq_qp);
+    if (oq && rc.fwd == CIMQ_ROUTE_DENSE)
+      return fail(CIMQ_EUNSUPPORTED, "cimq_module_forward_codes: the dense route writes no out_codes "
+                                     "(cimq_module_codes_supported)");
+    if (oq) {  // out_codes against every other buffer of the call whose extent the geometry gives
+      const uintptr_t q0 = reinterpret_cast<uintptr_t>(oq), qn = (uintptr_t)g.M * g.O;
+      auto hits = [&](const void* p, uintptr_t nb) {
+        const uintptr_t p0 = reinterpret_cast<uintptr_t>(p);
+        return p && p0 < q0 + qn && q0 < p0 + nb;
+      };
+      if (hits(out, qn * 4)) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: out_codes overlaps out");
+      if (hits(xq, (uintptr_t)g.Nin)) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: out_codes overlaps x_codes");
+      if (!xq && hits(x, (uintptr_t)g.Nin * 4)) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: out_codes overlaps x");
+      if (hits(ep->res, qn * 4)) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: out_codes overlaps the residual");
+    }
+  }
+  if ((!x && !xq) || !weight || !alpha_act || !alpha_weight || !binary_mask || !signed_act ||
+      (!out && !(ep && ep->nofloat)) || !ctx || !ws)
     return fail(CIMQ_EINVAL, "null pointer argument");
   CIMQ_TRY(check_alpha(g, &la, alpha_cim, nullptr, false));
   const bool has_alpha = la.nbits_alpha > 0;
@@ -609,7 +654,9 @@ static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
       aw.amm = part;
       aw.namm = 64;
     }
-    if (g.inference)
+    if (xq)  // (forward only; off the staging-quantiser routes, whose a.nact_blocks is 0: the bytes become slice words here)
+      hipLaunchKernelGGL(prep_module_fwd_codes_kernel, dim3(a.nact_blocks + nwblk), dim3(256), 0, s, g, la, aw, xq);
+    else if (g.inference)
       hipLaunchKernelGGL(prep_module_fwd_kernel, dim3(a.nact_blocks + nwblk), dim3(256), 0, s, g, la, aw);
     else
       hipLaunchKernelGGL(prep_module_kernel, dim3(a.nact_blocks + nwblk), dim3(256), 0, s, g, la, aw);
@@ -619,6 +666,14 @@ static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
   }
 prepared:
   const ActQ aq{x, signed_act};
+  // (input codes reach the forward kernel only where its own staging reads them: elsewhere the prologue above has
+  // turned them into slice words)
+  Epi epk;
+  if (ep && xq && !r.actq) {
+    epk = *ep;
+    epk.xq = nullptr;
+    ep = &epk;
+  }
   // (the fast forward writes NCHW, g.onchw; the dense one's P = 1: NCHW is [B, P, O])
   if (r.fwd != CIMQ_ROUTE_GENERAL)
     return launch_fwd_any(g, c, scal + 1, scal, out, nullptr, nullptr, s, r.actq ? &aq : nullptr, ep);
@@ -627,7 +682,8 @@ prepared:
   float* bpo = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(ws) + W.bpo);
   CIMQ_TRY(launch_fwd_any(g, c, scal + 1, scal, bpo, nullptr, nullptr, s));
   const dim3 tgrid(std::min(cdiv((long long)g.M * g.O, 256), 8192));
-  if (ep) hipLaunchKernelGGL(bpo_to_nchw_epi_kernel, tgrid, dim3(256), 0, s, g, bpo, out, *ep);
+  if (ep && oq) hipLaunchKernelGGL(bpo_to_nchw_codes_kernel, tgrid, dim3(256), 0, s, g, bpo, out, *ep);
+  else if (ep) hipLaunchKernelGGL(bpo_to_nchw_epi_kernel, tgrid, dim3(256), 0, s, g, bpo, out, *ep);
   else hipLaunchKernelGGL(bpo_to_nchw_kernel, tgrid, dim3(256), 0, s, g, bpo, out);
   return check_hip("bpo_to_nchw");
 }
@@ -675,16 +731,59 @@ int cimq_module_forward_epilogue(const cimq_conv_desc* d, const cimq_lsq_desc* q
                                  const float* signed_act, const cimq_epilogue* epi, float* out, void* ctx, void* ws,
                                  void* stream) {
   // (the descriptor-independent refusals first, before any other argument is looked at)
-  if (d && !(d->options & CIMQ_OPT_INFERENCE))
-    return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: a CIMQ_OPT_INFERENCE descriptor only (forward only)");
-  if (!epi || !epi->scale || !epi->shift)
-    return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: null epilogue, scale or shift");
-  if (epi->flags & ~CIMQ_EPI_RELU) return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: unknown flags 0x%x", epi->flags);
-  if (epi->reserved != 0) return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: reserved must be 0");
-  if (reinterpret_cast<uintptr_t>(epi->residual) % 16 != 0)
-    return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: residual must be 16-byte aligned");
-  if (beta_cim && !alpha_cim) return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: beta_cim needs alpha_cim");
+  CIMQ_TRY(check_forward_only(who_epi, d));
+  CIMQ_TRY(check_epilogue(who_epi, epi, alpha_cim, beta_cim));
   const Epi ep{epi->scale, epi->shift, epi->residual, (epi->flags & CIMQ_EPI_RELU) ? 1 : 0};
+  return module_forward_impl(d, q, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act,
+                             out, ctx, ws, stream, &ep);
+}
+
+int cimq_module_codes_supported(const cimq_conv_desc* d, int* in_ok, int* out_ok) {
+  if (!d) return fail(CIMQ_EINVAL, "null descriptor");
+  cimq_conv_desc di = *d;  // (the call takes forward-only descriptors alone: answer for that form)
+  di.options |= CIMQ_OPT_INFERENCE;
+  Geo g;
+  CIMQ_TRY(make_geo(&di, &g));
+  if (g.input_kind != CIMQ_INPUT_RAW_LSQ) return fail(CIMQ_EINVAL, "module entry points take the raw activation");
+  g = module_form(g);
+  const int fwd = route_of(g).fwd;
+  if (in_ok) *in_ok = codes_qp_ok(g.lsq_qp) ? 1 : 0;
+  if (out_ok) *out_ok = (fwd == CIMQ_ROUTE_FWD5 || fwd == CIMQ_ROUTE_V3 || fwd == CIMQ_ROUTE_GENERAL) ? 1 : 0;
+  return CIMQ_OK;
+}
+
+int cimq_module_forward_codes(const cimq_conv_desc* d, const cimq_lsq_desc* q, const cimq_act_codes* io,
+                              const float* x, const float* weight, const float* alpha_act,
+                              const float* alpha_weight, const float* alpha_cim, const float* beta_cim,
+                              const int8_t* binary_mask, const float* signed_act, const cimq_epilogue* epi,
+                              float* out, void* ctx, void* ws, void* stream) {
+  // (the descriptor-independent refusals first; the epilogue's are cimq_module_forward_epilogue's own)
+  static const char who[] = "cimq_module_forward_codes";
+  CIMQ_TRY(check_forward_only(who, d));
+  if (!io) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: null io");
+  CIMQ_TRY(check_epilogue(who, epi, alpha_cim, beta_cim));
+  if (io->flags & ~CIMQ_CODES_NO_FLOAT) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: unknown flags 0x%x", io->flags);
+  if (io->reserved != 0) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: reserved must be 0");
+  if (!io->x_codes && !io->out_codes && !io->flags)
+    return cimq_module_forward_epilogue(d, q, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask,
+                                        signed_act, epi, out, ctx, ws, stream);
+  if ((io->flags & CIMQ_CODES_NO_FLOAT) && !io->out_codes)
+    return fail(CIMQ_EINVAL, "cimq_module_forward_codes: CIMQ_CODES_NO_FLOAT needs out_codes");
+  if (io->out_codes) {
+    if (!io->out_alpha_act) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: out_codes needs out_alpha_act");
+    if (!codes_qp_ok(io->out_qp))
+      return fail(CIMQ_EINVAL, "cimq_module_forward_codes: out_qp must be an integer in [1, 254] (it is %g)",
+                  (double)io->out_qp);
+  }
+  if (reinterpret_cast<uintptr_t>(io->x_codes) % 16 != 0 || reinterpret_cast<uintptr_t>(io->out_codes) % 16 != 0)
+    return fail(CIMQ_EINVAL, "cimq_module_forward_codes: code buffers must be 16-byte aligned");
+  Epi ep{epi->scale, epi->shift, epi->residual, (epi->flags & CIMQ_EPI_RELU) ? 1 : 0};
+  ep.nofloat = (io->flags & CIMQ_CODES_NO_FLOAT) ? 1 : 0;
+  ep.xq = io->x_codes;
+  ep.oq = io->out_codes;
+  ep.oalpha = io->out_alpha_act;
+  ep.ogs = io->out_gscale_a;
+  ep.oqp = io->out_qp;
   return module_forward_impl(d, q, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act,
                              out, ctx, ws, stream, &ep);
 }

@@ -89,6 +89,28 @@ __device__ inline float grad_scale_value(float x, float s) {
   return d + yg;
 }
 
+// The activation code of a value entering a layer with step size sa and clamp maximum qp (an integer, <= 254):
+// the quantiser's own chain (act_words_tab) -- one IEEE division, the clamp, rint -- and qp + 1 for a NaN.
+__device__ inline uint32_t act_code(float y, float sa, float qp) {
+  const float r = rintf(clamp_nan(y / sa, 0.f, qp));
+  return (r == r) ? (uint32_t)(int)r : (uint32_t)(int)qp + 1u;
+}
+// the codes of the float4 a lane stores, one byte per pixel, lowest byte first: one 32-bit store at oq + idx
+__device__ inline uint32_t act_code4(const float4& y, float sa, float qp) {
+  return act_code(y.x, sa, qp) | (act_code(y.y, sa, qp) << 8) | (act_code(y.z, sa, qp) << 16) |
+         (act_code(y.w, sa, qp) << 24);
+}
+// The store of a code instance (cimq_module_forward_codes): the float4 y at out + idx unless
+// CIMQ_CODES_NO_FLOAT, and with ep.oq the codes of y for the consumer layer, one 32-bit store at oq + idx.
+// The consumer's step size is the module prologue's own expression on its parameter (grad_scale_value).
+__device__ inline void store_codes4(const Epi& ep, float* __restrict__ out, size_t idx, const float4& y) {
+  if (!ep.nofloat) *reinterpret_cast<float4*>(out + idx) = y;
+  if (ep.oq) {
+    const float osa = grad_scale_value(ep.oalpha[0], ep.ogs);
+    *reinterpret_cast<uint32_t*>(ep.oq + idx) = act_code4(y, osa, ep.oqp);
+  }
+}
+
 // round_pass(v) forward value: (v.round() - v).detach() + v  (lsq.py:29-32)
 __device__ inline float round_pass_value(float v) {
   const float r = rintf(v);

@@ -31,13 +31,20 @@ namespace cimq {
 // cim_bwd_r6_kernel: the forward then writes only `out`, and its ADC epilogue skips the state-bit shifts)
 // EPI (forward only, with WST false): the output epilogue ep on the float4 about to be stored (epi_val4); the other
 // instances never read ep
-template <int NOB, bool WST, bool EPI = false>
-__global__ __attribute__((amdgpu_flat_work_group_size(512 * NOB, 512 * NOB), amdgpu_waves_per_eu(4, 4))) void cim_fwd5_kernel(
+// NOBA: NOB = NOBA & 3; NOBA 4 + NOB (with EPI) is the code instance of cimq_module_forward_codes -- the staging
+// reads the input's codes (ep.xq: one byte per element, straight into the word table, no division) or fp32 x, and
+// the store writes the float4, the consumer's codes (ep.oq) or both: block-uniform branches on ep.  Encoded in
+// NOBA so that the other instances keep their symbols and their code.
+template <int NOBA, bool WST, bool EPI = false>
+__global__ __attribute__((amdgpu_flat_work_group_size(512 * (NOBA & 3), 512 * (NOBA & 3)), amdgpu_waves_per_eu(4, 4))) void cim_fwd5_kernel(
     Geo g, F5 v, const v4i* __restrict__ wf5, Params pp, const float* __restrict__ sw_p,
     const float* __restrict__ sa_p, const float* __restrict__ x, const float* __restrict__ sgn_p,
     float* __restrict__ out, uint32_t* __restrict__ st, uint32_t* __restrict__ xcb, uint32_t* __restrict__ cal,
     Epi ep) {
+  constexpr int NOB = NOBA & 3;
+  constexpr bool COD = NOBA >= 4;
   static_assert(!(EPI && WST), "the epilogue instances are forward only");
+  static_assert(!COD || EPI, "the code instances carry the epilogue");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int obl = wave >> 3, pw = wave & 7;  // this wave's output block within the block, its pixel group
@@ -137,10 +144,16 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512 * NOB, 512 * NOB), amd
       // as exact float-reciprocal quotients, and every item's decomposition computed once)
       constexpr int SU = NOB == 2 ? 3 : 2;
       constexpr int NT = 512 * NOB;
-      const int n = v.IPM * v.RH * QC * g.W;
+      // (code input, COD: an item is 4 channels x 4 columns -- one 32-bit load of four column bytes per channel --
+      // so a round stages four times the elements with the same number of loads)
+      const uint8_t* xq = nullptr;
+      if constexpr (COD) xq = ep.xq;
+      const bool cin = COD && xq != nullptr;  // uniform
+      const int wsh = cin ? 2 : 0;            // columns per item, as a shift
+      const int n = v.IPM * v.RH * QC * (g.W >> wsh);
       const float invQC = 1.f / (float)QC, invRH = 1.f / (float)v.RH;
       const int xbase = (b0 * g.C + 16 * cb0) * HWi + ih0 * g.W;  // element (image b0, channel 16 cb0, row ih0, col 0)
-      float xv[SU][4];
+      float xv[SU][4];  // (code input: the bits of channel e's 32-bit word, column c in byte c)
       int dsto[SU], xo[SU], ihs[SU], qqs[SU];
       auto ldx = [&](int base) {
 #pragma unroll
@@ -150,7 +163,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512 * NOB, 512 * NOB), amd
 #pragma unroll
           for (int e = 0; e < 4; ++e) xv[u][e] = 0.f;
           if (idx < n) {
-            const int col = idx & (g.W - 1), r1 = idx >> v.lwi;
+            const int col = (idx & ((g.W >> wsh) - 1)) << wsh, r1 = idx >> (v.lwi - wsh);
             const int r2 = sdiv(r1, invQC), qq = r1 - r2 * QC;
             const int sl = sdiv(r2, invRH), row = r2 - sl * v.RH;
             ihs[u] = ih0 + row;
@@ -158,8 +171,14 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512 * NOB, 512 * NOB), amd
             dsto[u] = sl * IMGB + f5_off(v.NCBP, v.WP, row, qq >> 2, col + 1) + 4 * (qq & 3);
             xo[u] = xbase + (sl * g.C + 4 * qq) * HWi + row * g.W + col;
             if ((unsigned)ihs[u] < (unsigned)g.H) {
+              if (cin) {
 #pragma unroll
-              for (int e = 0; e < 4; ++e) xv[u][e] = x[xo[u] + e * HWi];
+                for (int e = 0; e < 4; ++e)
+                  xv[u][e] = __uint_as_float(reinterpret_cast<const uint32_t*>(xq)[(xo[u] + e * HWi) >> 2]);
+              } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) xv[u][e] = x[xo[u] + e * HWi];
+              }
             }
           }
         }
@@ -170,6 +189,21 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512 * NOB, 512 * NOB), amd
           if (dsto[u] < 0) continue;
           uint32_t* dst = reinterpret_cast<uint32_t*>(patch + dsto[u]);
           const int ih = ihs[u];
+          if (cin) {
+            // four columns (48 bytes apart); a byte above Qp + 1 reads the NaN entry: none can index past the table
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              uint32_t f[4] = {0u, 0u, 0u, 0u}, Q[4];
+              if ((unsigned)ih < (unsigned)g.H) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                  f[e] = alut[2 * min((int)((__float_as_uint(xv[u][e]) >> (8 * c)) & 255u), nan_e)];
+              }
+              tr4(f[0], f[1], f[2], f[3], Q);
+              dst[12 * c] = Q[0]; dst[12 * c + 4] = Q[1]; dst[12 * c + 8] = Q[2];
+            }
+            continue;
+          }
           if ((unsigned)ih >= (unsigned)g.H) {
             dst[0] = 0u; dst[4] = 0u; dst[8] = 0u;
             continue;
@@ -286,7 +320,9 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512 * NOB, 512 * NOB), amd
     if (o < g.O) {
       const int bb = m0 / g.P, pq = m0 - bb * g.P;
       const int oi = (bb * g.O + o) * g.P + pq;
-      if constexpr (EPI)
+      if constexpr (COD)
+        store_codes4(ep, out, oi, epi_val4(ep, ep.scale[o], ep.shift[o], oi, acc[0], acc[1], acc[2], acc[3]));
+      else if constexpr (EPI)
         *reinterpret_cast<float4*>(out + oi) = epi_val4(ep, ep.scale[o], ep.shift[o], oi, acc[0], acc[1], acc[2], acc[3]);
       else
         *reinterpret_cast<float4*>(out + oi) = make_float4(acc[0], acc[1], acc[2], acc[3]);

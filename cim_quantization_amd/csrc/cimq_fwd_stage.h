@@ -162,6 +162,48 @@ __device__ inline void stage_rows_q(const Geo& g, int WP, int RHx, const float* 
   }
 }
 
+// stage_rows_q for an input that arrives as activation codes (cimq_module_forward_codes; forward only, so no
+// backward words): one byte per element, [B, C, H, W], four columns per 32-bit load, each byte straight into the
+// word table -- no division, clamp or rint.  A byte above Qp + 1 reads the NaN entry: none indexes past the table.
+__device__ inline void stage_rows_qc(const Geo& g, int WP, int RHx, const uint8_t* __restrict__ xq,
+                                     const uint32_t* lut, int b, int ih_first, uint8_t* patch) {
+  const int nan_e = (int)g.lsq_qp + 1;
+  const int QW = g.W >> 2;  // 4-element items per row (W % 4 == 0)
+  const int nrow = g.C * RHx;
+  const int n = nrow * QW;
+  const bool pq = (QW & (QW - 1)) == 0;
+  const int lq = 31 - __builtin_clz(QW);
+  const float invQ = 1.f / (float)QW, invR = 1.f / (float)RHx;
+  const size_t img = (size_t)b * g.C * g.H;
+  for (int base = threadIdx.x; base < n; base += 4 * (int)blockDim.x) {
+    uint32_t v[4];
+    int d[4];
+    bool in[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int idx = base + u * (int)blockDim.x;
+      d[u] = -1;
+      v[u] = 0u;
+      in[u] = false;
+      if (idx < n) {
+        const int row = pq ? (idx >> lq) : fdiv(idx, QW, invQ), q = pq ? (idx & (QW - 1)) : idx - row * QW;
+        const int c = fdiv(row, RHx, invR);
+        const int ih = ih_first + (row - c * RHx);
+        d[u] = row * WP * 4 + g.PW * 4 + q * 16;
+        in[u] = (unsigned)ih < (unsigned)g.H;
+        if (in[u]) v[u] = reinterpret_cast<const uint32_t*>(xq)[((img + (size_t)c * g.H + ih) * g.W >> 2) + q];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      if (d[u] < 0) continue;
+      uint32_t* p = reinterpret_cast<uint32_t*>(patch + d[u]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) p[e] = in[u] ? lut[2 * min((int)((v[u] >> (8 * e)) & 255u), nan_e)] : 0u;
+    }
+  }
+}
+
 // ptab[t] (t < KS*64) for tile i: patch word offset of contraction row f = i*xbar + t relative
 // to a pixel's window origin; 0 for t outside the tile (the weight operand is zero there).
 __device__ inline void build_ptab(const Geo& g, int i, int KSx, int RHx, int WP, int* ptab, int c0 = 0) {

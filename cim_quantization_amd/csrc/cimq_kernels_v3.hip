@@ -44,8 +44,12 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
   // xin (module path, NBP 4): the activation quantiser fused into the row staging (stage_rows_q)
   // CSTA 20 + s, s one of the stateless 0 / 9 / 12 / 13 / 18: the same with the output epilogue ep on the float4
   // about to be stored (cimq_module_forward_epilogue, NCHW only); no other instance reads ep
+  // CSTA 40 + s: the code instance of CSTA 20 + s (cimq_module_forward_codes) -- the row staging reads the
+  // input's codes (ep.xq: bytes straight into the word table, stage_rows_qc) or quantises fp32 x as before, and the
+  // store writes the float4, the consumer's codes (ep.oq) or both: block-uniform branches on ep
+  constexpr bool COD = CSTA >= 40;
   constexpr bool EPI = CSTA >= 20;
-  constexpr int CSTB = EPI ? CSTA - 20 : CSTA;
+  constexpr int CSTB = COD ? CSTA - 40 : EPI ? CSTA - 20 : CSTA;
   static_assert(!EPI || CSTB == 0 || CSTB == 9 || CSTB >= 10, "the epilogue instances are forward only");
   constexpr int CST = CSTB == 9 ? 8 : CSTB >= 10 ? CSTB - 10 : CSTB;
   constexpr bool WST = CSTB < 9;
@@ -184,7 +188,9 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
   if (pfx) load_tile(0);  // in flight through the prologue and the first row staging
   if (v.fwd_res) stage_all();
   zero_lds(reinterpret_cast<uint32_t*>(patch), g.C * v.RH * v.WP * NBP / 4);
-  const bool actq = NBP == 4 && xin != nullptr;  // uniform
+  const uint8_t* xq = nullptr;
+  if constexpr (COD && NBP == 4) xq = ep.xq;
+  const bool actq = NBP == 4 && (xin != nullptr || xq != nullptr);  // uniform
   const float sa_q = actq ? *sa_p : 0.f;
   const bool sgn_q = actq && *sgn_p != 0.f;
   if (actq) act_lut_build_q<(CST == 2 || CST == 3) ? CST : 0>(g, sa_q, sgn_q, alut);  // syncs the block
@@ -207,7 +213,9 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
       // image's end for its last m-tile; one o-group's blocks write them
       const int own_lo = blockIdx.y == 0 ? oh0 * g.SH : 0;
       const int own_hi = blockIdx.y == 0 ? (p0 + 64 == g.P ? g.H : (oh0 + (64 >> v.lw)) * g.SH) : 0;
-      if constexpr (NBP == 4)
+      if (COD && xq)
+        stage_rows_qc(g, v.WP, v.RH, xq, alut, b, oh0 * g.SH - g.PH, patch);
+      else if constexpr (NBP == 4)
         stage_rows_q<!INF>(g, v.WP, v.RH, xin, sa_q, alut, b, oh0 * g.SH - g.PH, patch, xcb, own_lo, own_hi);
     } else {
       stage_rows<NBP>(g, v.WP, v.RH, xcf, b, oh0 * g.SH - g.PH, patch);
@@ -472,7 +480,12 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
           const int m4 = mt * 64 + wave * 16 + 4 * g4;  // M < 2^24 (v3_plan)
           const int bb = fdiv(m4, g.P, inv_p), pq = m4 - bb * g.P;
           const size_t oi = ((size_t)bb * g.O + o) * g.P + pq;
-          if constexpr (EPI) {
+          if constexpr (COD) {
+            int oe = o;  // (opaque, as below)
+            asm volatile("" : "+v"(oe));
+            store_codes4(ep, out, oi,
+                         epi_val4(ep, ep.scale[oe], ep.shift[oe], oi, acc[ob][0], acc[ob][1], acc[ob][2], acc[ob][3]));
+          } else if constexpr (EPI) {
             // (the table index through an opaque copy: the two 64-bit entry addresses, invariant over the m-tiles,
             // would otherwise be kept in 4 VGPRs per output block across the whole loop -- a wave per SIMD in the
             // OBM 4 instances)

@@ -186,6 +186,27 @@ __global__ __launch_bounds__(256) void prep_module_fwd_kernel(Geo g, LsqArgs q, 
   module_prep_weights(g, q, a, (int)blockIdx.x, nwblk, red);
 }
 
+// prep_module_fwd_kernel for an input that arrives as activation codes (cimq_module_forward_codes on the routes whose
+// forward reads slice words: general, dense, shift, and v3 without the fused quantiser): the activation blocks turn
+// the bytes of xq into the forward slice words (act_range_codes); the weight side is prep_module_fwd_kernel's
+__global__ __launch_bounds__(256) void prep_module_fwd_codes_kernel(Geo g, LsqArgs q, ModulePrep a,
+                                                                    const uint8_t* __restrict__ xq) {
+  __shared__ float4 red4[16];
+  float* red = reinterpret_cast<float*>(red4);
+  const int nwblk = (int)gridDim.x - a.nact_blocks;
+  if ((int)blockIdx.x >= nwblk) {
+    const float sa = grad_scale_value(a.alpha_act[0], q.gs_a);  // lsq.py:547-548
+    const int ab = (int)blockIdx.x - nwblk;
+    const bool sgn = a.signed_act[0] != 0.f;
+    __shared__ __attribute__((aligned(16))) uint32_t lut[kActLutMax * 4];  // [Qp + 2] entries of NBP / 2 words
+    const long long first = (long long)ab * blockDim.x + threadIdx.x, step = (long long)a.nact_blocks * blockDim.x;
+    if (g.NBP == 4) act_range_codes<4>(g, xq, sa, sgn, a.xcf, first, step, lut);
+    else act_range_codes<8>(g, xq, sa, sgn, a.xcf, first, step, lut);
+    return;
+  }
+  module_prep_weights(g, q, a, (int)blockIdx.x, nwblk, red);
+}
+
 // The job of block b in a packed launch: the number of job starts blk0[1 .. n-1] at or below b, counted
 // over the whole (fixed-size) table -- independent scalar loads of the kernel arguments and a compare
 // chain, instead of a search loop whose every step waits on the previous step's argument load
@@ -378,6 +399,20 @@ __global__ void bpo_to_nchw_epi_kernel(Geo g, const float* __restrict__ src, flo
     const size_t p = e % g.P, bo = e / g.P;
     const size_t o = bo % g.O, b = bo / g.O;
     dst[e] = epi_val(src[(b * g.P + p) * g.O + o], ep.scale[o], ep.shift[o], hr, hr ? ep.res[e] : 0.f, rl);
+  }
+}
+// ... and with the consumer's activation codes of the value stored, or that would be stored (the general route of
+// cimq_module_forward_codes: scalar stores, so one byte store per element)
+__global__ void bpo_to_nchw_codes_kernel(Geo g, const float* __restrict__ src, float* __restrict__ dst, Epi ep) {
+  const size_t n = (size_t)g.M * g.O;
+  const bool hr = ep.res != nullptr, rl = ep.relu != 0;
+  const float osa = ep.oq ? grad_scale_value(ep.oalpha[0], ep.ogs) : 1.f;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+    const size_t p = e % g.P, bo = e / g.P;
+    const size_t o = bo % g.O, b = bo / g.O;
+    const float y = epi_val(src[(b * g.P + p) * g.O + o], ep.scale[o], ep.shift[o], hr, hr ? ep.res[e] : 0.f, rl);
+    if (!ep.nofloat) dst[e] = y;
+    if (ep.oq) ep.oq[e] = (uint8_t)act_code(y, osa, ep.oqp);
   }
 }
 __global__ void nchw_to_bpo_kernel(Geo g, const float* __restrict__ src, float* __restrict__ dst) {

@@ -239,6 +239,54 @@ __device__ inline void act_range(const Geo& g, const float* __restrict__ x, floa
   }
 }
 
+// act_range for an input that arrives as activation codes (cimq_module_forward_codes: forward words only): the
+// element's words are the table entry of its byte -- entries 0 .. Qp as act_lut_build makes them, entry Qp + 1 the
+// words of a NaN element (act_words of any NaN: its chain is independent of the NaN's sign and payload); a byte
+// above Qp + 1 reads that entry too, so none indexes past the table.  lut: (Qp + 2) * NBP / 2 words of LDS
+// (Qp <= 254: within kActLutMax entries); called by every thread of the block.
+template <int NBP>
+__device__ inline void act_range_codes(const Geo& g, const uint8_t* __restrict__ xq, float sa, bool sgn,
+                                       uint8_t* __restrict__ xcf, long long first, long long step, uint32_t* lut) {
+  constexpr int NW = NBP / 4;
+  const int nan_e = (int)g.lsq_qp + 1;
+  if (threadIdx.x == 0) {
+    uint32_t f[NW], b[NW];
+    act_words<NBP, 0>(g, __int_as_float(0x7fc00000), sa, sgn, f, b);
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      lut[nan_e * (NBP / 2) + w] = f[w];
+      lut[nan_e * (NBP / 2) + NW + w] = b[w];
+    }
+  }
+  act_lut_build<NBP, 0>(g, sa, sgn, lut);  // entries 0 .. Qp, then the block barrier
+  uint32_t* dst = reinterpret_cast<uint32_t*>(xcf);
+  if (g.Nin % 4 == 0) {
+    const long long n4 = g.Nin / 4;
+    for (long long t = first; t < n4; t += step) {
+      const uint32_t cw = reinterpret_cast<const uint32_t*>(xq)[t];
+      uint32_t f[4][NW];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int c = min((int)((cw >> (8 * e)) & 255u), nan_e) * (NBP / 2);
+#pragma unroll
+        for (int w = 0; w < NW; ++w) f[e][w] = lut[c + w];
+      }
+      if (NBP == 4) {
+        reinterpret_cast<uint4*>(xcf)[t] = make_uint4(f[0][0], f[1][0], f[2][0], f[3][0]);
+      } else {
+        reinterpret_cast<uint4*>(xcf)[2 * t] = make_uint4(f[0][0], f[0][NW - 1], f[1][0], f[1][NW - 1]);
+        reinterpret_cast<uint4*>(xcf)[2 * t + 1] = make_uint4(f[2][0], f[2][NW - 1], f[3][0], f[3][NW - 1]);
+      }
+    }
+  } else {
+    for (long long idx = first; idx < g.Nin; idx += step) {
+      const int c = min((int)xq[idx], nan_e) * (NBP / 2);
+#pragma unroll
+      for (int w = 0; w < NW; ++w) dst[idx * NW + w] = lut[c + w];
+    }
+  }
+}
+
 // =========================================================================================
 // prep_weight: MFMA fragments of the weight bit slices
 // =========================================================================================

@@ -14,7 +14,7 @@ int launch_fwd_v3(const Geo& g, const Plan3& p, uint8_t* ctx, const float* sw, c
   // backwards read -- nbw = nba = CST (2, 3), 8 the w8a8 planes, 9 the first conv, whose backward recomputes
   // them; forward only (CIMQ_OPT_INFERENCE): the same instances without the state words, their bits and the
   // backward words (10 + CST; 0 and 9 write no state as they are); with an output epilogue (ep, forward only, NCHW)
-  // 20 + that
+  // 20 + that; with activation codes in or out as well, 40 + that
   const int cst = route_of(g).cst;
   // OBM: 16-channel output blocks per block (register arrays sized for exactly that)
   int obm = std::min(p.v.obm, g.OB16 <= 2 ? g.OB16 : 4);
@@ -29,7 +29,12 @@ int launch_fwd_v3(const Geo& g, const Plan3& p, uint8_t* ctx, const float* sw, c
   // (the instances in the order the code object has always had them: a kernel's place decides its addresses)
   if (ep) {
     if (!g.inference || !g.onchw) return fail(CIMQ_EINVAL, "internal: output epilogue off the forward-only module path");
-    if (cst == 0) kern = CIMQ_FWD3(20);
+    if (ep->xq || ep->oq) {  // activation codes in or out (cimq_module_forward_codes): the code instances, 40 + that
+      if (cst == 0) kern = CIMQ_FWD3(40);
+      else if constexpr (NBP == 8) kern = cst == 9 ? cim_fwd_v3_kernel<8, KS, 49, 1> : cim_fwd_v3_kernel<8, KS, 58, 1>;
+      else if (cst == 12) kern = obm == 1 ? cim_fwd_v3_kernel<NBP, KS, 52, 1> : cim_fwd_v3_kernel<NBP, KS, 52, 2>;
+      else kern = CIMQ_FWD3(53);
+    } else if (cst == 0) kern = CIMQ_FWD3(20);
     else if constexpr (NBP == 8) kern = cst == 9 ? cim_fwd_v3_kernel<8, KS, 29, 1> : cim_fwd_v3_kernel<8, KS, 38, 1>;
     else if (cst == 12) kern = obm == 1 ? cim_fwd_v3_kernel<NBP, KS, 32, 1> : cim_fwd_v3_kernel<NBP, KS, 32, 2>;
     else kern = CIMQ_FWD3(33);

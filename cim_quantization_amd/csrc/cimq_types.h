@@ -66,6 +66,14 @@ struct Epi {
   const float* shift;  // [O]
   const float* res;    // null, or the residual in out's layout (NCHW)
   int relu;            // CIMQ_EPI_RELU
+  // activation codes (cimq_act_codes, cimq_module_forward_codes): read by the code instances alone -- the fields
+  // follow the epilogue's, so every other instance finds its arguments where they were
+  int nofloat;           // CIMQ_CODES_NO_FLOAT: out is not written
+  const uint8_t* xq;     // null, or the input as codes ([B, C, H, W] bytes) in place of the fp32 x
+  uint8_t* oq;           // null, or where the output's codes go ([B, O, Ho, Wo] bytes)
+  const float* oalpha;   // [1]: the consumer's alpha_act
+  float ogs;             // the consumer's gradient-scale factor
+  float oqp;             // the consumer's clamp maximum, an integer in [1, 254]
 };
 
 __host__ __device__ inline int pidx(const Geo& g, int i, int j, int k, int o) {

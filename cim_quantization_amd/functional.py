@@ -854,10 +854,60 @@ def cim_module_conv_epilogue(x, weight, alpha_act, alpha_weight, alpha_cim, bina
     shift.view(1, -1, 1, 1) + residual)`` gives on cim_module_conv's output.  ``scale`` / ``shift``: [O] fp32 device
     tensors (a folded BatchNorm); ``residual``: NCHW like the output, made contiguous fp32 if it is not.  Forward
     only: a call that could be differentiated raises RuntimeError."""
+    return _conv_epilogue(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding,
+                          dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha, scale, shift,
+                          residual, relu, beta_cim, stochastic, wprep, recompute, "cim_module_conv_epilogue")
+
+
+def act_code_step(alpha_act, gscale_a):
+    """The step size ``sa`` of a layer's activation quantiser as libcimq computes it: grad_scale's forward value
+    ``(alpha_act - alpha_act * s) + alpha_act * s`` with every operation in fp32 (cimq_device.h grad_scale_value)."""
+    a = alpha_act.detach().reshape(-1)[:1].to(torch.float32)
+    yg = a * torch.tensor(gscale_a, dtype=torch.float32, device=a.device)
+    return (a - yg) + yg
+
+
+def act_codes_of(y, alpha_act, gscale_a, qp):
+    """The torch twin of libcimq's activation code (include/cimq.h, cimq_act_codes) for an fp32 tensor ``y``
+    entering a layer with step-size parameter ``alpha_act``, gradient-scale factor ``gscale_a`` and clamp maximum
+    ``qp``: ``rint(clamp(y / sa, 0, qp))`` as uint8, ``qp + 1`` where y is NaN.  Runs on y's device; a CPU's fp32
+    division is IEEE."""
+    sa = act_code_step(alpha_act, gscale_a).to(y.device)
+    r = torch.round(torch.clamp(y.to(torch.float32) / sa, 0.0, float(qp)))
+    return torch.where(torch.isnan(r), torch.full_like(r, float(qp) + 1.0), r).to(torch.uint8)
+
+
+def cim_module_conv_codes(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding,
+                          dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha, scale, shift,
+                          residual=None, relu=False, beta_cim=None, stochastic=False, wprep=None, recompute=False,
+                          out_quant=None, keep_float=True):
+    """cim_module_conv_epilogue with activations as codes on either side (cimq_module_forward_codes).  ``x``: the
+    fp32 input, or a ``torch.uint8`` tensor [B, C, H, W] of this layer's activation codes (act_codes_of with its
+    alpha_act, its gradient-scale factor and Qp = 2^nbits_a - 1) -- the output is then bit for bit that of any fp32
+    input with these codes.  ``out_quant``: None, or ``(alpha_act, gscale_a, qp)`` of the layer that consumes the
+    output; the codes of the stored values for that layer are written by the kernel that stores them.  Returns the
+    fp32 output (``out_quant`` None), ``(output, codes)``, or with ``keep_float=False`` the codes alone (the fp32
+    output is then never written).  Forward only: a call that could be differentiated raises RuntimeError."""
+    return _conv_epilogue(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding,
+                          dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha, scale, shift,
+                          residual, relu, beta_cim, stochastic, wprep, recompute, "cim_module_conv_codes",
+                          True, out_quant, keep_float)
+
+
+def _conv_epilogue(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding, dilation,
+                   nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha, scale, shift, residual, relu,
+                   beta_cim, stochastic, wprep, recompute, who, codes=False, out_quant=None, keep_float=True):
+    """The shared body of cim_module_conv_epilogue (``codes`` False: cimq_module_forward_epilogue, fp32 in and
+    out) and cim_module_conv_codes (cimq_module_forward_codes)."""
     if not inference_call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, scale, shift, residual):
-        raise RuntimeError("cim_module_conv_epilogue is forward only: call it under torch.no_grad(), or with no "
+        raise RuntimeError(f"{who} is forward only: call it under torch.no_grad(), or with no "
                            "argument that requires a gradient")
     _require_device(x)
+    x_codes = codes and x.dtype == torch.uint8
+    if not codes and (x.dtype == torch.uint8 or out_quant is not None):
+        raise ValueError(f"{who}: fp32 in and out (activation codes: cim_module_conv_codes)")
+    if out_quant is None and not keep_float:
+        raise ValueError(f"{who}: keep_float=False needs out_quant")
     dev = x.device
     B, C, H, W, O, KH, KW, st, pd = _geometry(x, weight, stride, padding, dilation)
     if beta_cim is None:
@@ -874,7 +924,7 @@ def cim_module_conv_epilogue(x, weight, alpha_act, alpha_weight, alpha_cim, bina
         keep = wprep.buf
     sizes = _lib.query_sizes(desc)
     f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-    xc, wc = f32(x), f32(weight)
+    xc, wc = (x.detach().contiguous() if x_codes else f32(x)), f32(weight)
     aa, aw = f32(alpha_act).reshape(-1)[:1].contiguous(), f32(alpha_weight).reshape(-1)[:1].contiguous()
     ac = None if alpha_cim is None else f32(alpha_cim)
     bc = None if beta_cim is None else f32(beta_cim)
@@ -882,25 +932,47 @@ def cim_module_conv_epilogue(x, weight, alpha_act, alpha_weight, alpha_cim, bina
     sg = f32(signed_act).reshape(-1)[:1].contiguous()
     sc, sh = f32(scale).reshape(-1), f32(shift).reshape(-1)
     if sc.numel() != O or sh.numel() != O:
-        raise ValueError(f"cim_module_conv_epilogue: scale / shift need {O} elements (one per output channel)")
+        raise ValueError(f"{who}: scale / shift need {O} elements (one per output channel)")
     Ho = (H + 2 * pd[0] - KH) // st[0] + 1
     Wo = (W + 2 * pd[1] - KW) // st[1] + 1
     rs = None
     if residual is not None:
         if tuple(residual.shape) != (B, O, Ho, Wo):
-            raise ValueError(f"cim_module_conv_epilogue: residual {tuple(residual.shape)} is not the output's "
+            raise ValueError(f"{who}: residual {tuple(residual.shape)} is not the output's "
                              f"{(B, O, Ho, Wo)}")
         rs = f32(residual)
-    out = torch.empty(B, O, Ho, Wo, device=dev, dtype=torch.float32)
+    out = torch.empty(B, O, Ho, Wo, device=dev, dtype=torch.float32) if keep_float else None
     cbuf = torch.empty(max(sizes.ctx_bytes, 1), device=dev, dtype=torch.uint8)
     ws = torch.empty(max(sizes.fwd_workspace_bytes, 1), device=dev, dtype=torch.uint8)
     epi = _lib.make_epilogue(sc.data_ptr(), sh.data_ptr(), None if rs is None else rs.data_ptr(), relu)
-    _lib.check(_lib.load().cimq_module_forward_epilogue(
-        desc, lsq, xc.data_ptr(), wc.data_ptr(), aa.data_ptr(), aw.data_ptr(), None if ac is None else ac.data_ptr(),
-        None if bc is None else bc.data_ptr(), bm.data_ptr(), sg.data_ptr(), ctypes.byref(epi), out.data_ptr(),
-        cbuf.data_ptr(), ws.data_ptr(), _stream()), "cimq_module_forward_epilogue")
+    if not codes:
+        _lib.check(_lib.load().cimq_module_forward_epilogue(
+            desc, lsq, xc.data_ptr(), wc.data_ptr(), aa.data_ptr(), aw.data_ptr(),
+            None if ac is None else ac.data_ptr(), None if bc is None else bc.data_ptr(), bm.data_ptr(),
+            sg.data_ptr(), ctypes.byref(epi), out.data_ptr(), cbuf.data_ptr(), ws.data_ptr(), _stream()),
+            "cimq_module_forward_epilogue")
+        del keep
+        return out
+    oq = oa = None
+    if out_quant is None:
+        io = _lib.make_act_codes(x_codes=xc.data_ptr() if x_codes else None)
+    else:
+        o_alpha, o_gs, o_qp = out_quant
+        oa = o_alpha  # (a layer's own fp32 parameter on this device is read where it is)
+        if not (oa.dtype == torch.float32 and oa.device == dev and oa.is_contiguous()):
+            oa = f32(o_alpha).reshape(-1)[:1].contiguous()
+        oq = torch.empty(B, O, Ho, Wo, device=dev, dtype=torch.uint8)
+        io = _lib.make_act_codes(xc.data_ptr() if x_codes else None, oq.data_ptr(), oa.data_ptr(), float(o_gs),
+                                 float(o_qp), not keep_float)
+    _lib.check(_lib.load().cimq_module_forward_codes(
+        desc, lsq, ctypes.byref(io), None if x_codes else xc.data_ptr(), wc.data_ptr(), aa.data_ptr(), aw.data_ptr(),
+        None if ac is None else ac.data_ptr(), None if bc is None else bc.data_ptr(), bm.data_ptr(), sg.data_ptr(),
+        ctypes.byref(epi), None if out is None else out.data_ptr(), cbuf.data_ptr(), ws.data_ptr(), _stream()),
+        "cimq_module_forward_codes")
     del keep
-    return out
+    if oq is None:
+        return out
+    return (out, oq) if keep_float else oq
 
 
 def alpha_cim_init(x, w_q, sa, sw, binary_mask, signed_act, stride, padding, nbits_a, abitslice,

@@ -44,6 +44,9 @@ def get_base_parser():
     p.add_argument("--max-val-steps", default=0, type=int)
     p.add_argument("--fused-eval", action="store_true",
                    help="validate with BatchNorm, residual add and ReLU folded into the CiM convs (harness.fuse)")
+    p.add_argument("--fused-codes", action="store_true",
+                   help="--fused-eval with the activations handed from conv to conv as low-bit codes "
+                        "(FusedEval(model, codes=True))")
     return p
 
 
@@ -190,18 +193,21 @@ def train_epoch(loader, model, criterion, optimizer, epoch, hp, max_steps=0, log
     return loss_sum / max(seen, 1), top1 / max(seen, 1)
 
 
-def validate(loader, model, criterion, hp, max_steps=0, fused=False):
+def validate(loader, model, criterion, hp, max_steps=0, fused=False, codes=False):
     """main_lsq.py's validate(): top-1 / top-5 accuracy and mean loss in eval mode under no_grad.
     Nothing here selects the evaluation path: under no_grad every Conv2dLSQCiM runs libcimq's
     forward-only mode by itself (CIMQ_OPT_INFERENCE: same outputs, no backward state) and keeps its
     prepared weight side across the batches, so the weights are quantised once per input shape.
     ``fused``: evaluate through harness.fuse.FusedEval instead (folded BatchNorm, residual add and ReLU in the
-    conv kernels' epilogue; not bit-identical to the BatchNorm path, see that module)."""
+    conv kernels' epilogue; not bit-identical to the BatchNorm path, see that module).  ``codes`` (with
+    ``fused``): FusedEval(model, codes=True) -- activation codes between the convs, the same logits."""
     model.eval()
+    if codes and not fused:
+        raise ValueError("validate: codes=True needs fused=True")
     if fused:
         from .fuse import FusedEval
         bare = model.module if isinstance(model, nn.parallel.DistributedDataParallel) else model
-        model = FusedEval(bare)
+        model = FusedEval(bare, codes=codes)
     seen, loss_sum, c1, c5 = 0, 0.0, 0.0, 0.0
     with torch.no_grad():
         for i, (x, y) in enumerate(loader):
@@ -250,8 +256,9 @@ def main(argv=None):
     train_loader = CifarLoader(xtr, ytr, batch, device, train=True, seed=seed, rank=rank, world=world)
     val_loader = CifarLoader(xte, yte, batch, device, train=False)
     log = print if rank == 0 else (lambda *a, **k: None)
+    ev = dict(fused=args.fused_eval or args.fused_codes, codes=args.fused_codes)  # how validate evaluates
     if hp.evaluate:
-        acc1, acc5, _ = validate(val_loader, model, criterion, hp, args.max_val_steps, fused=args.fused_eval)
+        acc1, acc5, _ = validate(val_loader, model, criterion, hp, args.max_val_steps, **ev)
         log(f" * Acc@1 {acc1:.3f} Acc@5 {acc5:.3f}")
         return acc1
     for _ in range(args.start_epoch):
@@ -259,14 +266,14 @@ def main(argv=None):
     best = 0.0
     if rank == 0:
         os.makedirs(hp.log_name, exist_ok=True)
-    acc1, acc5, _ = validate(val_loader, model, criterion, hp, args.max_val_steps, fused=args.fused_eval)  # main_lsq.py validates first
+    acc1, acc5, _ = validate(val_loader, model, criterion, hp, args.max_val_steps, **ev)  # main_lsq.py validates first
     log(f"before training: val acc1 {acc1:.3f} acc5 {acc5:.3f}")
     acc1 = 0.0
     for epoch in range(args.start_epoch, hp.epochs):
         train_loader.set_epoch(epoch)
         loss, tacc = train_epoch(train_loader, model, criterion, optimizer, epoch, hp, args.max_steps, log)
         scheduler.step()
-        acc1, acc5, vloss = validate(val_loader, model, criterion, hp, args.max_val_steps, fused=args.fused_eval)
+        acc1, acc5, vloss = validate(val_loader, model, criterion, hp, args.max_val_steps, **ev)
         log(f"epoch {epoch}: train loss {loss:.4f} acc1 {tacc:.2f}  val acc1 {acc1:.3f} acc5 {acc5:.3f}")
         is_best = acc1 > best
         best = max(acc1, best)

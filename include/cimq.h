@@ -39,6 +39,9 @@ extern "C" {
 #endif
 
 #define CIMQ_ABI_VERSION 16
+/* additions that change no existing struct or call: 1 = activation codes (cimq_act_codes,
+ * cimq_module_forward_codes, cimq_module_codes_supported) */
+#define CIMQ_ABI_MINOR 1
 
 /* status codes */
 #define CIMQ_OK 0
@@ -140,6 +143,8 @@ typedef struct cimq_sizes {
 
 /* ABI version of the loaded library (compare with CIMQ_ABI_VERSION). */
 int cimq_abi_version(void);
+/* ... and its CIMQ_ABI_MINOR (a library from before the first addition has no such symbol). */
+int cimq_abi_minor(void);
 
 /* Message of the last failing call on this thread ("" if none). */
 const char* cimq_last_error(void);
@@ -281,6 +286,53 @@ int cimq_module_forward_epilogue(const cimq_conv_desc* d, const cimq_lsq_desc* q
                                  const float* alpha_cim, const float* beta_cim, const int8_t* binary_mask,
                                  const float* signed_act, const cimq_epilogue* epi, float* out, void* ctx, void* ws,
                                  void* stream);
+
+/* cimq_act_codes.flags */
+#define CIMQ_CODES_NO_FLOAT 1 /* out is not written and may be NULL (needs out_codes) */
+
+/* Activations as codes between two convs.  The code of a value y entering a layer with step-size parameter
+ * alpha_act, gradient-scale factor gscale_a and clamp maximum Qp (an integer in [1, 254]) is
+ *   sa = (alpha_act - alpha_act * gscale_a) + alpha_act * gscale_a      (fp32, the module prologue's expression)
+ *   code(y) = isnan(y) ? Qp + 1 : (uint8) rint(clamp(y / sa, 0, Qp))    (an IEEE fp32 division)
+ * exactly the chain of that layer's own activation quantiser, so its slice words depend on y through code(y)
+ * alone.  Layout: one byte per element, [B, C, H, W] contiguous, base 16-byte aligned. */
+typedef struct cimq_act_codes {
+  const uint8_t* x_codes;     /* NULL, or the input as codes (for this layer: d->lsq_qp is its Qp); x is then
+                                 ignored and may be NULL.  A byte above Qp + 1 is read as Qp + 1 */
+  uint8_t* out_codes;         /* NULL, or where the output's codes go, [B, O, Ho, Wo] */
+  const float* out_alpha_act; /* device [1]: the consumer's alpha_act */
+  float out_gscale_a;         /* the consumer's gradient-scale factor */
+  float out_qp;               /* the consumer's clamp maximum */
+  int32_t flags;              /* CIMQ_CODES_* */
+  int32_t reserved;           /* 0 */
+} cimq_act_codes;
+
+/* Whether cimq_module_forward_codes takes descriptor d with x_codes (*in_ok) and with out_codes (*out_ok): a host
+ * query, no device work.  in_ok: every forward route, where d->lsq_qp is an integer in [1, 254].  out_ok: the
+ * fwd5, v3 and general forward routes (cimq_module_route); the dense kernels write no codes.  Either pointer may
+ * be NULL.  Returns CIMQ_OK or the descriptor's own error. */
+int cimq_module_codes_supported(const cimq_conv_desc* d, int* in_ok, int* out_ok);
+
+/* cimq_module_forward_epilogue with the input read as codes, the output written as codes for the next layer, or
+ * both (io; the other arguments are that call's, epi required -- the identity is scale 1, shift 0).  With
+ * io->x_codes == NULL && io->out_codes == NULL it is cimq_module_forward_epilogue.
+ *  - x_codes: ``out`` is bit for bit what the same call gives on any fp32 x whose codes these are.  Where the
+ *    forward quantises in its own staging (fwd5, and v3 with the fused quantiser) the staging reads the bytes
+ *    straight into its word table; on the other routes a code-reading form of the forward-only prologue writes the
+ *    slice words and the forward kernels run unchanged.
+ *  - out_codes[b, o, h, w] = code(y) for the consumer layer (out_alpha_act, out_gscale_a, out_qp), y the value the
+ *    epilogue stores, or with CIMQ_CODES_NO_FLOAT would store, at out[b, o, h, w]: computed in the registers of
+ *    the storing kernel.
+ * No extra workspace (cimq_query_sizes).  CIMQ_EINVAL: every refusal of cimq_module_forward_epilogue, a NULL io, a
+ * non-zero reserved or unknown flags, CIMQ_CODES_NO_FLOAT without out_codes, out_codes with a NULL out_alpha_act
+ * or an out_qp that is not an integer in [1, 254], a code buffer that is not 16-byte aligned, out_codes
+ * overlapping out, x_codes, x or the residual.  CIMQ_EUNSUPPORTED: x_codes for a layer whose lsq_qp is not an
+ * integer in [1, 254], out_codes on the dense route (cimq_module_codes_supported).  Since ABI 16, minor 1. */
+int cimq_module_forward_codes(const cimq_conv_desc* d, const cimq_lsq_desc* q, const cimq_act_codes* io,
+                              const float* x, const float* weight, const float* alpha_act,
+                              const float* alpha_weight, const float* alpha_cim, const float* beta_cim,
+                              const int8_t* binary_mask, const float* signed_act, const cimq_epilogue* epi,
+                              float* out, void* ctx, void* ws, void* stream);
 
 /* One layer of cimq_module_prepare: its descriptors (as the forward will receive them; the
  * lsq descriptor's wprep and flags are ignored here) and raw parameters, and its output buffer

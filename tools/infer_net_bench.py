@@ -6,6 +6,10 @@ conv, xbar 128, 1.5-bit ADC) on a synthetic batch, eval mode under torch.no_grad
   side B  FusedEval(model)(x) -- each BatchNorm folded into a per-channel affine and, with the residual add and
           the ReLU, applied in the conv kernel's registers (cimq_module_forward_epilogue).
 
+  side C  (--codes) FusedEval(model, codes=True)(x) -- side B with the activations handed from conv to conv as
+          the consumer's low-bit codes, one byte per element (cimq_module_forward_codes).  The rounds then run
+          A, B, C, B again: the second B window gives the spread, and the bar is C <= B + spread.
+
 The two sides alternate (A, B, A again per round); a window is HIP events round ``passes`` forwards, sized to at
 least --window seconds; the second A window of a round gives the run-to-run spread.  Reports the time per
 forward of both sides, the spread, the device kernel launches of one forward of each (torch.profiler), the
@@ -14,6 +18,7 @@ torch.cuda.max_memory_allocated of one forward of each.
 
     python tools/infer_net_bench.py [--batch 256] [--rounds 7] [--window 0.25]
                                     [--out profiles/inference/infer_net_bench_B256.json]
+    python tools/infer_net_bench.py --codes    # -> profiles/inference/infer_net_bench_codes_B256.json
 
 Needs the GPU: there is no CPU fallback and no number without a run.
 """
@@ -82,17 +87,30 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--window", type=float, default=0.25, help="seconds per timed window (at least 0.2)")
     ap.add_argument("--no-launch-count", action="store_true")
+    ap.add_argument("--codes", action="store_true", help="add side C, FusedEval(model, codes=True): A, B, C, B per round")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("infer_net_bench: no ROCm device (there is no CPU fallback; nothing is measured)")
-    out_path = args.out or os.path.join(REPO, "profiles", "inference", f"infer_net_bench_B{args.batch}.json")
+    out_path = args.out or os.path.join(REPO, "profiles", "inference",
+                                        f"infer_net_bench{'_codes' if args.codes else ''}_B{args.batch}.json")
     dev = torch.device("cuda:0")
     model, x = build_model(args.batch, dev)
     fused = FusedEval(model)
     sides = {"A": lambda: model(x), "B": lambda: fused(x)}
+    order = ("A", "B", "A2")
+    if args.codes:
+        coded = FusedEval(model, codes=True)
+        sides["C"] = lambda: coded(x)
+        order = ("A", "B", "C", "B2")
     with torch.no_grad():
         ya, yb = sides["A"](), sides["B"]()
+        codes_info = None
+        if args.codes:
+            yc = sides["C"]()
+            codes_info = {"logits_equal_B": bool(torch.equal(yb, yc)), "code_edges": len(coded.code_edges),
+                          "edges_codes_only": sum(e[2] == "codes" for e in coded.code_edges)}
+            del yc
         diff = {"max_abs_logit_difference": float((ya - yb).abs().max()), "max_abs_logit": float(ya.abs().max()),
                 "top1_agree": float((ya.argmax(1) == yb.argmax(1)).float().mean())}
         del ya, yb
@@ -110,15 +128,16 @@ def main(argv=None):
             torch.cuda.synchronize()
             peak[key] = {"max_memory_allocated": torch.cuda.max_memory_allocated(),
                          "above_resident": torch.cuda.max_memory_allocated() - base}
-        tot = {"A": [], "B": [], "A2": []}
+        tot = {k: [] for k in order}
         for _ in range(args.rounds):
-            for key in ("A", "B", "A2"):
+            for key in order:
                 tot[key].append(timed(sides[key[0]], passes) * 1e3)
         if not args.no_launch_count:  # (after the timing: the profiler stays out of the windows)
             for key, fn in sides.items():
                 launches[key] = count_launches(fn)
     med = {k: statistics.median(v) for k, v in tot.items()}
-    spread = max(abs(a - b) for a, b in zip(tot["A"], tot["A2"]))
+    twin = order[-1]  # the repeated side: the same code, the same call
+    spread = max(abs(a - b) for a, b in zip(tot[twin[0]], tot[twin]))
     result = {
         "workload": f"harness ResNet-20 evaluation forward (model(x) vs FusedEval(model)(x)), eval + no_grad, "
                     f"B = {args.batch}, w3a3 (first conv w8a8), xbar {bench.XBAR}, adc {bench.ADC}, synthetic input",
@@ -126,19 +145,26 @@ def main(argv=None):
         "passes_per_window": passes, "rounds": args.rounds,
         "forward_us": {k: round(v, 1) for k, v in med.items()},
         "forward_us_windows": {k: [round(t, 1) for t in v] for k, v in tot.items()},
-        "spread_us": round(spread, 1),  # the largest |A - A2| of a round: the same code, the same call
+        "spread_us": round(spread, 1),  # the largest |A - A2| (with --codes |B - B2|) of a round
         "B_minus_A_us": round(med["B"] - med["A"], 1),
         "B_not_above_A_by_more_than_spread": bool(med["B"] <= med["A"] + spread),
         "kernel_launches_per_forward": launches,
         "peak_memory_bytes": peak,
         "fused_vs_batchnorm_path": diff,
     }
+    if args.codes:
+        result["workload"] += "; side C = FusedEval(model, codes=True)(x)"
+        result["abi_minor"] = _lib.ABI_MINOR
+        result["C_minus_B_us"] = round(med["C"] - med["B"], 1)
+        result["C_not_above_B_by_more_than_spread"] = bool(med["C"] <= med["B"] + spread)
+        result["codes"] = codes_info
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, "w") as f:
         json.dump(result, f, indent=1)
         f.write("\n")
-    print(json.dumps({k: result[k] for k in ("forward_us", "spread_us", "B_minus_A_us", "kernel_launches_per_forward",
-                                             "peak_memory_bytes", "fused_vs_batchnorm_path")}))
+    keys = ("forward_us", "spread_us", "B_minus_A_us", "kernel_launches_per_forward", "peak_memory_bytes",
+            "fused_vs_batchnorm_path") + (("C_minus_B_us", "C_not_above_B_by_more_than_spread", "codes") if args.codes else ())
+    print(json.dumps({k: result[k] for k in keys}))
     return result
 
 
