@@ -64,6 +64,9 @@ EXPORTED_SYMBOLS = (
     "cimq_module_forward_epilogue",
     "cimq_module_codes_supported",
     "cimq_module_forward_codes",
+    "cimq_net_abi",
+    "cimq_net_sizes",
+    "cimq_net_forward",
     "cimq_alpha_init",
     "cimq_shift_forward",
     "cimq_shift_backward",
@@ -132,6 +135,37 @@ class ActCodes(ctypes.Structure):
     _fields_ = [("x_codes", ctypes.c_void_p), ("out_codes", ctypes.c_void_p), ("out_alpha_act", ctypes.c_void_p),
                 ("out_gscale_a", ctypes.c_float), ("out_qp", ctypes.c_float), ("flags", ctypes.c_int32),
                 ("reserved", ctypes.c_int32)]
+
+
+class NetLayer(ctypes.Structure):
+    """Mirror of ``cimq_net_layer`` (cimq_net_abi() == 1)."""
+
+    _fields_ = [("desc", ctypes.POINTER(ConvDesc)), ("lsq", ctypes.POINTER(LsqDesc)),
+                ("weight", ctypes.c_void_p), ("alpha_act", ctypes.c_void_p), ("alpha_weight", ctypes.c_void_p),
+                ("alpha_cim", ctypes.c_void_p), ("beta_cim", ctypes.c_void_p), ("binary_mask", ctypes.c_void_p),
+                ("signed_act", ctypes.c_void_p), ("scale", ctypes.c_void_p), ("shift", ctypes.c_void_p),
+                ("epi_flags", ctypes.c_int32), ("in_slot", ctypes.c_int32), ("in_codes", ctypes.c_int32),
+                ("out_slot", ctypes.c_int32), ("out_mode", ctypes.c_int32), ("consumer", ctypes.c_int32),
+                ("res_slot", ctypes.c_int32), ("res_c0", ctypes.c_int32), ("res_stride", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("ctx", ctypes.c_void_p)]
+
+
+class NetHead(ctypes.Structure):
+    """Mirror of ``cimq_net_head``."""
+
+    _fields_ = [("in_slot", ctypes.c_int32), ("classes", ctypes.c_int32), ("weight", ctypes.c_void_p),
+                ("bias", ctypes.c_void_p), ("pooled", ctypes.c_void_p), ("reserved", ctypes.c_int32 * 2)]
+
+
+class NetDesc(ctypes.Structure):
+    """Mirror of ``cimq_net_desc``."""
+
+    _fields_ = [("n_layers", ctypes.c_int32), ("n_slots", ctypes.c_int32), ("layers", ctypes.POINTER(NetLayer)),
+                ("head", ctypes.POINTER(NetHead)), ("B", ctypes.c_int32), ("C", ctypes.c_int32),
+                ("H", ctypes.c_int32), ("W", ctypes.c_int32)]
+
+
+NET_HEAD_MAX_C = 8192  # CIMQ_NET_HEAD_MAX_C
 
 
 class QConvDesc(ctypes.Structure):
@@ -228,6 +262,13 @@ def _bind(lib):
     lib.cimq_module_forward_codes.argtypes = ([ctypes.POINTER(ConvDesc), ctypes.POINTER(LsqDesc),
                                                ctypes.POINTER(ActCodes)] + [_VP] * 8 +
                                               [ctypes.POINTER(Epilogue)] + [_VP] * 4)
+    lib.cimq_net_abi.restype = ctypes.c_int
+    lib.cimq_net_abi.argtypes = []
+    lib.cimq_net_sizes.restype = ctypes.c_int
+    lib.cimq_net_sizes.argtypes = [ctypes.POINTER(NetDesc)] + [ctypes.POINTER(ctypes.c_size_t)] * 3
+    lib.cimq_net_forward.restype = ctypes.c_int
+    lib.cimq_net_forward.argtypes = [ctypes.POINTER(NetDesc), _VP, ctypes.POINTER(_VP), ctypes.POINTER(_VP), _VP, _VP,
+                                     _VP]
     lib.cimq_alpha_init.restype = ctypes.c_int
     lib.cimq_alpha_init.argtypes = [ctypes.POINTER(ConvDesc)] + [_VP] * 10
     lib.cimq_shift_forward.restype = ctypes.c_int

@@ -1,6 +1,8 @@
 // cimq_api.hip -- the extern "C" boundary of libcimq.so (declared in include/cimq.h).
 // Host-side geometry validation, ctx / workspace carving and the kernel launch sequences
 // that replace get_cim_output_signed.forward / backward (models/_modules/lsq.py:92-386).
+#include <vector>
+
 #include "cimq_host.h"
 #include "cimq_prep.hip"
 #include "cimq_lsq.hip"
@@ -588,17 +590,30 @@ static bool codes_qp_ok(float qp) { return qp >= 1.f && qp <= 254.f && qp == (fl
 static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* x, const float* weight,
                                const float* alpha_act, const float* alpha_weight, const float* alpha_cim,
                                const float* beta_cim, const int8_t* binary_mask, const float* signed_act, float* out,
-                               void* ctx, void* ws, void* stream, const Epi* ep = nullptr) {
+                               void* ctx, void* ws, void* stream, const Epi* ep = nullptr, bool dry = false) {
+  // dry (cimq_net_forward's validation pass): every refusal below, no launch
   Geo g;
   LsqArgs la;
   CIMQ_TRY(module_geo(d, q, &g, &la, beta_cim != nullptr));
+  // the residual's extent: out's geometry, or the view's own (Epi::rview, cimq_net_forward alone)
+  const ResView rv = ep ? res_view(ep->rvw0, ep->rvw1) : ResView{};
+  const uintptr_t res_bytes = !ep ? 0 : ep->rvw1 ? (uintptr_t)g.B * rv.cr * rv.h * rv.w * 4 : (uintptr_t)g.M * g.O * 4;
   if (ep) {  // cimq_module_forward_epilogue: the residual has out's geometry
     if (!g.inference) return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: a CIMQ_OPT_INFERENCE descriptor only");
     if (ep->res && out) {
       const uintptr_t r0 = reinterpret_cast<uintptr_t>(ep->res), o0 = reinterpret_cast<uintptr_t>(out);
       const uintptr_t nb = (uintptr_t)g.M * g.O * 4;
-      if (r0 < o0 + nb && o0 < r0 + nb)
+      if (r0 < o0 + nb && o0 < r0 + res_bytes)
         return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: residual overlaps out");
+    }
+    if (ep->rvw1) {  // the view lives in the code instances of the fwd5, v3 and general routes
+      const int fwd = route_of(g).fwd;
+      if (fwd == CIMQ_ROUTE_DENSE)
+        return fail(CIMQ_EUNSUPPORTED, "cimq_net_forward: the dense route reads no residual view (res_stride 2 or "
+                                       "fewer source channels than out_channels)");
+      if (fwd != CIMQ_ROUTE_GENERAL && g.Wo % 4 != 0)
+        return fail(CIMQ_EUNSUPPORTED, "cimq_net_forward: a residual view on the fwd5 / v3 routes needs an output "
+                                       "width that is a multiple of 4 (it is %d)", g.Wo);
     }
   }
   const uint8_t* xq = ep ? ep->xq : nullptr;  // cimq_module_forward_codes: the input as codes, x ignored
@@ -620,13 +635,14 @@ static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
       if (hits(out, qn * 4)) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: out_codes overlaps out");
       if (hits(xq, (uintptr_t)g.Nin)) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: out_codes overlaps x_codes");
       if (!xq && hits(x, (uintptr_t)g.Nin * 4)) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: out_codes overlaps x");
-      if (hits(ep->res, qn * 4)) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: out_codes overlaps the residual");
+      if (hits(ep->res, res_bytes)) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: out_codes overlaps the residual");
     }
   }
   if ((!x && !xq) || !weight || !alpha_act || !alpha_weight || !binary_mask || !signed_act ||
       (!out && !(ep && ep->nofloat)) || !ctx || !ws)
     return fail(CIMQ_EINVAL, "null pointer argument");
   CIMQ_TRY(check_alpha(g, &la, alpha_cim, nullptr, false));
+  if (dry) return CIMQ_OK;
   const bool has_alpha = la.nbits_alpha > 0;
   const Route r = route_of(g);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -682,7 +698,8 @@ prepared:
   float* bpo = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(ws) + W.bpo);
   CIMQ_TRY(launch_fwd_any(g, c, scal + 1, scal, bpo, nullptr, nullptr, s));
   const dim3 tgrid(std::min(cdiv((long long)g.M * g.O, 256), 8192));
-  if (ep && oq) hipLaunchKernelGGL(bpo_to_nchw_codes_kernel, tgrid, dim3(256), 0, s, g, bpo, out, *ep);
+  if (ep && ep->rvw1) hipLaunchKernelGGL(bpo_to_nchw_view_kernel, tgrid, dim3(256), 0, s, g, bpo, out, *ep);
+  else if (ep && oq) hipLaunchKernelGGL(bpo_to_nchw_codes_kernel, tgrid, dim3(256), 0, s, g, bpo, out, *ep);
   else if (ep) hipLaunchKernelGGL(bpo_to_nchw_epi_kernel, tgrid, dim3(256), 0, s, g, bpo, out, *ep);
   else hipLaunchKernelGGL(bpo_to_nchw_kernel, tgrid, dim3(256), 0, s, g, bpo, out);
   return check_hip("bpo_to_nchw");
@@ -752,11 +769,16 @@ int cimq_module_codes_supported(const cimq_conv_desc* d, int* in_ok, int* out_ok
   return CIMQ_OK;
 }
 
-int cimq_module_forward_codes(const cimq_conv_desc* d, const cimq_lsq_desc* q, const cimq_act_codes* io,
+}  // extern "C"
+
+// cimq_module_forward_codes, and one layer of cimq_net_forward: view (the net alone) makes epi->residual a view of
+// a larger tensor (Epi::rvw0 / rvw1); dry (the net's validation pass) stops before the first launch
+static int forward_codes_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, const cimq_act_codes* io,
                               const float* x, const float* weight, const float* alpha_act,
                               const float* alpha_weight, const float* alpha_cim, const float* beta_cim,
                               const int8_t* binary_mask, const float* signed_act, const cimq_epilogue* epi,
-                              float* out, void* ctx, void* ws, void* stream) {
+                              float* out, void* ctx, void* ws, void* stream, const ResView* view = nullptr,
+                              bool dry = false) {
   // (the descriptor-independent refusals first; the epilogue's are cimq_module_forward_epilogue's own)
   static const char who[] = "cimq_module_forward_codes";
   CIMQ_TRY(check_forward_only(who, d));
@@ -764,9 +786,12 @@ int cimq_module_forward_codes(const cimq_conv_desc* d, const cimq_lsq_desc* q, c
   CIMQ_TRY(check_epilogue(who, epi, alpha_cim, beta_cim));
   if (io->flags & ~CIMQ_CODES_NO_FLOAT) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: unknown flags 0x%x", io->flags);
   if (io->reserved != 0) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: reserved must be 0");
-  if (!io->x_codes && !io->out_codes && !io->flags)
-    return cimq_module_forward_epilogue(d, q, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask,
-                                        signed_act, epi, out, ctx, ws, stream);
+  if (!io->x_codes && !io->out_codes && !io->flags) {  // no codes: cimq_module_forward_epilogue
+    Epi ep{epi->scale, epi->shift, epi->residual, (epi->flags & CIMQ_EPI_RELU) ? 1 : 0};
+    if (view) set_res_view(&ep, view->c0, view->cr, view->s, view->h, view->w);
+    return module_forward_impl(d, q, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act,
+                               out, ctx, ws, stream, &ep, dry);
+  }
   if ((io->flags & CIMQ_CODES_NO_FLOAT) && !io->out_codes)
     return fail(CIMQ_EINVAL, "cimq_module_forward_codes: CIMQ_CODES_NO_FLOAT needs out_codes");
   if (io->out_codes) {
@@ -784,8 +809,223 @@ int cimq_module_forward_codes(const cimq_conv_desc* d, const cimq_lsq_desc* q, c
   ep.oalpha = io->out_alpha_act;
   ep.ogs = io->out_gscale_a;
   ep.oqp = io->out_qp;
+  if (view) set_res_view(&ep, view->c0, view->cr, view->s, view->h, view->w);
   return module_forward_impl(d, q, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act,
-                             out, ctx, ws, stream, &ep);
+                             out, ctx, ws, stream, &ep, dry);
+}
+
+// ---- cimq_net_*: a plan of fused conv layers, their slots and the head, run in one call ----
+
+// what a slot holds while the plan is walked in order
+struct NetSlot {
+  bool has_float = false, has_codes = false;
+  int B = 0, C = 0, H = 0, W = 0;
+  int consumer = -1;  // the layer whose quantiser the code plane was written for
+};
+
+// One layer's call (forward_codes_impl's arguments from the plan); view: the residual as a view, or null
+static int net_layer_call(const cimq_net_desc* n, int i, const float* x, void* const* sf, void* const* sc,
+                          const ResView* view, void* ws, void* stream, bool dry) {
+  const cimq_net_layer& L = n->layers[i];
+  cimq_epilogue e;
+  e.scale = L.scale;
+  e.shift = L.shift;
+  e.residual = L.res_slot >= 0 ? reinterpret_cast<const float*>(sf[L.res_slot]) : nullptr;
+  e.flags = L.epi_flags;
+  e.reserved = 0;
+  cimq_act_codes io;
+  memset(&io, 0, sizeof(io));
+  const float* xin = x;
+  if (L.in_slot >= 0) {
+    xin = L.in_codes ? nullptr : reinterpret_cast<const float*>(sf[L.in_slot]);
+    io.x_codes = L.in_codes ? reinterpret_cast<const uint8_t*>(sc[L.in_slot]) : nullptr;
+  }
+  if (L.out_mode & 2) {
+    const cimq_net_layer& K = n->layers[L.consumer];
+    io.out_codes = reinterpret_cast<uint8_t*>(sc[L.out_slot]);
+    io.out_alpha_act = K.alpha_act;
+    io.out_gscale_a = K.lsq->gscale_a;
+    io.out_qp = K.desc->lsq_qp;
+    if (!(L.out_mode & 1)) io.flags = CIMQ_CODES_NO_FLOAT;
+  }
+  float* out = (L.out_mode & 1) ? reinterpret_cast<float*>(sf[L.out_slot]) : nullptr;
+  return forward_codes_impl(L.desc, L.lsq, &io, xin, L.weight, L.alpha_act, L.alpha_weight, L.alpha_cim, L.beta_cim,
+                            L.binary_mask, L.signed_act, &e, out, L.ctx, ws, stream, view, dry);
+}
+
+// The whole validation of a plan, in layer order, and with ``run`` its launches.  bufs: the caller's buffers are
+// there to be checked (cimq_net_forward) -- each layer's own call is then made dry, so that every refusal it has
+// comes before the first launch.  fb / cb / wsb: cimq_net_sizes' outputs (may be null).
+static int net_walk(const cimq_net_desc* n, bool bufs, bool run, const float* x, void* const* sf, void* const* sc,
+                    float* logits, void* ws, void* stream, size_t* fb, size_t* cb, size_t* wsb) {
+  static const char who[] = "cimq_net_forward";
+  if (!n) return fail(CIMQ_EINVAL, "%s: null plan", who);
+  if (n->n_layers < 0 || n->n_slots < 0) return fail(CIMQ_EINVAL, "%s: negative n_layers or n_slots", who);
+  if (n->n_layers == 0 && !n->head) return fail(CIMQ_EINVAL, "%s: n_layers == 0 without a head", who);
+  if (n->n_layers > 0 && !n->layers) return fail(CIMQ_EINVAL, "%s: null layers", who);
+  if (n->B < 1 || n->C < 1 || n->H < 1 || n->W < 1) return fail(CIMQ_EINVAL, "%s: bad input shape", who);
+  auto misaligned = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; };
+  if (bufs) {
+    if (!x) return fail(CIMQ_EINVAL, "%s: null x", who);
+    if (misaligned(x)) return fail(CIMQ_EINVAL, "%s: x must be 16-byte aligned", who);
+    if (n->n_slots > 0 && (!sf || !sc)) return fail(CIMQ_EINVAL, "%s: null slot arrays", who);
+    if (n->n_layers > 0 && !ws) return fail(CIMQ_EINVAL, "%s: null workspace", who);
+  }
+  std::vector<NetSlot> slot((size_t)n->n_slots);
+  for (int k = 0; k < n->n_slots; ++k) {
+    if (fb) fb[k] = 0;
+    if (cb) cb[k] = 0;
+  }
+  size_t wsmax = 0;
+  auto in_range = [&](int k) { return k >= 0 && k < n->n_slots; };
+  for (int i = 0; i < n->n_layers; ++i) {
+    const cimq_net_layer& L = n->layers[i];
+    if (!L.desc || !L.lsq) return fail(CIMQ_EINVAL, "%s: layer %d: null descriptor", who, i);
+    if (L.reserved != 0) return fail(CIMQ_EINVAL, "%s: layer %d: reserved must be 0", who, i);
+    CIMQ_TRY(check_forward_only(who, L.desc));
+    Geo g;
+    CIMQ_TRY(make_geo(L.desc, &g));
+    if (g.input_kind != CIMQ_INPUT_RAW_LSQ) return fail(CIMQ_EINVAL, "%s: layer %d: module entry points take the raw activation", who, i);
+    g = module_form(g);
+    if (g.variant == VAR_STOCHASTIC)
+      return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: a stochastic-ADC layer takes its seed per call", who, i);
+    const int fwd = route_of(g).fwd;
+    // the input
+    if (L.in_codes != 0 && L.in_codes != 1) return fail(CIMQ_EINVAL, "%s: layer %d: in_codes must be 0 or 1", who, i);
+    if (L.in_slot == -1) {
+      if (L.in_codes) return fail(CIMQ_EINVAL, "%s: layer %d: the net's input x has no code plane", who, i);
+      if (g.B != n->B || g.C != n->C || g.H != n->H || g.W != n->W)
+        return fail(CIMQ_EINVAL, "%s: layer %d: its descriptor's input shape is not x's", who, i);
+    } else {
+      if (!in_range(L.in_slot)) return fail(CIMQ_EINVAL, "%s: layer %d: in_slot %d out of range", who, i, L.in_slot);
+      const NetSlot& s = slot[L.in_slot];
+      if (L.in_codes ? !s.has_codes : !s.has_float)
+        return fail(CIMQ_EINVAL, "%s: layer %d: reads a plane of slot %d that no earlier layer wrote", who, i, L.in_slot);
+      if (L.in_codes && s.consumer != i)
+        return fail(CIMQ_EINVAL, "%s: layer %d: the codes in slot %d were written for layer %d", who, i, L.in_slot, s.consumer);
+      if (g.B != s.B || g.C != s.C || g.H != s.H || g.W != s.W)
+        return fail(CIMQ_EINVAL, "%s: layer %d: the producer's output shape [%d, %d, %d, %d] differs from its descriptor's "
+                                 "input", who, i, s.B, s.C, s.H, s.W);
+      if (L.in_codes && !codes_qp_ok(g.lsq_qp))
+        return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: x_codes needs an integer lsq_qp in [1, 254]", who, i);
+    }
+    // the output
+    if (L.out_mode < 1 || L.out_mode > 3) return fail(CIMQ_EINVAL, "%s: layer %d: out_mode must be 1, 2 or 3", who, i);
+    if (!in_range(L.out_slot)) return fail(CIMQ_EINVAL, "%s: layer %d: out_slot %d out of range", who, i, L.out_slot);
+    if (L.out_slot == L.in_slot || L.out_slot == L.res_slot)
+      return fail(CIMQ_EINVAL, "%s: layer %d: out_slot is its own in_slot or res_slot", who, i);
+    if (L.out_mode & 2) {
+      if (L.consumer <= i || L.consumer >= n->n_layers || n->layers[L.consumer].in_slot != L.out_slot)
+        return fail(CIMQ_EINVAL, "%s: layer %d: consumer %d is not a later layer that reads slot %d", who, i, L.consumer,
+                    L.out_slot);
+      const cimq_net_layer& K = n->layers[L.consumer];
+      if (!K.desc || !K.lsq) return fail(CIMQ_EINVAL, "%s: layer %d: null descriptor", who, L.consumer);
+      if (fwd == CIMQ_ROUTE_DENSE)
+        return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: the dense route writes no out_codes (cimq_module_codes_supported)",
+                    who, i);
+      if (!codes_qp_ok(K.desc->lsq_qp))
+        return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: its consumer %d reads no codes (an integer lsq_qp in [1, 254]; "
+                                       "cimq_module_codes_supported)", who, i, L.consumer);
+    }
+    // the residual
+    ResView view{};
+    bool is_view = false;
+    if (L.res_slot != -1) {
+      if (!in_range(L.res_slot)) return fail(CIMQ_EINVAL, "%s: layer %d: res_slot %d out of range", who, i, L.res_slot);
+      const NetSlot& s = slot[L.res_slot];
+      if (!s.has_float)
+        return fail(CIMQ_EINVAL, "%s: layer %d: reads a plane of slot %d that no earlier layer wrote", who, i, L.res_slot);
+      const int rs = L.res_stride;
+      if (rs != 1 && rs != 2) return fail(CIMQ_EINVAL, "%s: layer %d: res_stride must be 1 or 2", who, i);
+      if (s.B != g.B || (s.H + rs - 1) / rs != g.Ho || (s.W + rs - 1) / rs != g.Wo)
+        return fail(CIMQ_EINVAL, "%s: layer %d: the residual source [%d, %d, %d, %d] at stride %d is not the output's "
+                                 "[%d, %d]", who, i, s.B, s.C, s.H, s.W, rs, g.Ho, g.Wo);
+      if (L.res_c0 < 0 || L.res_c0 + s.C > g.O)
+        return fail(CIMQ_EINVAL, "%s: layer %d: res_c0 %d with %d source channels leaves the %d output channels", who, i,
+                    L.res_c0, s.C, g.O);
+      is_view = rs == 2 || s.C != g.O;
+      if (is_view) {
+        if (fwd == CIMQ_ROUTE_DENSE)
+          return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: the dense route reads no residual view (res_stride 2 or fewer "
+                                         "source channels than out_channels)", who, i);
+        if (fwd != CIMQ_ROUTE_GENERAL && g.Wo % 4 != 0)
+          return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: a residual view on the fwd5 / v3 routes needs an output width that "
+                                         "is a multiple of 4 (it is %d)", who, i, g.Wo);
+        if (s.C > kViewMaxDim ||s.H > kViewMaxDim || s.W > kViewMaxDim || g.O > kViewMaxDim)
+          return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: a residual view's dimensions must fit 15 bits", who, i);
+        view = ResView{L.res_c0, s.C, rs, s.H, s.W};
+      }
+    }
+    if (fb && (L.out_mode & 1)) fb[L.out_slot] = std::max(fb[L.out_slot], (size_t)g.M * g.O * 4);
+    if (cb && (L.out_mode & 2)) cb[L.out_slot] = std::max(cb[L.out_slot], (size_t)g.M * g.O);
+    wsmax = std::max(wsmax, ws_layout(g).total);
+    if (bufs) {
+      auto bad = [&](const void* p) { return !p || misaligned(p); };
+      if ((L.in_slot >= 0 && bad(L.in_codes ? sc[L.in_slot] : sf[L.in_slot])) || ((L.out_mode & 1) && bad(sf[L.out_slot])) ||
+          ((L.out_mode & 2) && bad(sc[L.out_slot])) || (L.res_slot >= 0 && bad(sf[L.res_slot])))
+        return fail(CIMQ_EINVAL, "%s: layer %d: a slot buffer it uses is null or not 16-byte aligned", who, i);
+      // every refusal of the per-layer call, and with run its launches
+      CIMQ_TRY(net_layer_call(n, i, x, sf, sc, is_view ? &view : nullptr, ws, stream, !run));
+    }
+    NetSlot& o = slot[L.out_slot];
+    o.has_float = (L.out_mode & 1) != 0;
+    o.has_codes = (L.out_mode & 2) != 0;
+    o.consumer = o.has_codes ? L.consumer : -1;
+    o.B = g.B; o.C = g.O; o.H = g.Ho; o.W = g.Wo;
+  }
+  if (wsb) *wsb = wsmax;
+  if (const cimq_net_head* h = n->head) {
+    if (h->reserved[0] != 0 || h->reserved[1] != 0) return fail(CIMQ_EINVAL, "%s: head: reserved must be 0", who);
+    if (h->classes < 1) return fail(CIMQ_EINVAL, "%s: head: classes must be at least 1", who);
+    if (!h->weight) return fail(CIMQ_EINVAL, "%s: head: null weight", who);
+    int B = n->B, C = n->C, H = n->H, W = n->W;
+    const float* src = x;
+    if (h->in_slot != -1) {
+      if (!in_range(h->in_slot)) return fail(CIMQ_EINVAL, "%s: head: in_slot %d out of range", who, h->in_slot);
+      const NetSlot& s = slot[h->in_slot];
+      if (!s.has_float) return fail(CIMQ_EINVAL, "%s: head: reads a plane of slot %d that no earlier layer wrote", who, h->in_slot);
+      B = s.B; C = s.C; H = s.H; W = s.W;
+      if (bufs) src = reinterpret_cast<const float*>(sf[h->in_slot]);
+    }
+    if (C > kHeadMaxC)
+      return fail(CIMQ_EUNSUPPORTED, "%s: head: %d channels, at most CIMQ_NET_HEAD_MAX_C (%d) fit its LDS plan", who, C, kHeadMaxC);
+    if ((long long)H * W > 0x7fffffffLL / 4) return fail(CIMQ_EUNSUPPORTED, "%s: head: map too large", who);
+    if (bufs) {
+      if (!logits) return fail(CIMQ_EINVAL, "%s: null logits", who);
+      if (!src || misaligned(src)) return fail(CIMQ_EINVAL, "%s: head: its input is null or not 16-byte aligned", who);
+    }
+    if (run) {
+      hipLaunchKernelGGL(net_head_kernel, dim3(B), dim3(256), (size_t)C * 4, reinterpret_cast<hipStream_t>(stream), src, C,
+                         H * W, h->classes, h->weight, h->bias, h->pooled, logits);
+      CIMQ_TRY(check_hip("net_head"));
+    }
+  }
+  return CIMQ_OK;
+}
+
+extern "C" {
+
+int cimq_module_forward_codes(const cimq_conv_desc* d, const cimq_lsq_desc* q, const cimq_act_codes* io,
+                              const float* x, const float* weight, const float* alpha_act,
+                              const float* alpha_weight, const float* alpha_cim, const float* beta_cim,
+                              const int8_t* binary_mask, const float* signed_act, const cimq_epilogue* epi,
+                              float* out, void* ctx, void* ws, void* stream) {
+  return forward_codes_impl(d, q, io, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act,
+                            epi, out, ctx, ws, stream);
+}
+
+int cimq_net_abi(void) { return 1; }
+
+int cimq_net_sizes(const cimq_net_desc* net, size_t* slot_float_bytes, size_t* slot_code_bytes, size_t* ws_bytes) {
+  return net_walk(net, false, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, slot_float_bytes,
+                  slot_code_bytes, ws_bytes);
+}
+
+int cimq_net_forward(const cimq_net_desc* net, const float* x, void* const* slot_float, void* const* slot_codes,
+                     float* logits, void* ws, void* stream) {
+  // the whole plan is validated first (every layer's own call made dry): a refused plan launches nothing
+  CIMQ_TRY(net_walk(net, true, false, x, slot_float, slot_codes, logits, ws, stream, nullptr, nullptr, nullptr));
+  return net_walk(net, true, true, x, slot_float, slot_codes, logits, ws, stream, nullptr, nullptr, nullptr);
 }
 
 static int module_backward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* grad_out,

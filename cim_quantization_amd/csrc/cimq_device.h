@@ -63,6 +63,38 @@ __device__ inline float4 epi_val4(const Epi& ep, float sc, float sh, size_t idx,
                      epi_val(a2, sc, sh, hr, rv.z, rl), epi_val(a3, sc, sh, hr, rv.w, rl));
 }
 
+// The residual as a view (Epi::rvw0 / rvw1, the code instances alone): the element that adds to out (b, o, pixel p
+// of a wo-wide map), +0.0f outside the view's channels -- the add itself stays a real one, so that a -0.0 becomes
+// +0.0 as torch's add of the padded zero makes it.
+__device__ inline float epi_view(const Epi& ep, int b, int o, int p, int wo) {
+  const ResView v = res_view(ep.rvw0, ep.rvw1);
+  const int c = o - v.c0;
+  if ((unsigned)c >= (unsigned)v.cr) return 0.f;
+  const int h = p / wo, w = p - h * wo;
+  return ep.res[(((size_t)b * v.cr + c) * v.h + (size_t)v.s * h) * v.w + v.s * w];
+}
+// ... epi_val4 of a code instance: the four pixels p .. p + 3 of one output row (wo % 4 == 0, checked on the host)
+// of image b, channel o; a view is read with four scalar loads, a full residual is epi_val4's float4
+__device__ inline float4 epi_val4v(const Epi& ep, float sc, float sh, size_t idx, int b, int o, int p, int wo, float a0,
+                                   float a1, float a2, float a3) {
+  if (ep.rvw1 == 0) return epi_val4(ep, sc, sh, idx, a0, a1, a2, a3);  // (block-uniform)
+  // (the two words through opaque copies: unpacked here, at the store, and not into five scalar registers held
+  // across the whole m-tile loop)
+  uint32_t w0 = ep.rvw0, w1 = ep.rvw1;
+  asm volatile("" : "+s"(w0), "+s"(w1));
+  const ResView v = res_view(w0, w1);
+  const bool rl = ep.relu != 0;
+  float4 rv = make_float4(0.f, 0.f, 0.f, 0.f);
+  const int c = o - v.c0;
+  if ((unsigned)c < (unsigned)v.cr) {
+    const int h = p / wo, w = p - h * wo;
+    const float* src = ep.res + (((size_t)b * v.cr + c) * v.h + (size_t)v.s * h) * v.w + v.s * w;
+    rv = make_float4(src[0], src[v.s], src[2 * v.s], src[3 * v.s]);
+  }
+  return make_float4(epi_val(a0, sc, sh, true, rv.x, rl), epi_val(a1, sc, sh, true, rv.y, rl),
+                     epi_val(a2, sc, sh, true, rv.z, rl), epi_val(a3, sc, sh, true, rv.w, rl));
+}
+
 // tensor.type(torch.int8): truncate toward zero, keep the low byte (wraps).  NaN -> 0.
 __device__ inline int to_i8_wrap(float v) {
   if (!(fabsf(v) < 2147483520.f)) return 0;

@@ -43,6 +43,9 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512 * (NOBA & 3), 512 * (N
     Epi ep) {
   constexpr int NOB = NOBA & 3;
   constexpr bool COD = NOBA >= 4;
+  // NOBA 8 + NOB: the code instance with the residual read as a view (Epi::rvw0 / rvw1, cimq_net_forward's option-A
+  // shortcut: four scalar loads per float4) -- instances of their own, so that the 4 + NOB ones keep their code
+  constexpr bool VIEW = NOBA >= 8;
   static_assert(!(EPI && WST), "the epilogue instances are forward only");
   static_assert(!COD || EPI, "the code instances carry the epilogue");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -320,7 +323,10 @@ __global__ __attribute__((amdgpu_flat_work_group_size(512 * (NOBA & 3), 512 * (N
     if (o < g.O) {
       const int bb = m0 / g.P, pq = m0 - bb * g.P;
       const int oi = (bb * g.O + o) * g.P + pq;
-      if constexpr (COD)
+      if constexpr (VIEW)
+        store_codes4(ep, out, oi,
+                     epi_val4v(ep, ep.scale[o], ep.shift[o], oi, bb, o, pq, g.Wo, acc[0], acc[1], acc[2], acc[3]));
+      else if constexpr (COD)
         store_codes4(ep, out, oi, epi_val4(ep, ep.scale[o], ep.shift[o], oi, acc[0], acc[1], acc[2], acc[3]));
       else if constexpr (EPI)
         *reinterpret_cast<float4*>(out + oi) = epi_val4(ep, ep.scale[o], ep.shift[o], oi, acc[0], acc[1], acc[2], acc[3]);

@@ -47,9 +47,13 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
   // CSTA 40 + s: the code instance of CSTA 20 + s (cimq_module_forward_codes) -- the row staging reads the
   // input's codes (ep.xq: bytes straight into the word table, stage_rows_qc) or quantises fp32 x as before, and the
   // store writes the float4, the consumer's codes (ep.oq) or both: block-uniform branches on ep
+  // CSTA 60 + s: the code instance with the residual read as a view (Epi::rvw0 / rvw1, cimq_net_forward's
+  // option-A shortcut: four scalar loads per float4).  Instances of their own: inside the 40 + s ones the view cost
+  // cim_fwd_v3_kernel<4, 1, 40, 2> a wave per SIMD (96 -> 97 VGPRs)
+  constexpr bool VIEW = CSTA >= 60;
   constexpr bool COD = CSTA >= 40;
   constexpr bool EPI = CSTA >= 20;
-  constexpr int CSTB = COD ? CSTA - 40 : EPI ? CSTA - 20 : CSTA;
+  constexpr int CSTB = VIEW ? CSTA - 60 : COD ? CSTA - 40 : EPI ? CSTA - 20 : CSTA;
   static_assert(!EPI || CSTB == 0 || CSTB == 9 || CSTB >= 10, "the epilogue instances are forward only");
   constexpr int CST = CSTB == 9 ? 8 : CSTB >= 10 ? CSTB - 10 : CSTB;
   constexpr bool WST = CSTB < 9;
@@ -483,8 +487,13 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
           if constexpr (COD) {
             int oe = o;  // (opaque, as below)
             asm volatile("" : "+v"(oe));
-            store_codes4(ep, out, oi,
-                         epi_val4(ep, ep.scale[oe], ep.shift[oe], oi, acc[ob][0], acc[ob][1], acc[ob][2], acc[ob][3]));
+            if constexpr (VIEW)
+              store_codes4(ep, out, oi,
+                           epi_val4v(ep, ep.scale[oe], ep.shift[oe], oi, bb, oe, pq, g.Wo, acc[ob][0], acc[ob][1],
+                                     acc[ob][2], acc[ob][3]));
+            else
+              store_codes4(ep, out, oi,
+                           epi_val4(ep, ep.scale[oe], ep.shift[oe], oi, acc[ob][0], acc[ob][1], acc[ob][2], acc[ob][3]));
           } else if constexpr (EPI) {
             // (the table index through an opaque copy: the two 64-bit entry addresses, invariant over the m-tiles,
             // would otherwise be kept in 4 VGPRs per output block across the whole loop -- a wave per SIMD in the

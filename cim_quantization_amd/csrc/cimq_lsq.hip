@@ -415,6 +415,74 @@ __global__ void bpo_to_nchw_codes_kernel(Geo g, const float* __restrict__ src, f
     if (ep.oq) ep.oq[e] = (uint8_t)act_code(y, osa, ep.oqp);
   }
 }
+// ... and with the residual read as a view (Epi::rvw0 / rvw1, cimq_net_forward's option-A shortcut): one scalar read
+// at the view's own address, +0.0f outside its channels; codes as above where ep.oq is set
+__global__ void bpo_to_nchw_view_kernel(Geo g, const float* __restrict__ src, float* __restrict__ dst, Epi ep) {
+  const size_t n = (size_t)g.M * g.O;
+  const bool rl = ep.relu != 0;
+  const float osa = ep.oq ? grad_scale_value(ep.oalpha[0], ep.ogs) : 1.f;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
+    const size_t p = e % g.P, bo = e / g.P;
+    const size_t o = bo % g.O, b = bo / g.O;
+    const float y = epi_val(src[(b * g.P + p) * g.O + o], ep.scale[o], ep.shift[o], true,
+                            epi_view(ep, (int)b, (int)o, (int)p, g.Wo), rl);
+    if (!ep.nofloat) dst[e] = y;
+    if (ep.oq) ep.oq[e] = (uint8_t)act_code(y, osa, ep.oqp);
+  }
+}
+// The head of cimq_net_forward: global average pool over H x W, then y = W p + b.  One 256-thread workgroup per
+// image.  Pooling: wave w takes channels w, w + 4, ...; a channel's hw contiguous values are summed per lane (lane l
+// takes the float4 at 4 l, 4 l + 256, ... where hw % 4 == 0 -- x is 16-byte aligned -- its four values added in
+// order; else the scalars l, l + 64, ...), then across the lanes by a fixed xor butterfly (32, 16, ..., 1), and
+// divided by (float)hw with an IEEE division: the C pooled values stay in LDS (C <= kHeadMaxC).  Classifier: wave
+// w takes classes w, w + 4, ...; lane l sums w[k, c] * p[c] over c = l, l + 64, ... (a product, then an add: no
+// fused multiply-add), the same butterfly, lane 0 adds the bias.  No atomics, one fixed order: two runs are equal
+// bit for bit.  A NaN feature makes its image's pooled value and so all of that image's logits NaN, nobody else's.
+constexpr int kHeadMaxC = 8192;  // 32 KB of LDS (include/cimq.h states it: CIMQ_NET_HEAD_MAX_C)
+__device__ inline float wave_sum_fixed(float v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+__global__ __launch_bounds__(256) void net_head_kernel(const float* __restrict__ x, int C, int hw, int classes,
+                                                       const float* __restrict__ weight,
+                                                       const float* __restrict__ bias, float* __restrict__ pooled,
+                                                       float* __restrict__ logits) {
+  extern __shared__ __attribute__((aligned(16))) float pl[];  // [C]
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.x;
+  const float* xb = x + (size_t)b * C * hw;
+  const float n = (float)hw;
+  for (int c = wave; c < C; c += 4) {
+    const float* src = xb + (size_t)c * hw;
+    float s = 0.f;
+    if ((hw & 3) == 0) {
+      for (int e = 4 * lane; e < hw; e += 256) {
+        const float4 v = *reinterpret_cast<const float4*>(src + e);
+        s += v.x;
+        s += v.y;
+        s += v.z;
+        s += v.w;
+      }
+    } else {
+      for (int e = lane; e < hw; e += 64) s += src[e];
+    }
+    s = wave_sum_fixed(s);
+    const float p = __fdiv_rn(s, n);
+    if (lane == 0) {
+      pl[c] = p;
+      if (pooled) pooled[(size_t)b * C + c] = p;
+    }
+  }
+  __syncthreads();
+  for (int k = wave; k < classes; k += 4) {
+    const float* wk = weight + (size_t)k * C;
+    float s = 0.f;
+    for (int c = lane; c < C; c += 64) s += wk[c] * pl[c];
+    s = wave_sum_fixed(s);
+    if (lane == 0) logits[(size_t)b * classes + k] = bias ? s + bias[k] : s;
+  }
+}
+
 __global__ void nchw_to_bpo_kernel(Geo g, const float* __restrict__ src, float* __restrict__ dst) {
   const size_t n = (size_t)g.M * g.O;
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {

@@ -48,6 +48,14 @@ int launch_fwd_v3(const Geo& g, const Plan3& p, uint8_t* ctx, const float* sw, c
   } else {
     kern = cst == 2 ? CIMQ_FWD3(2) : CIMQ_FWD3(3);
   }
+  // the residual as a view (cimq_net_forward), with or without codes: the view instances, 60 + that (last, so that
+  // the others keep their order)
+  if (ep && ep->rvw1) {
+    if (cst == 0) kern = CIMQ_FWD3(60);
+    else if constexpr (NBP == 8) kern = cst == 9 ? cim_fwd_v3_kernel<8, KS, 69, 1> : cim_fwd_v3_kernel<8, KS, 78, 1>;
+    else if (cst == 12) kern = obm == 1 ? cim_fwd_v3_kernel<NBP, KS, 72, 1> : cim_fwd_v3_kernel<NBP, KS, 72, 2>;
+    else kern = CIMQ_FWD3(73);
+  }
 #undef CIMQ_FWD3
   // the fused activation quantiser's word table (after the kernel's other LDS)
   const size_t lds = p.lds_fwd + (aq ? (size_t)kActLutMax * 2 * 4 : 0);

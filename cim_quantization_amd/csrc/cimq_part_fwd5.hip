@@ -19,6 +19,8 @@ int launch_fwd5(const Geo& g, const Plan5& p, uint8_t* ctx, const float* sw, con
   if (ep) kern = p.nob == 2 ? cim_fwd5_kernel<2, false, true> : cim_fwd5_kernel<1, false, true>;
   // activation codes in or out (cimq_module_forward_codes): the code instances, NOBA = 4 + NOB
   if (ep && (ep->xq || ep->oq)) kern = p.nob == 2 ? cim_fwd5_kernel<6, false, true> : cim_fwd5_kernel<5, false, true>;
+  // the residual as a view (cimq_net_forward), with or without codes: the view instances, NOBA = 8 + NOB
+  if (ep && ep->rvw1) kern = p.nob == 2 ? cim_fwd5_kernel<10, false, true> : cim_fwd5_kernel<9, false, true>;
   CIMQ_TRY(set_lds(kern, p.lds));
   // 4 waves per SIMD: two 512-thread blocks per CU (one output block each) or one 1024-thread block (two),
   // a grid-stride walk over the 128-pixel m-tiles; the output-block groups in y

@@ -74,7 +74,22 @@ struct Epi {
   const float* oalpha;   // [1]: the consumer's alpha_act
   float ogs;             // the consumer's gradient-scale factor
   float oqp;             // the consumer's clamp maximum, an integer in [1, 254]
+  // the residual as a view (cimq_net_layer's res_c0 / res_stride, the option-A shortcut): read by the code
+  // instances alone, trailing for the same reason.  rvw1 0: res has out's layout.  Otherwise res is
+  // [B, rcr, rh, rw] and out (b, o, h, w) adds res[b, o - rc0, rs * h, rs * w] where rc0 <= o < rc0 + rcr, +0.0f
+  // elsewhere.  Two packed words (two scalar registers, unpacked at the store): rvw0 = rc0 | rcr << 16,
+  // rvw1 = rh | rw << 15 | (rs - 1) << 30 (rh >= 1, so a view's rvw1 is never 0)
+  uint32_t rvw0, rvw1;
 };
+constexpr int kViewMaxDim = 32767;  // rh, rw (15 bits each); rc0, rcr fit 16 bits likewise
+struct ResView { int c0, cr, s, h, w; };
+__host__ __device__ inline ResView res_view(uint32_t w0, uint32_t w1) {
+  return ResView{(int)(w0 & 0xffffu), (int)(w0 >> 16), (int)(w1 >> 30) + 1, (int)(w1 & 0x7fffu), (int)((w1 >> 15) & 0x7fffu)};
+}
+inline void set_res_view(Epi* ep, int c0, int cr, int s, int h, int w) {
+  ep->rvw0 = (uint32_t)c0 | (uint32_t)cr << 16;
+  ep->rvw1 = (uint32_t)h | (uint32_t)w << 15 | (uint32_t)(s - 1) << 30;
+}
 
 __host__ __device__ inline int pidx(const Geo& g, int i, int j, int k, int o) {
   return ((i * g.nba + j) * g.nbw + k) * g.Opad + o;

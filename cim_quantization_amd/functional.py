@@ -975,6 +975,23 @@ def _conv_epilogue(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, s
     return (out, oq) if keep_float else oq
 
 
+def net_sizes(net):
+    """cimq_net_sizes of a ``_lib.NetDesc``: (float bytes per slot, code bytes per slot, workspace bytes).  Raises
+    CimqError where the library refuses the plan."""
+    n = max(int(net.n_slots), 1)
+    fb, cb, ws = (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)(), ctypes.c_size_t()
+    _lib.check(_lib.load().cimq_net_sizes(ctypes.byref(net), fb, cb, ctypes.byref(ws)), "cimq_net_sizes")
+    return list(fb)[:net.n_slots], list(cb)[:net.n_slots], ws.value
+
+
+def net_forward(net, x, slot_float, slot_codes, logits, ws, stream=None):
+    """cimq_net_forward: the whole plan ``net`` (a ``_lib.NetDesc``) on ``stream`` (default: torch's current one) in
+    one library call.  ``x`` / ``logits`` / ``ws``: device addresses (None where the plan has no use for one);
+    ``slot_float`` / ``slot_codes``: ``(ctypes.c_void_p * n_slots)`` arrays of device addresses."""
+    _lib.check(_lib.load().cimq_net_forward(ctypes.byref(net), x, slot_float, slot_codes, logits, ws,
+                                            _stream() if stream is None else stream), "cimq_net_forward")
+
+
 def alpha_cim_init(x, w_q, sa, sw, binary_mask, signed_act, stride, padding, nbits_a, abitslice,
                    nbits_w, wbitslice, adcbits, xbar, num_xbars):
     """First-step alpha_cim initialisation on the device (lsq.py:557-563, 35-87)."""

@@ -45,6 +45,189 @@ def _bn_versions(bn):
                  for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
 
 
+def assign_slots(steps):
+    """Activation slots by liveness.  ``steps``: the plan in execution order, each ``(reads, write)`` -- the values
+    the step reads and the one it writes (None: the head).  Returns ``({value: slot}, n_slots)``: a value keeps its
+    slot until its last reader has run, a step's output never takes the slot of a value that step reads, and the
+    lowest free slot is taken -- so the peak is the largest number of values alive at once, not one per layer.
+    Values that no step writes (the net's input) get no slot."""
+    last = {}
+    for t, (reads, write) in enumerate(steps):
+        for v in reads:
+            last[v] = t
+        if write is not None:
+            last.setdefault(write, t)
+    slot_of, holder = {}, []  # holder[s]: the value in slot s
+    for t, (reads, write) in enumerate(steps):
+        if write is None:
+            continue
+        free = [s for s, v in enumerate(holder) if last[v] < t]
+        if free:
+            s = free[0]
+            holder[s] = write
+        else:
+            s = len(holder)
+            holder.append(write)
+        slot_of[write] = s
+    return slot_of, len(holder)
+
+
+def resnet_steps(blocks_per_stage):
+    """``assign_slots``' steps of a harness ResNet run as one cimq_net_forward plan: value i is conv i's output, a
+    block's second conv also reads the block's input (the shortcut is a view of it, not a tensor of its own), the
+    head reads the last conv's."""
+    steps = [((), 0)]  # conv1 reads x
+    v = 0
+    for _ in range(3 * blocks_per_stage):
+        steps.append(((v,), v + 1))          # blk.conv1
+        steps.append(((v + 1, v), v + 2))    # blk.conv2 + shortcut(block input)
+        v += 2
+    steps.append(((v,), None))
+    return steps
+
+
+class _NetPlan:
+    """One cimq_net_forward plan of a FusedEval: the ctypes structures, everything they point to (kept alive here)
+    and the arena behind the slots.  ``run(x)`` is one library call."""
+
+    def __init__(self, fused, x):
+        import ctypes
+
+        from .. import _lib
+        from .. import functional as CF
+        from .models import PadShortcut
+        m = fused.model
+        chain, names = fused._chain_of()
+        dev = x.device
+        self.keep = []
+        self.code_edges = []
+        n = len(chain)
+        steps = resnet_steps(len(m.layer1))
+        if len(steps) != n + 1:
+            raise _NoPlan("the model is not three equal stages of basic blocks")
+        slot_of, n_slots = assign_slots(steps)
+        layers = (_lib.NetLayer * n)()
+        shape = tuple(x.shape)
+        shapes, block_shape = [], None
+        for i, (conv, bn, blk) in enumerate(chain):
+            probe = torch.empty(1, dtype=torch.uint8, device=dev).expand(shape)
+            if not getattr(conv, "fused_epilogue_ready", lambda t: False)(probe):
+                raise _NoPlan("a conv is off the library path")
+            if conv.adc_shift or conv.stochastic_quant:
+                raise _NoPlan("shift-ADC and stochastic-ADC layers run in the loop")
+            ps = (conv.weight, conv.alpha_act, conv.alpha_weight, conv.alpha_cim)
+            if any(t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev) for t in ps):
+                raise _NoPlan("parameters must be contiguous fp32 on the input's device")
+            if conv.binary_mask.device != dev:
+                conv.binary_mask = conv.binary_mask.to(dev)
+            desc, lsq = CF._prepare_descs(conv, shape, inference=True)
+            wp = conv._inf_prep = CF.inference_weights(conv, shape, conv._inf_prep)
+            lsq.wprep = wp.buf.data_ptr()
+            sizes = _lib.query_sizes(desc)
+            ctx = torch.empty(max(sizes.ctx_bytes, 1), device=dev, dtype=torch.uint8)
+            bm = conv.binary_mask.to(device=dev, dtype=torch.int8).contiguous()
+            sg = conv.signed_act.detach().to(device=dev, dtype=torch.float32).reshape(-1)[:1].contiguous()
+            scale, shift = fused.tables(bn)
+            scale, shift = scale.to(dev), shift.to(dev)
+            self.keep += [desc, lsq, wp, ctx, bm, sg, scale, shift]
+            L = layers[i]
+            L.desc, L.lsq = ctypes.pointer(desc), ctypes.pointer(lsq)
+            L.weight, L.alpha_act = conv.weight.data_ptr(), conv.alpha_act.data_ptr()
+            L.alpha_weight = conv.alpha_weight.data_ptr()
+            L.alpha_cim = None if conv.alpha_cim is None else conv.alpha_cim.data_ptr()
+            L.beta_cim = None
+            L.binary_mask, L.signed_act = bm.data_ptr(), sg.data_ptr()
+            L.scale, L.shift, L.epi_flags = scale.data_ptr(), shift.data_ptr(), _lib.CIMQ_EPI_RELU
+            L.in_slot = -1 if i == 0 else slot_of[i - 1]
+            L.out_slot, L.out_mode, L.consumer, L.in_codes = slot_of[i], 1, 0, 0
+            L.res_slot, L.res_c0, L.res_stride, L.reserved = -1, 0, 1, 0
+            L.ctx = ctx.data_ptr()
+            if i > 0 and blk is None:
+                block_shape = shape  # a block's first conv: its input feeds the block's shortcut too
+            ho = (shape[2] + 2 * conv.padding[0] - conv.weight.shape[2]) // conv.stride[0] + 1
+            wo = (shape[3] + 2 * conv.padding[1] - conv.weight.shape[3]) // conv.stride[1] + 1
+            out_shape = (shape[0], conv.out_channels, ho, wo)
+            if blk is not None:  # the shortcut: the block's input (value i - 2) as a view
+                L.res_slot = slot_of[i - 2]
+                if isinstance(blk.shortcut, PadShortcut):
+                    L.res_c0, L.res_stride = int(blk.shortcut.extra), 2
+                elif isinstance(blk.shortcut, nn.Sequential) and len(blk.shortcut) == 0:
+                    if tuple(block_shape) != out_shape:
+                        raise _NoPlan("an identity shortcut of another shape")
+                else:
+                    raise _NoPlan("a shortcut that is neither the identity nor option A")
+            shapes.append((shape, out_shape))
+            shape = out_shape
+        if shape[2] != shape[3]:
+            raise _NoPlan("the final map is not square (ResNet.forward pools with kernel W)")
+        # activation codes on the conv -> conv edges, by FusedEval's edge rules
+        if fused.codes:
+            for i in range(n - 1):
+                conv, nxt = chain[i][0], chain[i + 1][0]
+                pin = torch.empty(1, dtype=torch.uint8, device=dev).expand(shapes[i][0])
+                pout = torch.empty(1, dtype=torch.uint8, device=dev).expand(shapes[i][1])
+                if not (conv.codes_ready(pin)[1] and nxt.codes_ready(pout)[0]):
+                    continue
+                only_codes = chain[i + 1][2] is not None  # the next conv is a block's second: nothing else reads y
+                layers[i].out_mode, layers[i].consumer = (2 if only_codes else 3), i + 1
+                layers[i + 1].in_codes = 1
+                self.code_edges.append((names[id(conv)], names[id(nxt)], "codes" if only_codes else "float+codes"))
+        lin = m.linear
+        if not isinstance(lin, nn.Linear) or lin.weight.device != dev or lin.weight.dtype != torch.float32 or \
+                not lin.weight.is_contiguous() or lin.in_features != shape[1]:
+            raise _NoPlan("the classifier is not a contiguous fp32 nn.Linear over the last conv's channels")
+        head = _lib.NetHead()
+        head.in_slot, head.classes = slot_of[n - 1], lin.out_features
+        head.weight = lin.weight.data_ptr()
+        head.bias = None if lin.bias is None else lin.bias.data_ptr()
+        head.pooled = None
+        net = _lib.NetDesc()
+        net.n_layers, net.n_slots = n, n_slots
+        net.layers, net.head = layers, ctypes.pointer(head)
+        net.B, net.C, net.H, net.W = x.shape
+        self.keep += [layers, head]
+        try:
+            fb, cb, wsb = CF.net_sizes(net)
+        except _lib.CimqError as e:
+            raise _NoPlan(str(e))
+        # one arena behind the slots' planes and the shared workspace
+        al = lambda v: (v + 255) & ~255  # noqa: E731
+        total = sum(al(v) for v in fb) + sum(al(v) for v in cb) + al(wsb)
+        self.arena = torch.empty(max(total, 256), device=dev, dtype=torch.uint8)
+        base, off = self.arena.data_ptr(), 0
+        if base % 256:
+            raise _NoPlan("the arena is not 256-byte aligned")
+        self.slot_float, self.slot_codes = (ctypes.c_void_p * n_slots)(), (ctypes.c_void_p * n_slots)()
+        self._float_off = []
+        for s in range(n_slots):
+            self.slot_float[s] = base + off if fb[s] else None
+            self._float_off.append(off)
+            off += al(fb[s])
+        for s in range(n_slots):
+            self.slot_codes[s] = base + off if cb[s] else None
+            off += al(cb[s])
+        self.ws = base + off
+        self.net, self.n_slots, self.classes, self.batch = net, n_slots, lin.out_features, x.shape[0]
+        self.last_shape, self.last_slot = shape, slot_of[n - 1]
+        self._run = CF.net_forward
+
+    def run(self, x):
+        logits = torch.empty(self.batch, self.classes, device=x.device, dtype=torch.float32)
+        self._run(self.net, x.data_ptr(), self.slot_float, self.slot_codes, logits.data_ptr(), self.ws,
+                  torch.cuda.current_stream(x.device).cuda_stream)
+        return logits
+
+    def last_plane(self):
+        """the last conv's fp32 output as the last run left it in the arena (a view, overwritten by the next run)"""
+        nb = 4 * self.last_shape[0] * self.last_shape[1] * self.last_shape[2] * self.last_shape[3]
+        o = self._float_off[self.last_slot]
+        return self.arena[o:o + nb].view(torch.float32).view(self.last_shape)
+
+
+class _NoPlan(Exception):
+    """why a FusedEval(net=True) forward runs the loop instead"""
+
+
 class FusedEval(nn.Module):
     """Evaluation-only forward of a ``harness.models.ResNet``: conv1 and each block's two convs run
     ``forward_fused`` with their BatchNorm folded (fold_bn), the block's shortcut as the second conv's residual
@@ -59,18 +242,89 @@ class FusedEval(nn.Module):
     travels as fp32 and codes, the fp32 for the shortcut; the last conv writes fp32 only.  An edge whose producer
     cannot write codes or whose consumer cannot read them (``Conv2dLSQCiM.codes_ready``) stays fp32.
     ``code_edges``: the (producer, consumer, kind) names of the edges that carried codes in the last forward, kind
-    "codes" or "float+codes"."""
+    "codes" or "float+codes".
 
-    def __init__(self, model, codes=False):
+    ``net=True``: the whole forward is one library call (cimq_net_forward): the convs with the same arguments and
+    edge rules as the loop, each option-A shortcut read as a view of the block's input inside the epilogue of the
+    conv it adds to, and pooling + classifier in one head kernel -- no torch kernel, no Python between the launches.
+    The plan (descriptors, prepared weight sides, folded tables, ctx buffers, one arena behind the activation slots,
+    which are assigned by liveness: ``assign_slots``) is built once and reused while its key matches (``_net_state``).
+    Every conv's output is bit for bit the loop's; the logits differ from the loop's by the summation order of the
+    pooling and of the classifier alone.  Where a conv is off the library path, the library refuses the plan or the
+    final map is not square, the loop runs: ``net_used`` says which of the two the last forward was."""
+
+    def __init__(self, model, codes=False, net=False):
         super().__init__()
         if not isinstance(model, ResNet):
             raise TypeError("FusedEval wraps a harness.models.ResNet")
         self.model = model
         self.codes = bool(codes)
+        self.net = bool(net)
+        self.net_used = False   # whether the last forward ran as one cimq_net_forward call
+        self.net_reason = None  # ... and if not, why (the loop ran)
         self.code_edges = []
         self._tables = {}
         self._probe = {}
         self._chain = self._names = None
+        self._net_key = self._net_plan = None
+
+    def _chain_of(self):
+        """the convs in order, each with its BatchNorm and the block whose shortcut adds to it (None: no residual),
+        and the module names; made once, the model's modules are shared, not copied"""
+        if self._chain is None:
+            m = self.model
+            chain = [(m.conv1, m.bn1, None)]
+            for stage in (m.layer1, m.layer2, m.layer3):
+                for blk in stage:
+                    chain += [(blk.conv1, blk.bn1, None), (blk.conv2, blk.bn2, blk)]
+            self._chain = chain
+            self._names = {id(mod): name for name, mod in m.named_modules()}
+        return self._chain, self._names
+
+    def _net_state(self, x):
+        """the key a plan is reused under: the input's shape and device, whether edges carry codes, and the
+        (_version, data_ptr) of every conv parameter, BatchNorm tensor and classifier tensor; None where a conv is
+        off the library path (the loop then runs, and says so)"""
+        from ..functional import _versions
+        chain, _ = self._chain_of()
+        key = [tuple(x.shape), x.device, self.codes]
+        for conv, bn, _ in chain:
+            ready = getattr(conv, "fused_epilogue_ready", None)
+            if ready is None or not ready(x):
+                return None
+            if bn.training:
+                raise RuntimeError("FusedEval: BatchNorm in training mode (call model.eval() first)")
+            key.append(_versions(conv.weight, conv.alpha_act, conv.alpha_weight, conv.alpha_cim, conv.binary_mask,
+                                 conv.signed_act))
+            key.append(_bn_versions(bn))
+        lin = self.model.linear
+        key.append(_versions(getattr(lin, "weight", None), getattr(lin, "bias", None)))
+        return tuple(key)
+
+    def _forward_net(self, x):
+        """the forward as one library call, or None where the loop has to run (``net_reason`` says why)"""
+        if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
+            self.net_reason = "not a ROCm NCHW input"
+            return None
+        key = self._net_state(x)
+        if key is None:
+            self.net_reason = "a conv is off the library path"
+            return None
+        if key != self._net_key:
+            self._net_key, self._net_plan = key, None
+            try:
+                self._net_plan = _NetPlan(self, x)
+                self.net_reason = None
+            except _NoPlan as e:
+                self.net_reason = str(e)
+        plan = self._net_plan
+        if plan is None:
+            return None
+        xc = x if (x.dtype == torch.float32 and x.is_contiguous() and x.data_ptr() % 16 == 0) else \
+            x.to(torch.float32).contiguous().clone()
+        y = plan.run(xc)
+        self.code_edges = list(plan.code_edges)
+        return y
 
     def tables(self, bn):
         if bn.training:
@@ -96,16 +350,7 @@ class FusedEval(nn.Module):
     def _forward_codes(self, x):
         """forward with activation codes on the conv -> conv edges (see the class)."""
         m = self.model
-        if self._chain is None:
-            # the convs in order, each with its BatchNorm and the block whose shortcut adds to it (None: no
-            # residual); made once, the model's modules are shared, not copied
-            chain = [(m.conv1, m.bn1, None)]
-            for stage in (m.layer1, m.layer2, m.layer3):
-                for blk in stage:
-                    chain += [(blk.conv1, blk.bn1, None), (blk.conv2, blk.bn2, blk)]
-            self._chain = chain
-            self._names = {id(mod): name for name, mod in m.named_modules()}
-        chain, names = self._chain, self._names
+        chain, names = self._chain_of()
         self.code_edges = []
         y, q = x, None  # the current activation: fp32 (None where only codes exist) and codes for chain[i]'s conv
         block_in = None  # fp32 input of the current block, for its shortcut
@@ -152,6 +397,11 @@ class FusedEval(nn.Module):
     def forward(self, x):
         if torch.is_grad_enabled():
             raise RuntimeError("FusedEval is evaluation only: call it under torch.no_grad()")
+        if self.net:
+            y = self._forward_net(x)
+            self.net_used = y is not None
+            if y is not None:
+                return y
         if self.codes:
             return self._forward_codes(x)
         m = self.model

@@ -47,6 +47,9 @@ def get_base_parser():
     p.add_argument("--fused-codes", action="store_true",
                    help="--fused-eval with the activations handed from conv to conv as low-bit codes "
                         "(FusedEval(model, codes=True))")
+    p.add_argument("--fused-net", action="store_true",
+                   help="--fused-eval with each forward as one library call (FusedEval(model, net=True): "
+                        "cimq_net_forward; combines with --fused-codes)")
     return p
 
 
@@ -193,21 +196,25 @@ def train_epoch(loader, model, criterion, optimizer, epoch, hp, max_steps=0, log
     return loss_sum / max(seen, 1), top1 / max(seen, 1)
 
 
-def validate(loader, model, criterion, hp, max_steps=0, fused=False, codes=False):
+def validate(loader, model, criterion, hp, max_steps=0, fused=False, codes=False, net=False):
     """main_lsq.py's validate(): top-1 / top-5 accuracy and mean loss in eval mode under no_grad.
     Nothing here selects the evaluation path: under no_grad every Conv2dLSQCiM runs libcimq's
     forward-only mode by itself (CIMQ_OPT_INFERENCE: same outputs, no backward state) and keeps its
     prepared weight side across the batches, so the weights are quantised once per input shape.
     ``fused``: evaluate through harness.fuse.FusedEval instead (folded BatchNorm, residual add and ReLU in the
     conv kernels' epilogue; not bit-identical to the BatchNorm path, see that module).  ``codes`` (with
-    ``fused``): FusedEval(model, codes=True) -- activation codes between the convs, the same logits."""
+    ``fused``): FusedEval(model, codes=True) -- activation codes between the convs, the same logits.  ``net``
+    (with ``fused``): FusedEval(model, net=True) -- each forward one cimq_net_forward call; the convs' outputs are
+    the loop's, the logits differ by the head's summation order alone."""
     model.eval()
     if codes and not fused:
         raise ValueError("validate: codes=True needs fused=True")
+    if net and not fused:
+        raise ValueError("validate: net=True needs fused=True")
     if fused:
         from .fuse import FusedEval
         bare = model.module if isinstance(model, nn.parallel.DistributedDataParallel) else model
-        model = FusedEval(bare, codes=codes)
+        model = FusedEval(bare, codes=codes, net=net)
     seen, loss_sum, c1, c5 = 0, 0.0, 0.0, 0.0
     with torch.no_grad():
         for i, (x, y) in enumerate(loader):
@@ -256,7 +263,8 @@ def main(argv=None):
     train_loader = CifarLoader(xtr, ytr, batch, device, train=True, seed=seed, rank=rank, world=world)
     val_loader = CifarLoader(xte, yte, batch, device, train=False)
     log = print if rank == 0 else (lambda *a, **k: None)
-    ev = dict(fused=args.fused_eval or args.fused_codes, codes=args.fused_codes)  # how validate evaluates
+    ev = dict(fused=args.fused_eval or args.fused_codes or args.fused_net, codes=args.fused_codes,
+              net=args.fused_net)  # how validate evaluates
     if hp.evaluate:
         acc1, acc5, _ = validate(val_loader, model, criterion, hp, args.max_val_steps, **ev)
         log(f" * Acc@1 {acc1:.3f} Acc@5 {acc5:.3f}")

@@ -334,6 +334,87 @@ int cimq_module_forward_codes(const cimq_conv_desc* d, const cimq_lsq_desc* q, c
                               const int8_t* binary_mask, const float* signed_act, const cimq_epilogue* epi,
                               float* out, void* ctx, void* ws, void* stream);
 
+/* ---- a whole fused evaluation network in one call (cimq_net_abi() == 1; CIMQ_ABI_VERSION / _MINOR unchanged) ----
+ *
+ * A plan is a list of conv layers that run in order on one stream, the activation slots they read and write, and an
+ * optional head (global average pool + classifier).  Layer i is exactly the cimq_module_forward_codes call with these
+ * arguments (cimq_module_forward_epilogue for a float-only edge): the same code path, and every float plane and code
+ * plane it writes is bit for bit what that call writes.  A slot is a pair of caller-owned device buffers: a float
+ * plane ([B, O, Ho, Wo] fp32) and a code plane (one byte per element), each 16-byte aligned and as large as
+ * cimq_net_sizes reports; a slot may be reused once its last reader has run.
+ *
+ * The residual is a whole tensor of the output's shape, or a view of a larger one (ResNet's option-A shortcut,
+ * F.pad(src[:, :, ::s, ::s], channels)): with the source [B, Cr, Hr, Wr] in res_slot, out (b, o, h, w) adds
+ * src[b, o - res_c0, s h, s w] where res_c0 <= o < res_c0 + Cr and +0.0f elsewhere (a real add: -0.0 becomes +0.0),
+ * read in the epilogue of the kernel that stores the output -- bit for bit the add of the materialised tensor. */
+#define CIMQ_NET_HEAD_MAX_C 8192 /* cimq_net_head: the pooled features of one image live in LDS (32 KB) */
+
+typedef struct cimq_net_layer {
+  const cimq_conv_desc* desc; /* CIMQ_OPT_INFERENCE set */
+  const cimq_lsq_desc* lsq;   /* wprep as for cimq_module_forward_codes */
+  const float* weight;
+  const float* alpha_act;
+  const float* alpha_weight;
+  const float* alpha_cim;
+  const float* beta_cim;
+  const int8_t* binary_mask;
+  const float* signed_act;
+  const float* scale; /* cimq_epilogue's scale, shift, flags */
+  const float* shift;
+  int32_t epi_flags;
+  int32_t in_slot;    /* -1: the net's input x; else an activation slot */
+  int32_t in_codes;   /* 1: read the slot's code plane (x_codes) */
+  int32_t out_slot;
+  int32_t out_mode;   /* 1 float, 2 codes, 3 both; the codes are for layer ``consumer``'s quantiser */
+  int32_t consumer;   /* a layer index in (i, n_layers) whose in_slot is this out_slot; used when out_mode & 2 */
+  int32_t res_slot;   /* -1: no residual; else the slot whose float plane is the residual's source */
+  int32_t res_c0;     /* the output channel that the source's channel 0 adds to */
+  int32_t res_stride; /* 1 or 2 */
+  int32_t reserved;   /* 0 */
+  void* ctx;          /* this layer's ctx (cimq_query_sizes), caller-owned */
+} cimq_net_layer;
+
+typedef struct cimq_net_head { /* global average pool over H x W, then y = W p + b */
+  int32_t in_slot;     /* the slot whose float plane is pooled; -1: x itself (a head-only net, n_layers == 0) */
+  int32_t classes;
+  const float* weight; /* [classes, C] */
+  const float* bias;   /* NULL or [classes] */
+  float* pooled;       /* NULL, or [B, C]: the pooled features, also written */
+  int32_t reserved[2]; /* 0 */
+} cimq_net_head;
+
+typedef struct cimq_net_desc {
+  int32_t n_layers, n_slots;
+  const cimq_net_layer* layers;
+  const cimq_net_head* head; /* may be NULL */
+  int32_t B, C, H, W;        /* shape of x */
+} cimq_net_desc;
+
+/* 1 where the cimq_net_* calls exist (a library from before them has no such symbol). */
+int cimq_net_abi(void);
+
+/* Validates the plan (as cimq_net_forward does, but for the buffers) and reports, per slot, the bytes of the largest
+ * float plane and of the largest code plane stored in it (0 where that plane is never stored) -- two arrays of
+ * n_slots entries, either may be NULL -- and the shared workspace: the largest of the layers' forward workspaces
+ * (the head needs none). */
+int cimq_net_sizes(const cimq_net_desc* net, size_t* slot_float_bytes, size_t* slot_code_bytes, size_t* ws_bytes);
+
+/* Runs the plan on ``stream``: the layers in order, then the head into logits [B, classes].  slot_float /
+ * slot_codes: host arrays of n_slots device pointers (an entry may be NULL where cimq_net_sizes reports 0; either
+ * array may be NULL when n_slots is 0).  The plan is validated completely before the first launch and a refused plan
+ * launches nothing.  The call allocates nothing, does not synchronise and reads no device memory on the host.
+ * CIMQ_EINVAL: a NULL where a pointer is required; n_layers < 0, or n_layers == 0 without a head; a slot index out of
+ * range; a layer or head reading a slot, or a plane of a slot, that no earlier layer wrote; a producer's output shape
+ * that differs from the consumer's descriptor or from x's; out_slot equal to the layer's in_slot or res_slot; a
+ * consumer outside (i, n_layers) or whose in_slot is not this out_slot; out_mode outside 1..3; in_codes outside 0..1;
+ * res_stride not 1 or 2; a residual source whose [ceil(Hr / s), ceil(Wr / s)] is not [Ho, Wo] or whose batch is not
+ * B; res_c0 < 0 or res_c0 + Cr > O; a non-zero reserved; a buffer that is not 16-byte aligned; classes < 1; every
+ * refusal of the per-layer call.  CIMQ_EUNSUPPORTED: what cimq_module_codes_supported refuses; a stochastic-ADC layer
+ * (its seed is per call); a residual view (res_stride 2, or Cr != O) on the dense route, or on the fwd5 / v3 routes
+ * with an output width that is no multiple of 4; a head over more than CIMQ_NET_HEAD_MAX_C channels. */
+int cimq_net_forward(const cimq_net_desc* net, const float* x, void* const* slot_float, void* const* slot_codes,
+                     float* logits, void* ws, void* stream);
+
 /* One layer of cimq_module_prepare: its descriptors (as the forward will receive them; the
  * lsq descriptor's wprep and flags are ignored here) and raw parameters, and its output buffer
  * ``wprep`` (cimq_sizes.wprep_bytes, caller-owned device memory). */

@@ -1,0 +1,534 @@
+"""GPU: a whole fused evaluation network in one library call (cimq_net_forward) -- every plane a layer of a plan
+writes is bit for bit what Conv2dLSQCiM.forward_fused writes for the same arguments (fp32 and codes, on the fwd5,
+v3 and general routes), the option-A shortcut read as a view inside the storing kernel equals the add of the
+materialised F.pad(src[:, :, ::s, ::s]) down to the sign of zero, the head's pooled features and logits sit inside
+bars derived from the fp32 format, and FusedEval(model, net=True) / validate(net=True) run ResNet-20 as one call.
+
+A plan's layer may only read what an earlier layer of the plan wrote, so the smallest net that shows a case
+layer's codes has a second layer that consumes them; that second layer also takes the case layer's fp32 plane as
+a whole-tensor residual.  The view tests run the three-layer shape of a ResNet block: a layer that writes the
+view's source, a strided layer that writes the case layer's input, and the case layer.
+Shapes: test_inference_host.CASES (the smallest that reach each route)."""
+import ctypes
+
+import pytest
+import torch
+import torch.nn.functional as TF
+
+from test_gpu_codes import KW, _second
+from test_gpu_epilogue import _fused, _net, _plain, _tables
+from test_gpu_inference import _case, _check_route, _route0
+from test_inference_host import CASES, INF
+
+pytestmark = pytest.mark.gpu
+
+U = 2.0 ** -24
+
+
+def _gamma(n):
+    return n * U / (1 - n * U)
+
+
+def _F():
+    from cim_quantization_amd import functional as F
+    return F
+
+
+def _L():
+    import cim_quantization_amd._lib as L
+    return L
+
+
+def _mk(dev, cin, cout, stride, x, seed):
+    """a fresh w3a3 Conv2dLSQCiM cin -> cout (3 x 3, pad 1) after its first-step initialisation on input x"""
+    import cim_quantization_amd._modules as my_nn
+    torch.manual_seed(seed)
+    m = my_nn.Conv2dLSQCiM(cin, cout, 3, stride, 1, bias=False, **KW)
+    torch.nn.init.kaiming_normal_(m.weight)
+    m = m.to(dev).train()
+    m(x)
+    return m
+
+
+class _Plan:
+    """a cimq_net_forward plan over real buffers: add layers in order, then run()"""
+
+    def __init__(self, x):
+        self.x = x.contiguous()
+        self.dev = x.device
+        self.items, self.keep = [], []
+        self.sf, self.sc = [], []  # per slot: the fp32 plane / the code plane (a tensor or None)
+        self.head = None
+        self.logits = None
+
+    def slot(self, shape, flt=True, codes=False):
+        self.sf.append(torch.full(shape, 7.0, device=self.dev) if flt else None)
+        self.sc.append(torch.full(shape, 99, device=self.dev, dtype=torch.uint8) if codes else None)
+        return len(self.sf) - 1
+
+    def layer(self, m, in_shape, scale, shift, relu, in_slot, out_slot, out_mode=1, consumer=0, in_codes=0,
+              res_slot=-1, res_c0=0, res_stride=1):
+        F, L = _F(), _L()
+        if m.adc_shift:
+            desc, lsq = F._shift_module_descs(tuple(in_shape), m.weight, m.stride, m.padding, m.dilation, m.nbits_a,
+                                              m.abitslice, m.nbits_w, m.wbitslice, m.xbar, m.nbits_alpha)
+        else:
+            desc, lsq = F._module_descs(tuple(in_shape), m.weight, m.stride, m.padding, m.dilation, m.nbits_a,
+                                        m.abitslice, m.nbits_w, m.wbitslice, m.adcbits, m.xbar, m.nbits_alpha,
+                                        m.alpha_cim is not None, False)
+        desc.options = INF
+        sizes = L.query_sizes(desc)
+        ctx = torch.empty(max(sizes.ctx_bytes, 1), device=self.dev, dtype=torch.uint8)
+        t = dict(weight=m.weight.detach().contiguous(), alpha_act=m.alpha_act.detach().reshape(-1)[:1].contiguous(),
+                 alpha_weight=m.alpha_weight.detach().reshape(-1)[:1].contiguous(),
+                 alpha_cim=None if m.alpha_cim is None else m.alpha_cim.detach().contiguous(),
+                 beta_cim=m.beta_cim.detach().contiguous() if m.adc_shift else None,
+                 binary_mask=m.binary_mask.to(device=self.dev, dtype=torch.int8).contiguous(),
+                 signed_act=m.signed_act.detach().to(torch.float32).reshape(-1)[:1].contiguous(),
+                 scale=scale.contiguous(), shift=shift.contiguous(), ctx=ctx)
+        self.keep.append((desc, lsq, t))
+        self.items.append(dict(desc=desc, lsq=lsq, t=t, epi_flags=L.CIMQ_EPI_RELU if relu else 0, in_slot=in_slot,
+                               in_codes=in_codes, out_slot=out_slot, out_mode=out_mode, consumer=consumer,
+                               res_slot=res_slot, res_c0=res_c0, res_stride=res_stride, ws=sizes.fwd_workspace_bytes))
+
+    def set_head(self, in_slot, weight, bias, classes, pooled=None):
+        L = _L()
+        h = L.NetHead()
+        h.in_slot, h.classes = in_slot, classes
+        h.weight, h.bias = weight.data_ptr(), None if bias is None else bias.data_ptr()
+        h.pooled = None if pooled is None else pooled.data_ptr()
+        self.keep.append((weight, bias, pooled))
+        self.head = h
+        self.logits = torch.full((self.x.shape[0] if in_slot < 0 else self.sf[in_slot].shape[0], classes), 7.0,
+                                 device=self.dev)
+
+    def pack(self):
+        L = _L()
+        n = len(self.items)
+        layers = (L.NetLayer * max(n, 1))()
+        for lay, it in zip(layers, self.items):
+            lay.desc, lay.lsq = ctypes.pointer(it["desc"]), ctypes.pointer(it["lsq"])
+            for k, v in it["t"].items():
+                setattr(lay, k, None if v is None else v.data_ptr())
+            for k in ("epi_flags", "in_slot", "in_codes", "out_slot", "out_mode", "consumer", "res_slot", "res_c0",
+                      "res_stride"):
+                setattr(lay, k, it[k])
+            lay.reserved = 0
+        net = L.NetDesc()
+        net.n_layers, net.n_slots = n, len(self.sf)
+        net.layers = ctypes.cast(layers, ctypes.POINTER(L.NetLayer))
+        net.head = ctypes.pointer(self.head) if self.head is not None else None
+        net.B, net.C, net.H, net.W = self.x.shape
+        self.keep.append(layers)
+        return net
+
+    def run(self, expect=0):
+        L = _L()
+        net = self.pack()
+        fb, cb, wsb = (_F().net_sizes(net) if expect == 0 else ([], [], 1 << 20))
+        if expect == 0:  # the buffers are exactly what cimq_net_sizes asks for, or larger where a slot is reused
+            for s in range(len(self.sf)):
+                assert (0 if self.sf[s] is None else self.sf[s].numel() * 4) >= fb[s]
+                assert (0 if self.sc[s] is None else self.sc[s].numel()) >= cb[s]
+            assert wsb == max([it["ws"] for it in self.items] + [0])
+        ws = torch.empty(max(wsb, 16), device=self.dev, dtype=torch.uint8)
+        n = max(len(self.sf), 1)
+        p = lambda u: None if u is None else u.data_ptr()  # noqa: E731
+        sf = (ctypes.c_void_p * n)(*[p(u) for u in self.sf])
+        sc = (ctypes.c_void_p * n)(*[p(u) for u in self.sc])
+        rc = L.load().cimq_net_forward(ctypes.byref(net), p(self.x), sf, sc, p(self.logits), p(ws),
+                                       torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert rc == expect, (rc, L.load().cimq_last_error())
+        return rc
+
+
+def _bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+# ---------------------------------------------------------------------------------------------------
+# 1. a case layer and the layer that consumes its codes
+# ---------------------------------------------------------------------------------------------------
+NET_CASES = [n for n in CASES if CASES[n][-1] in ("fwd5", "v3", "general")]
+
+
+@pytest.mark.parametrize("name", NET_CASES)
+def test_layer_planes(cuda_device, name):
+    m, x, _ = _case(name, cuda_device)
+    _check_route(name, m, x)
+    v = _plain(m, x)
+    s1, t1, _ = _tables(v, 500 + sum(map(ord, name)))
+    y1 = _fused(m, x, s1, t1, relu=True)
+    O = y1.shape[1]
+    cons = _mk(cuda_device, O, O, 1, y1, 600 + sum(map(ord, name)))
+    v2 = _plain(cons, y1)
+    s2, t2, _ = _tables(v2, 501)
+    try:
+        m.eval()
+        cons.eval()
+        yf, q = _fused(m, x, s1, t1, relu=True, out_quant=cons)
+        assert torch.equal(yf, y1)
+        want2 = _fused(cons, q, s2, t2, residual=y1, relu=True)
+        p = _Plan(x)
+        a = p.slot(y1.shape, codes=True)
+        b = p.slot(want2.shape)
+        p.layer(m, x.shape, s1, t1, True, -1, a, out_mode=3, consumer=1)
+        p.layer(cons, y1.shape, s2, t2, True, a, b, in_codes=1, res_slot=a)
+        runs = []
+        for _ in range(2):  # twice on the same buffers
+            p.run()
+            runs.append((p.sf[a].clone(), p.sc[a].clone(), p.sf[b].clone()))
+    finally:
+        m.train()
+        cons.train()
+    for got in runs:
+        assert torch.equal(_bits(got[0]), _bits(y1)), name
+        assert torch.equal(got[1], q), name
+        assert torch.equal(_bits(got[2]), _bits(want2)), name
+
+
+# ---------------------------------------------------------------------------------------------------
+# 2. the residual as a view
+# ---------------------------------------------------------------------------------------------------
+#            case,  route,     source [B, Cr, Hr, Wr], c0, s
+VIEW_CASES = {
+    "l2": ("l2", "fwd5", (1, 16, 32, 32), 8, 2),
+    "l3": ("l3", "fwd5", (2, 32, 16, 16), 16, 2),
+    "w2a2": ("w2a2", "v3", (2, 8, 32, 32), 4, 2),
+    "w2a2-odd": ("w2a2", "v3", (2, 8, 31, 31), 4, 2),
+    "c48": ("c48", "general", (1, 24, 32, 32), 12, 2),
+    "l2-edge0": ("l2", "fwd5", (1, 16, 32, 32), 0, 2),
+    "l2-edge16": ("l2", "fwd5", (1, 16, 32, 32), 16, 2),
+    "l1-partial": ("l1", "fwd5", (1, 8, 32, 32), 4, 1),
+}
+
+
+@pytest.mark.parametrize("key", list(VIEW_CASES))
+def test_residual_view(cuda_device, key):
+    name, route, src_shape, c0, s = VIEW_CASES[key]
+    dev = cuda_device
+    B, Cr, Hr, Wr = src_shape
+    Bc, C, O, H = CASES[name][:4]
+    assert Bc == B
+    m = _second(name, dev, B)  # a fresh layer of the case's shape (the cached one is shared with other tests)
+    seed = 700 + sum(map(ord, key))
+    x0 = torch.randn(B, 16, Hr, Wr, generator=torch.Generator().manual_seed(seed)).relu().to(dev)
+    p1 = _mk(dev, 16, Cr, 1, x0, seed + 1)              # writes the view's source
+    sa, ta, _ = _tables(_plain(p1, x0), seed + 2)
+    y0 = _fused(p1, x0, sa, ta, relu=True)
+    assert tuple(y0.shape) == src_shape
+    p2 = _mk(dev, Cr, C, s, y0, seed + 3)               # writes the case layer's input
+    sb, tb, _ = _tables(_plain(p2, y0), seed + 4)
+    y1 = _fused(p2, y0, sb, tb, relu=True)
+    assert tuple(y1.shape) == (B, C, H, H)
+    assert _route0(m, y1) == route
+    v = _plain(m, y1)
+    sc, tc, _ = _tables(v, seed + 5)
+    # one channel outside the view with scale 0 and shift -0.0: v * 0 + -0.0 is -0.0 wherever v < 0, and only the
+    # add of the padded +0.0 makes it +0.0
+    z = O - 1 if c0 + Cr < O else 0
+    assert not (c0 <= z < c0 + Cr)
+    sc[z], tc[z] = 0.0, -0.0
+    pad = TF.pad(y0[:, :, ::s, ::s], (0, 0, 0, 0, c0, O - c0 - Cr))
+    assert tuple(pad.shape) == tuple(v.shape)
+    for relu in (True, False):
+        want = _fused(m, y1, sc, tc, residual=pad, relu=relu)
+        bare = _fused(m, y1, sc, tc, relu=relu)
+        assert bool((_bits(bare[:, z]) == -2 ** 31).any()) and bool((_bits(want[:, z]) == 0).all())
+        try:
+            for mod in (p1, p2, m):
+                mod.eval()
+            p = _Plan(x0)
+            a, b, c = p.slot(y0.shape), p.slot(y1.shape), p.slot(want.shape)
+            p.layer(p1, x0.shape, sa, ta, True, -1, a)
+            p.layer(p2, y0.shape, sb, tb, True, a, b)
+            p.layer(m, y1.shape, sc, tc, relu, b, c, res_slot=a, res_c0=c0, res_stride=s)
+            p.run()
+            first = p.sf[c].clone()
+            p.run()
+        finally:
+            for mod in (p1, p2, m):
+                mod.train()
+        assert torch.equal(_bits(p.sf[a]), _bits(y0)) and torch.equal(_bits(p.sf[b]), _bits(y1))
+        assert torch.equal(_bits(p.sf[c]), _bits(want)), (key, relu, float((p.sf[c] - want).abs().max()))
+        assert torch.equal(_bits(first), _bits(p.sf[c]))
+
+
+def test_dense_refuses_view(cuda_device):
+    """a residual view on the dense route: CIMQ_EUNSUPPORTED, nothing launched, no buffer touched"""
+    L = _L()
+    m, x, _ = _case("dense", cuda_device)
+    _check_route("dense", m, x)
+    v = _plain(m, x)
+    s1, t1, _ = _tables(v, 800)
+    try:
+        m.eval()
+        p = _Plan(x)
+        a, b = p.slot(v.shape), p.slot(v.shape)
+        p.layer(m, x.shape, s1, t1, True, -1, a)
+        p.layer(m, x.shape, s1, t1, True, a, b, res_slot=a, res_stride=2)
+        assert p.run(expect=L.CIMQ_EUNSUPPORTED) == L.CIMQ_EUNSUPPORTED
+    finally:
+        m.train()
+    assert b"dense" in L.load().cimq_last_error()
+    assert bool((p.sf[a] == 7.0).all()) and bool((p.sf[b] == 7.0).all())
+
+
+# ---------------------------------------------------------------------------------------------------
+# 3. two-layer chains through codes alone
+# ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("prod,cons", [("l1", "l1"), ("l2s2", "l2"), ("l3", "l3"), ("conv1", "l1"), ("c48", "c48")])
+def test_chain_codes_only(cuda_device, prod, cons):
+    m1, x, _ = _case(prod, cuda_device)
+    _check_route(prod, m1, x)
+    m2 = _second(cons, cuda_device, x.shape[0])
+    s1, t1, _ = _tables(_plain(m1, x), 40)
+    y1 = _fused(m1, x, s1, t1, relu=True)
+    with torch.no_grad():  # (the consumer's step size to the scale of what it is fed)
+        m2.alpha_act.fill_(float(y1[y1 > 0].mean()) / 2)
+    s2, t2, _ = _tables(_plain(m2, y1), 41)
+    want = _fused(m2, y1, s2, t2, relu=True)  # the chain through fp32
+    try:
+        m1.eval()
+        m2.eval()
+        p = _Plan(x)
+        a = p.slot(y1.shape, flt=False, codes=True)
+        b = p.slot(want.shape)
+        p.layer(m1, x.shape, s1, t1, True, -1, a, out_mode=2, consumer=1)
+        p.layer(m2, y1.shape, s2, t2, True, a, b, in_codes=1)
+        p.run()
+    finally:
+        m1.train()
+        m2.train()
+    assert torch.equal(p.sc[a].cpu(), m2.act_codes(y1.cpu()))
+    assert torch.equal(_bits(p.sf[b]), _bits(want))
+
+
+# ---------------------------------------------------------------------------------------------------
+# 4. the head alone
+# ---------------------------------------------------------------------------------------------------
+def _head_bars(y, pooled, w, b):
+    """(pooled bar, logit bar) from the fp32 format: any order of HW - 1 additions and one division, and any order
+    of C products, C - 1 additions and the bias add (u = 2^-24, gamma_n = n u / (1 - n u))"""
+    y64 = y.double().cpu()
+    hw = y.shape[2] * y.shape[3]
+    pbar = _gamma(hw + 1) * y64.abs().sum(dim=(2, 3)) / hw
+    p64, w64 = pooled.double().cpu(), w.double().cpu()
+    terms = (w64.abs().unsqueeze(0) * p64.abs().unsqueeze(1)).sum(dim=2)
+    if b is not None:
+        terms = terms + b.double().cpu().abs().unsqueeze(0)
+    return pbar, _gamma(y.shape[1] + 1) * terms
+
+
+def _head_check(y, pooled, logits, w, b):
+    pbar, lbar = _head_bars(y, pooled, w, b)
+    mean64 = y.double().cpu().mean(dim=(2, 3))
+    perr = (pooled.double().cpu() - mean64).abs()
+    want = pooled.double().cpu() @ w.double().cpu().t()
+    if b is not None:
+        want = want + b.double().cpu()
+    lerr = (logits.double().cpu() - want).abs()
+    print("head: max pooled error %.3e (bar %.3e), max logit error %.3e (bar %.3e)"
+          % (float(perr.max()), float(pbar.max()), float(lerr.max()), float(lbar.max())))
+    assert bool((perr <= pbar).all()) and bool((lerr <= lbar).all())
+    return float(lbar.max())
+
+
+def _run_head(y, w, b):
+    p = _Plan(y)
+    pooled = torch.full((y.shape[0], y.shape[1]), 7.0, device=y.device)
+    p.set_head(-1, w, b, w.shape[0], pooled)
+    p.run()
+    return pooled, p.logits
+
+
+@pytest.mark.parametrize("shape", [(3, 64, 8, 8), (2, 48, 5, 7), (2, 16, 1, 1)])
+@pytest.mark.parametrize("classes", [10, 1])
+@pytest.mark.parametrize("bias", [True, False])
+def test_head_alone(cuda_device, shape, classes, bias):
+    g = torch.Generator().manual_seed(sum(shape) + classes)
+    y = torch.randn(shape, generator=g).to(cuda_device)
+    w = torch.randn(classes, shape[1], generator=g).to(cuda_device)
+    b = torch.randn(classes, generator=g).to(cuda_device) if bias else None
+    pooled, logits = _run_head(y, w, b)
+    _head_check(y, pooled, logits, w, b)
+    # torch's own pooling and linear sit inside the same bars (the bar is a bar, not a fit to this kernel)
+    tp = TF.avg_pool2d(y, (shape[2], shape[3])).flatten(1)
+    tl = TF.linear(tp, w, b)
+    _head_check(y, tp, tl, w, b)
+    # two runs are equal bit for bit
+    pooled2, logits2 = _run_head(y, w, b)
+    assert torch.equal(_bits(pooled), _bits(pooled2)) and torch.equal(_bits(logits), _bits(logits2))
+
+
+def test_head_nan_stays_in_its_image(cuda_device):
+    g = torch.Generator().manual_seed(9)
+    y = torch.randn(3, 64, 8, 8, generator=g).to(cuda_device)
+    y[1, 17, 3, 5] = float("nan")
+    w = torch.randn(10, 64, generator=g).to(cuda_device)
+    b = torch.randn(10, generator=g).to(cuda_device)
+    pooled, logits = _run_head(y, w, b)
+    assert bool(torch.isnan(logits[1]).all())
+    assert bool(torch.isfinite(logits[0]).all()) and bool(torch.isfinite(logits[2]).all())
+    assert int(torch.isnan(pooled).sum()) == 1 and bool(torch.isnan(pooled[1, 17]))
+
+
+# ---------------------------------------------------------------------------------------------------
+# 5. the whole network
+# ---------------------------------------------------------------------------------------------------
+def _loop_last_plane(model, x):
+    """the last conv's fused output as FusedEval(model)'s loop computes it"""
+    from cim_quantization_amd.harness.fuse import FusedEval
+    box = {}
+    fused = FusedEval(model)
+    orig = fused._conv
+
+    def spy(conv, bn, t, residual=None):
+        y = orig(conv, bn, t, residual)
+        box["y"] = y
+        return y
+    fused._conv = spy
+    logits = fused(x)
+    return box["y"], logits
+
+
+def _logit_bar(plane, model):
+    lin = model.linear
+    tp = TF.avg_pool2d(plane, plane.shape[3]).flatten(1)
+    return float(_head_bars(plane, tp, lin.weight.detach(), lin.bias.detach())[1].max())
+
+
+def test_fused_eval_net_resnet20(cuda_device):
+    from cim_quantization_amd.harness.fuse import FusedEval
+    model, x = _net(cuda_device)
+    lin = model.linear
+    with torch.no_grad():
+        plane, loop_logits = _loop_last_plane(model, x)
+        fused = FusedEval(model, net=True)
+        got = fused(x)
+        assert fused.net_used is True, fused.net_reason
+        assert fused._net_plan.n_slots == 3
+        last = fused._net_plan.last_plane().clone()
+        assert torch.equal(_bits(last), _bits(plane))
+        # the logits: inside the head's bars of float64 arithmetic on that plane
+        pooled = TF.avg_pool2d(last, last.shape[3]).flatten(1)
+        pbar, lbar = _head_bars(last, pooled, lin.weight.detach(), lin.bias.detach())
+        mean64 = last.double().cpu().mean(dim=(2, 3))
+        want = mean64 @ lin.weight.detach().double().cpu().t() + lin.bias.detach().double().cpu()
+        # (against the float64 pooling too: its error passes through the classifier)
+        extra = (lin.weight.detach().double().cpu().abs().unsqueeze(0) * pbar.unsqueeze(1)).sum(dim=2)
+        err = (got.double().cpu() - want).abs()
+        print("net logits: max error %.3e, bar %.3e" % (float(err.max()), float((lbar + extra).max())))
+        assert bool((err <= lbar + extra).all())
+        assert torch.equal(fused(x), got)  # the plan reused: the same bits
+        # codes on the edges: the same logits, the loop's 18 edges
+        fc = FusedEval(model, net=True, codes=True)
+        gotc = fc(x)
+        assert fc.net_used is True, fc.net_reason
+        assert torch.equal(_bits(gotc), _bits(got))
+        assert torch.equal(_bits(fc._net_plan.last_plane()), _bits(plane))
+        loop = FusedEval(model, codes=True)
+        loop(x)
+        assert len(fc.code_edges) == 18 and fc.code_edges == loop.code_edges
+
+
+def test_fused_eval_net_launches(cuda_device):
+    """one forward's device kernels: the loop's library kernels and the head kernel, nothing of torch's"""
+    import importlib.util
+    import os
+
+    from conftest import REPO
+    from cim_quantization_amd.harness.fuse import FusedEval
+    spec = importlib.util.spec_from_file_location("infer_net_bench",
+                                                  os.path.join(REPO, "tools", "infer_net_bench.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    model, x = _net(cuda_device)
+    with torch.no_grad():
+        loop, net = FusedEval(model), FusedEval(model, net=True)
+        loop(x)
+        net(x)
+        n_loop = tool.count_launches(lambda: loop(x))
+        n_net = tool.count_launches(lambda: net(x))
+    assert net.net_used
+    assert "error" not in n_loop and "error" not in n_net, (n_loop, n_net)
+    print("device kernels per forward: loop %s, net %s" % (n_loop, n_net))
+    assert n_net["libcimq"] == n_loop["libcimq"] + 1  # the loop's library kernels and the head kernel
+    assert n_net["kernels"] == n_net["libcimq"]       # ... and no other kernel
+    assert n_loop["kernels"] > n_loop["libcimq"]      # (the loop runs torch kernels: shortcut, pooling, classifier)
+
+
+def test_plan_reuse_and_invalidation(cuda_device):
+    from cim_quantization_amd.harness.fuse import FusedEval
+    model, x = _net(cuda_device)
+    bn, conv = model.layer2[1].bn1, model.layer3[0].conv1
+    var0, w0 = bn.running_var.clone(), conv.weight.detach().clone()
+    try:
+        with torch.no_grad():
+            fused = FusedEval(model, net=True)
+            base = fused(x)
+            plan = fused._net_plan
+            fused(x)
+            assert fused._net_plan is plan  # reused while the key matches
+            bn.running_var.mul_(1.5)
+            a = fused(x)
+            assert fused.net_used and fused._net_plan is not plan
+            assert torch.equal(_bits(a), _bits(FusedEval(model, net=True)(x))) and not torch.equal(a, base)
+            plan = fused._net_plan
+            conv.weight.mul_(0.5)
+            b = fused(x)
+            assert fused.net_used and fused._net_plan is not plan
+            assert torch.equal(_bits(b), _bits(FusedEval(model, net=True)(x))) and not torch.equal(b, a)
+    finally:
+        with torch.no_grad():
+            bn.running_var.copy_(var0)
+            conv.weight.copy_(w0)
+    c = model.layer1[0].conv2
+    try:
+        c.fused = False
+        with torch.no_grad():
+            got = fused(x)
+            assert fused.net_used is False and fused.net_reason
+            assert torch.equal(_bits(got), _bits(FusedEval(model)(x)))
+    finally:
+        c.fused = True
+    with torch.no_grad():
+        assert torch.equal(_bits(fused(x)), _bits(base)) and fused.net_used
+
+
+def test_validate_net(cuda_device):
+    from cim_quantization_amd.harness import train
+    model, x = _net(cuda_device)
+    g = torch.Generator().manual_seed(5)
+    batches = [(torch.randn(2, 3, 32, 32, generator=g).to(cuda_device),
+                torch.randint(0, 10, (2,), generator=g).to(cuda_device)) for _ in range(3)]
+
+    class HP:
+        overfit_test = False
+
+    crit = torch.nn.CrossEntropyLoss()
+    used = []
+    from cim_quantization_amd.harness import fuse
+    orig = fuse.FusedEval.forward
+
+    def spy(self, t):
+        y = orig(self, t)
+        used.append((self.net, self.net_used))
+        return y
+    fuse.FusedEval.forward = spy
+    try:
+        got = train.validate(batches, model, crit, HP, fused=True, net=True)
+        assert used == [(True, True)] * 3
+        want = train.validate(batches, model, crit, HP, fused=True)
+    finally:
+        fuse.FusedEval.forward = orig
+    # cross-entropy moves by at most twice the largest logit change, and the logits move by the head's error alone
+    # (the convs' planes are the loop's bit for bit)
+    with torch.no_grad():
+        bar = max(_logit_bar(_loop_last_plane(model, bx)[0], model) for bx, _ in batches)
+    print("validate: loss %.9g (net) vs %.9g (loop), bound %.3e" % (got[2], want[2], 2 * bar))
+    assert abs(got[2] - want[2]) <= 2 * bar
+    assert len(got) == 3
+    with pytest.raises(ValueError):
+        train.validate(batches, model, crit, HP, net=True)

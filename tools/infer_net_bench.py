@@ -10,6 +10,12 @@ conv, xbar 128, 1.5-bit ADC) on a synthetic batch, eval mode under torch.no_grad
           the consumer's low-bit codes, one byte per element (cimq_module_forward_codes).  The rounds then run
           A, B, C, B again: the second B window gives the spread, and the bar is C <= B + spread.
 
+  side D  (--net) FusedEval(model, net=True)(x) -- side B as ONE library call (cimq_net_forward): the plan built
+          once, the option-A shortcuts read as views in the conv epilogues, pooling and the classifier in one head
+          kernel, no torch kernel and no Python between the launches.  The rounds run A, B, D, B again.
+  side E  (--net --codes) FusedEval(model, net=True, codes=True)(x) -- side D with side C's code edges; the rounds
+          run A, B, C, D, E, B again.
+
 The two sides alternate (A, B, A again per round); a window is HIP events round ``passes`` forwards, sized to at
 least --window seconds; the second A window of a round gives the run-to-run spread.  Reports the time per
 forward of both sides, the spread, the device kernel launches of one forward of each (torch.profiler), the
@@ -19,6 +25,7 @@ torch.cuda.max_memory_allocated of one forward of each.
     python tools/infer_net_bench.py [--batch 256] [--rounds 7] [--window 0.25]
                                     [--out profiles/inference/infer_net_bench_B256.json]
     python tools/infer_net_bench.py --codes    # -> profiles/inference/infer_net_bench_codes_B256.json
+    python tools/infer_net_bench.py --net --codes   # -> profiles/inference/infer_net_bench_net_B256.json
 
 Needs the GPU: there is no CPU fallback and no number without a run.
 """
@@ -88,12 +95,14 @@ def main(argv=None):
     ap.add_argument("--window", type=float, default=0.25, help="seconds per timed window (at least 0.2)")
     ap.add_argument("--no-launch-count", action="store_true")
     ap.add_argument("--codes", action="store_true", help="add side C, FusedEval(model, codes=True): A, B, C, B per round")
+    ap.add_argument("--net", action="store_true",
+                    help="add side D, FusedEval(model, net=True) (with --codes also E, net=True and codes=True)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("infer_net_bench: no ROCm device (there is no CPU fallback; nothing is measured)")
     out_path = args.out or os.path.join(REPO, "profiles", "inference",
-                                        f"infer_net_bench{'_codes' if args.codes else ''}_B{args.batch}.json")
+                                        f"infer_net_bench{'_net' if args.net else '_codes' if args.codes else ''}_B{args.batch}.json")
     dev = torch.device("cuda:0")
     model, x = build_model(args.batch, dev)
     fused = FusedEval(model)
@@ -103,6 +112,14 @@ def main(argv=None):
         coded = FusedEval(model, codes=True)
         sides["C"] = lambda: coded(x)
         order = ("A", "B", "C", "B2")
+    nets = {}
+    if args.net:
+        nets["D"] = FusedEval(model, net=True)
+        if args.codes:
+            nets["E"] = FusedEval(model, net=True, codes=True)
+        for k, f in nets.items():
+            sides[k] = (lambda f: lambda: f(x))(f)
+        order = order[:-1] + tuple(nets) + ("B2",)
     with torch.no_grad():
         ya, yb = sides["A"](), sides["B"]()
         codes_info = None
@@ -113,6 +130,14 @@ def main(argv=None):
             del yc
         diff = {"max_abs_logit_difference": float((ya - yb).abs().max()), "max_abs_logit": float(ya.abs().max()),
                 "top1_agree": float((ya.argmax(1) == yb.argmax(1)).float().mean())}
+        net_info = {}
+        for k, f in nets.items():
+            yd = f(x)
+            net_info[k] = {"net_used": bool(f.net_used), "net_reason": f.net_reason,
+                           "max_abs_logit_difference_to_B": float((yd - yb).abs().max()),
+                           "top1_agree_with_B": float((yd.argmax(1) == yb.argmax(1)).float().mean()),
+                           "code_edges": len(f.code_edges)}
+            del yd
         del ya, yb
         for fn in sides.values():
             for _ in range(3):
@@ -158,12 +183,20 @@ def main(argv=None):
         result["C_minus_B_us"] = round(med["C"] - med["B"], 1)
         result["C_not_above_B_by_more_than_spread"] = bool(med["C"] <= med["B"] + spread)
         result["codes"] = codes_info
+    if args.net:
+        result["workload"] += "; side D = FusedEval(model, net=True)(x)" + (", E = net=True, codes=True" if args.codes else "")
+        result["net"] = net_info
+        for k in nets:
+            result[f"{k}_minus_B_us"] = round(med[k] - med["B"], 1)
+            result[f"{k}_below_B_by_more_than_spread"] = bool(med[k] < med["B"] - spread)
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     with open(out_path, "w") as f:
         json.dump(result, f, indent=1)
         f.write("\n")
     keys = ("forward_us", "spread_us", "B_minus_A_us", "kernel_launches_per_forward", "peak_memory_bytes",
             "fused_vs_batchnorm_path") + (("C_minus_B_us", "C_not_above_B_by_more_than_spread", "codes") if args.codes else ())
+    if args.net:
+        keys += ("net",) + tuple(f"{k}_minus_B_us" for k in nets) + tuple(f"{k}_below_B_by_more_than_spread" for k in nets)
     print(json.dumps({k: result[k] for k in keys}))
     return result
 

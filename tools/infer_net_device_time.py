@@ -1,5 +1,6 @@
-"""Where a fused evaluation forward spends its time, on the MI355X: for sides B = FusedEval(model) and
-C = FusedEval(model, codes=True) of tools/infer_net_bench.py (same network, same batch, eval + no_grad),
+"""Where a fused evaluation forward spends its time, on the MI355X: for sides B = FusedEval(model),
+C = FusedEval(model, codes=True), D = FusedEval(model, net=True) and E = FusedEval(model, net=True, codes=True) of
+tools/infer_net_bench.py (same network, same batch, eval + no_grad),
 
   * the host time to issue one forward with the device left behind (50 forwards, no synchronisation inside) and
     the wall time per forward of the same loop once the device has drained;
@@ -68,9 +69,11 @@ def main(argv=None):
     out_path = args.out or os.path.join(REPO, "profiles", "inference", f"infer_net_device_time_B{args.batch}.json")
     model, x = nb.build_model(args.batch, torch.device("cuda:0"))
     with torch.no_grad():
-        sides = {"B": measure(FusedEval(model), x), "C": measure(FusedEval(model, codes=True), x)}
+        sides = {"B": measure(FusedEval(model), x), "C": measure(FusedEval(model, codes=True), x),
+                 "D": measure(FusedEval(model, net=True), x), "E": measure(FusedEval(model, net=True, codes=True), x)}
     result = {"workload": f"harness ResNet-20 fused evaluation forward, B = {args.batch}: B = FusedEval(model), "
-                          "C = FusedEval(model, codes=True); host issue and wall over 50 forwards, device kernel time "
+                          "C = FusedEval(model, codes=True), D = FusedEval(model, net=True), E = net=True and codes=True; "
+                          "host issue and wall over 50 forwards, device kernel time "
                           "from torch.profiler over 5 forwards",
               "device": torch.cuda.get_device_name(0), "abi": [_lib.ABI_VERSION, _lib.ABI_MINOR], "sides": sides}
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
