@@ -197,7 +197,14 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
   const bool actq = NBP == 4 && (xin != nullptr || xq != nullptr);  // uniform
   const float sa_q = actq ? *sa_p : 0.f;
   const bool sgn_q = actq && *sgn_p != 0.f;
-  if (actq) act_lut_build_q<(CST == 2 || CST == 3) ? CST : 0>(g, sa_q, sgn_q, alut);  // syncs the block
+  // (a compile-time slice count also fixes 1-bit activation slices: CST counts slices, whatever their width, so
+  // wider ones take the runtime digit loop; g.bsa is uniform, and either call syncs the block)
+  if (actq) {
+    if ((CST == 2 || CST == 3) && g.bsa == 1)
+      act_lut_build_q<(CST == 2 || CST == 3) ? CST : 0>(g, sa_q, sgn_q, alut);
+    else
+      act_lut_build_q<0>(g, sa_q, sgn_q, alut);
+  }
 
   __syncthreads();
   // w8a8: is binary_mask the standard int8-wrapped one (zero exactly where j + k >= 8)?

@@ -2,7 +2,9 @@
 
 Run in the build container only (the reference is not present on the GPU box):
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py [case ...]
+
+(with case names: only those are written, and the other fixtures stay byte for byte.)
 
 It imports ``models._modules`` from /root/reference (read-only, unmodified).  The
 reference hard-codes CUDA allocations (lsq.py:64,169,336-337) and ``.cuda()``
@@ -71,6 +73,16 @@ FUNCTION_CASES = [
                            adc=1.5, sa=0.0571, sw=0.0377, signed=0)),
     ("fn_alpha_equal_nan", dict(B=1, C=8, O=8, H=4, k=3, s=1, p=1, wb=3, ab=3, wbs=1, abs=1,
                                 xbar=64, adc=1.5, sa=0.25, sw=0.5, signed=0, alpha_equal=True)),
+    # slice widths other than 1: unequal widths on the two sides, bits the width does not divide
+    # (int(5 / 2) = 2 slices cover 4 of the 5 bits), 4-bit slices on the signed first-layer form
+    ("fn_w6a3_bs21", dict(B=2, C=16, O=8, H=6, k=3, s=1, p=1, wb=6, ab=3, wbs=2, abs=1, xbar=64,
+                          adc=1.5, sa=0.0913, sw=0.0213, signed=0)),
+    ("fn_w3a6_bs12", dict(B=2, C=16, O=8, H=6, k=3, s=1, p=1, wb=3, ab=6, wbs=1, abs=2, xbar=64,
+                          adc=1.5, sa=0.0213, sw=0.0913, signed=0)),
+    ("fn_w5a5_bs2", dict(B=2, C=16, O=8, H=6, k=3, s=1, p=1, wb=5, ab=5, wbs=2, abs=2, xbar=64,
+                         adc=1.5, sa=0.0413, sw=0.0513, signed=0)),
+    ("fn_w8a8_bs4", dict(B=2, C=3, O=16, H=8, k=3, s=1, p=1, wb=8, ab=8, wbs=4, abs=4, xbar=128,
+                         adc=1.5, sa=0.0123, sw=0.00731, signed=1)),
 ]
 
 MODULE_CASES = [
@@ -84,6 +96,8 @@ MODULE_CASES = [
                            signed_input=False, bias=False)),
     ("mod_linear_1x1_w4a4", dict(B=8, C=64, O=32, H=1, k=1, s=1, p=0, wb=4, ab=4, xbar=32,
                                  adc=1.5, signed_input=False, bias=False)),
+    ("mod_w4a4_bs2", dict(B=2, C=16, O=16, H=8, k=3, s=1, p=1, wb=4, ab=4, wbs=2, abs=2, xbar=128,
+                          adc=1.5, signed_input=False, bias=False)),
 ]
 
 
@@ -195,8 +209,9 @@ def module_inputs(cfg, seed):
 
 
 def _module_kwargs(cfg):
-    return dict(nbits_w=cfg["wb"], nbits_a=cfg["ab"], nbits_alpha=8, wbitslice=1, abitslice=1,
-                xbar=cfg["xbar"], adcbits=cfg["adc"], signed_xbar=True, stochastic_quant=False)
+    return dict(nbits_w=cfg["wb"], nbits_a=cfg["ab"], nbits_alpha=8, wbitslice=cfg.get("wbs", 1),
+                abitslice=cfg.get("abs", 1), xbar=cfg["xbar"], adcbits=cfg["adc"], signed_xbar=True,
+                stochastic_quant=False)
 
 
 def run_module(mod, inp):
@@ -231,11 +246,18 @@ def run_module(mod, inp):
     return res
 
 
-def main():
+def main(only=()):
+    """``only``: the case names to (re)generate; the other fixtures and their manifest entries stay as they are
+    (an .npz is a zip archive and carries its time of writing, so a rewrite changes the file, not the data)"""
     ref = _import_reference()
     torch.set_num_threads(4)
     manifest = {}
+    if only:
+        with open(os.path.join(HERE, "manifest.json")) as f:
+            manifest = json.load(f)
     for idx, (name, cfg) in enumerate(FUNCTION_CASES):
+        if only and name not in only:
+            continue
         inp = function_inputs(cfg, 1000 + idx)
         res = run_reference_function(ref, cfg, inp)
         check_function_case(name, cfg, inp, res)
@@ -244,6 +266,8 @@ def main():
         np.savez_compressed(os.path.join(HERE, name + ".npz"), **arrays)
         manifest[name] = dict(kind="function", cfg=cfg, seed=1000 + idx)
     for idx, (name, cfg) in enumerate(MODULE_CASES):
+        if only and name not in only:
+            continue
         inp = module_inputs(cfg, 2000 + idx)
         st, pd = cfg["s"], cfg["p"]
         rmod = ref.Conv2dLSQCiM(cfg["C"], cfg["O"], (cfg["k"], cfg["k"]), (st, st), (pd, pd), (1, 1),
@@ -277,4 +301,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(tuple(sys.argv[1:]))

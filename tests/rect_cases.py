@@ -8,7 +8,8 @@ def _pair(v):
 
 
 def case(B, C, O, H, W, k=3, s=1, p=1, bits=3, adc=1.5, xbar=128, signed=0, recompute=False, route=None, **extra):
-    """one layer; k / s / p are ints (both axes) or (h, w) pairs"""
+    """one layer; k / s / p are ints (both axes) or (h, w) pairs.  ``bits`` sets both widths with 1-bit slices;
+    ``wb`` / ``ab`` / ``wbs`` / ``abs`` among ``extra`` override them one by one (slice_cases.py)"""
     kh, kw = _pair(k)
     d = dict(B=B, C=C, O=O, H=H, W=W, kh=kh, kw=kw, s=_pair(s), p=_pair(p), wb=bits, ab=bits, wbs=1, abs=1, adc=adc,
              xbar=xbar, signed=signed, recompute=recompute, route=route)
@@ -105,7 +106,7 @@ def make_desc(L, c, variant=None, options=None):
     """the module entry points' descriptor of a case (RAW_LSQ input)"""
     opt = (L.CIMQ_OPT_RECOMPUTE if c["recompute"] else 0) if options is None else options
     return L.make_desc(B=c["B"], C=c["C"], H=c["H"], W=c["W"], O=c["O"], KH=c["kh"], KW=c["kw"], stride=c["s"],
-                       padding=c["p"], xbar=c["xbar"], bits_w=c["wb"], bits_a=c["ab"], bs_w=1, bs_a=1,
+                       padding=c["p"], xbar=c["xbar"], bits_w=c["wb"], bits_a=c["ab"], bs_w=c["wbs"], bs_a=c["abs"],
                        adc_bits=c["adc"], input_kind=L.CIMQ_INPUT_RAW_LSQ, lsq_qp=float(2 ** c["ab"] - 1),
                        adc_variant=L.CIMQ_ADC_LIBRARY if variant is None else variant, options=opt)
 

@@ -45,9 +45,11 @@ RESNET20_SHAPES = [
 ]
 
 
-def _kw(bits, xbar=128, adc=1.5):
-    return dict(nbits_w=bits, nbits_a=bits, nbits_alpha=8, wbitslice=1, abitslice=1, xbar=xbar, adcbits=adc,
-                signed_xbar=True, stochastic_quant=False)
+def _kw(bits, xbar=128, adc=1.5, ab=None, wbs=1, abs_=1):
+    """``bits``: the weight bits, and the activation bits too unless ``ab`` is given; ``wbs`` / ``abs_``: the slice
+    widths"""
+    return dict(nbits_w=bits, nbits_a=bits if ab is None else ab, nbits_alpha=8, wbitslice=wbs, abitslice=abs_,
+                xbar=xbar, adcbits=adc, signed_xbar=True, stochastic_quant=False)
 
 
 def _close(mine, ref, tol, what):
@@ -113,10 +115,13 @@ def _pin(mods, aa, aw, ac):
         m.train()
 
 
-def _oracle_codes(xq, wq, st, pd, bits, xbar, alpha_q, sw, sa, signed):
-    """ADC code and STE-pass bit of every partial sum (lsq.py:195-230, 257-313), from the oracle."""
-    _, c = co.cim_forward(xq, wq, st, pd, (1, 1), bits, 1, bits, 1, 1.5, xbar, co.make_binary_mask(bits, bits, 1, 1),
-                          alpha_q, sw, sa, False, np.array([signed], np.float32))
+def _oracle_codes(xq, wq, st, pd, bits, xbar, alpha_q, sw, sa, signed, ab=None, wbs=1, abs_=1):
+    """ADC code and STE-pass bit of every partial sum (lsq.py:195-230, 257-313), from the oracle.  ``bits``: the weight
+    bits, and the activation bits too unless ``ab`` is given; ``wbs`` / ``abs_``: the slice widths."""
+    ab = bits if ab is None else ab
+    _, c = co.cim_forward(xq, wq, st, pd, (1, 1), ab, abs_, bits, wbs, 1.5, xbar,
+                          co.make_binary_mask(bits // wbs, ab // abs_, wbs, abs_), alpha_q, sw, sa, False,
+                          np.array([signed], np.float32))
     u = ((c.ps16.astype(np.float32) * sw).astype(np.float32) * sa).astype(np.float32)
     with np.errstate(all="ignore"):
         v = (u / alpha_q).astype(np.float32)

@@ -189,8 +189,8 @@ def test_function_vs_oracle_random(cuda_device, idx):
 # module level: Conv2dLSQCiM (fused LSQ + CiM, first-step init) against the golden runs
 # ------------------------------------------------------------------------------------------
 def _module_kwargs(cfg):
-    return dict(nbits_w=cfg["wb"], nbits_a=cfg["ab"], nbits_alpha=8, wbitslice=1, abitslice=1,
-                xbar=cfg["xbar"], adcbits=cfg["adc"], signed_xbar=True, stochastic_quant=False)
+    return dict(nbits_w=cfg["wb"], nbits_a=cfg["ab"], nbits_alpha=8, wbitslice=cfg.get("wbs", 1),
+                abitslice=cfg.get("abs", 1), xbar=cfg["xbar"], adcbits=cfg["adc"], signed_xbar=True, stochastic_quant=False)
 
 
 def _lsq_scalar_terms(x, g_xq, s, qn, qp, gscale):

@@ -65,11 +65,13 @@ def test_function_vs_oracle_rect(cuda_device, idx):
 # ------------------------------------------------------------------------------------------
 # the module path, steady state
 # ------------------------------------------------------------------------------------------
-def _module_data(c, seed):
+def _module_data(c, seed, step="mean"):
     """weights, input, output gradient and the pinned state of a case: the step sizes of lsq.py:539-542 on the
-    data, a data-driven alpha_cim (lsq.py:557-563) spread so that the codes vary"""
+    data (``step`` "quantile": the 97 % points of x and |w| over Qp instead, so that a few per cent of the values
+    clamp and the top slices of wide codes are filled), a data-driven alpha_cim (lsq.py:557-563) at the case's bit
+    and slice widths, spread so that the codes vary"""
     rng = np.random.default_rng(seed)
-    B, C, O, H, W, bits = c["B"], c["C"], c["O"], c["H"], c["W"], c["wb"]
+    B, C, O, H, W = c["B"], c["C"], c["O"], c["H"], c["W"]
     k = (c["kh"], c["kw"])
     w = (rng.standard_normal((O, C) + k) * math.sqrt(2.0 / (k[0] * k[1] * C))).astype(np.float32)
     x = rng.standard_normal((B, C, H, W)).astype(np.float32)
@@ -77,16 +79,21 @@ def _module_data(c, seed):
         x = np.maximum(x, 0)
     ho, wo = out_hw(c)
     g = (rng.standard_normal((B, O, ho, wo)) / math.sqrt(B * O * ho * wo)).astype(np.float32)
-    qp_a, (qn_w, qp_w) = 2 ** bits - 1, co.lsq_weight_params(bits)
-    aa = np.float32(2 * np.abs(x).mean() / math.sqrt(qp_a))
-    aw = np.float32(2 * np.abs(w).mean() / math.sqrt(qp_w))
+    qp_a, (qn_w, qp_w) = 2 ** c["ab"] - 1, co.lsq_weight_params(c["wb"])
+    if step == "quantile":
+        aa = np.float32(np.quantile(x, 0.97) / qp_a)
+        aw = np.float32(np.quantile(np.abs(w), 0.97) / qp_w)
+    else:
+        aa = np.float32(2 * np.abs(x).mean() / math.sqrt(qp_a))
+        aw = np.float32(2 * np.abs(w).mean() / math.sqrt(qp_w))
     ac = None
     if c["adc"] in (1, 1.5):
         sa0 = co.grad_scale_value(np.array([aa], np.float32), 1.0 / math.sqrt(x.size * qp_a))
         sw0 = co.grad_scale_value(np.array([aw], np.float32), 1.0 / math.sqrt(w.size * qp_w))
         xq0, _ = co.lsq_quantize(x, sa0, 0, qp_a)
         wq0, _ = co.lsq_quantize(w, sw0, qn_w, qp_w)
-        ac = co.alpha_cim_init(xq0, wq0, c["s"], c["p"], bits, 1, bits, 1, c["xbar"], sw0, sa0, c["adc"])
+        ac = co.alpha_cim_init(xq0, wq0, c["s"], c["p"], c["ab"], c["abs"], c["wb"], c["wbs"], c["xbar"], sw0, sa0,
+                               c["adc"])
         ac = (ac * (0.7 + 0.6 * rng.random(ac.shape))).astype(np.float32)
     return dict(x=x, w=w, g=g, aa=aa, aw=aw, ac=ac, qp_a=qp_a, qn_w=qn_w, qp_w=qp_w)
 
@@ -94,7 +101,7 @@ def _module_data(c, seed):
 def _modules(c, d, dev, oracle=True):
     import cim_quantization_amd._modules as my_nn
     k = (c["kh"], c["kw"])
-    kw = _kw(c["wb"], c["xbar"], c["adc"])
+    kw = _kw(c["wb"], c["xbar"], c["adc"], c["ab"], c["wbs"], c["abs"])
     m = my_nn.Conv2dLSQCiM(c["C"], c["O"], k, c["s"], c["p"], bias=False, **kw).to(dev)
     m.recompute_psum = c["recompute"]
     mods = [m]

@@ -35,8 +35,8 @@ from oracle import cim_oracle as co
 pytestmark = pytest.mark.gpu
 
 
-def _kw(bits, xbar=64, shift=True):
-    return dict(nbits_w=bits, nbits_a=bits, nbits_alpha=8, wbitslice=1, abitslice=1, xbar=xbar, adcbits=1.5,
+def _kw(bits, xbar=64, shift=True, bs=1):
+    return dict(nbits_w=bits, nbits_a=bits, nbits_alpha=8, wbitslice=bs, abitslice=bs, xbar=xbar, adcbits=1.5,
                 stochastic_quant=False, adc_shift=shift)
 
 
@@ -61,15 +61,16 @@ def _scalar_terms(x, g_xq, s, qn, qp, gscale):
     return gscale * (np.abs(g * r).sum() + np.abs(np.where(inside, g * float(s), 0) * y / float(s)).sum())
 
 
-def _build(dev, C, O, H, s, bits, B, seed, signed, shift=True, W=None, xbar=64):
+def _build(dev, C, O, H, s, bits, B, seed, signed, shift=True, W=None, xbar=64, bs=1):
     """The MI355X module and the oracle module with identical weights and step sizes; alpha_cim from
     the reference's data-driven init (lsq.py:557-563) on a few images, spread so codes vary; beta a
-    fraction of alpha of either sign.  ``W``: the image width where it is not H; ``xbar``: the tile rows."""
+    fraction of alpha of either sign.  ``W``: the image width where it is not H; ``xbar``: the tile rows; ``bs``: the
+    slice width of weights and activations."""
     import cim_quantization_amd._modules as my_nn
     rng = np.random.default_rng(seed)
     W = H if W is None else W
-    m = my_nn.Conv2dLSQCiM(C, O, (3, 3), (s, s), (1, 1), (1, 1), bias=False, **_kw(bits, xbar, shift)).to(dev)
-    om = cmo.OracleConv2dLSQCiM(C, O, (3, 3), (s, s), (1, 1), (1, 1), bias=False, **_kw(bits, xbar, shift))
+    m = my_nn.Conv2dLSQCiM(C, O, (3, 3), (s, s), (1, 1), (1, 1), bias=False, **_kw(bits, xbar, shift, bs)).to(dev)
+    om = cmo.OracleConv2dLSQCiM(C, O, (3, 3), (s, s), (1, 1), (1, 1), bias=False, **_kw(bits, xbar, shift, bs))
     om.debug_retain = True
     w = (rng.standard_normal((O, C, 3, 3)) * math.sqrt(2.0 / (9 * C))).astype(np.float32)
     x = rng.standard_normal((B, C, H, W)).astype(np.float32)
@@ -82,7 +83,7 @@ def _build(dev, C, O, H, s, bits, B, seed, signed, shift=True, W=None, xbar=64):
     sw0 = co.grad_scale_value(np.array([aw], np.float32), 1.0 / math.sqrt(w.size * qp_w))
     xq0, _ = co.lsq_quantize(x[:2], sa0, 0, qp_a)
     wq0, _ = co.lsq_quantize(w, sw0, qn_w, qp_w)
-    ac = co.alpha_cim_init(xq0, wq0, (s, s), (1, 1), bits, 1, bits, 1, xbar, sw0, sa0, 1.5)
+    ac = co.alpha_cim_init(xq0, wq0, (s, s), (1, 1), bits, bs, bits, bs, xbar, sw0, sa0, 1.5)
     ac = (ac * (0.6 + 0.8 * rng.random(ac.shape))).astype(np.float32)
     bc = (ac * (rng.random(ac.shape) - 0.5)).astype(np.float32)
     for mod in (m, om):
@@ -115,8 +116,8 @@ def _run(m, x, g, dev):
                 gaa=m.alpha_act.grad.clone(), gaw=m.alpha_weight.grad.clone())
 
 
-def _check(dev, monkeypatch, C, O, H, s, bits, B, seed, signed, repeat=True, shift=True, W=None, xbar=64):
-    m, om, x, w, g, qp_a, qn_w, qp_w = _build(dev, C, O, H, s, bits, B, seed, signed, shift, W, xbar)
+def _check(dev, monkeypatch, C, O, H, s, bits, B, seed, signed, repeat=True, shift=True, W=None, xbar=64, bs=1):
+    m, om, x, w, g, qp_a, qn_w, qp_w = _build(dev, C, O, H, s, bits, B, seed, signed, shift, W, xbar, bs)
     r1 = _run(m, x, g, dev)
     if repeat:
         r2 = _run(m, x, g, dev)

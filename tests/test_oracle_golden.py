@@ -41,8 +41,8 @@ def test_oracle_function_matches_reference(name):
 
 
 def _module_kwargs(cfg):
-    return dict(nbits_w=cfg["wb"], nbits_a=cfg["ab"], nbits_alpha=8, wbitslice=1, abitslice=1,
-                xbar=cfg["xbar"], adcbits=cfg["adc"], signed_xbar=True, stochastic_quant=False)
+    return dict(nbits_w=cfg["wb"], nbits_a=cfg["ab"], nbits_alpha=8, wbitslice=cfg.get("wbs", 1),
+                abitslice=cfg.get("abs", 1), xbar=cfg["xbar"], adcbits=cfg["adc"], signed_xbar=True, stochastic_quant=False)
 
 
 @pytest.mark.parametrize("name", module_cases())
