@@ -57,6 +57,8 @@ EXPORTED_SYMBOLS = (
     "cimq_pending_flush",
     "cimq_pending_jobs",
     "cimq_module_prepare",
+    "cimq_shift_prepare_abi",
+    "cimq_module_prepare_shift",
     "cimq_module_shift_supported",
     "cimq_module_route",
     "cimq_module_shift_forward",
@@ -205,6 +207,12 @@ class PrepareItem(ctypes.Structure):
                 ("alpha_cim", ctypes.c_void_p), ("binary_mask", ctypes.c_void_p), ("wprep", ctypes.c_void_p)]
 
 
+class PrepareShiftItem(ctypes.Structure):
+    """Mirror of ``cimq_prepare_shift_item`` (cimq_shift_prepare_abi() == 1)."""
+
+    _fields_ = PrepareItem._fields_ + [("beta_cim", ctypes.c_void_p), ("reserved", ctypes.c_int32 * 2)]
+
+
 _VP = ctypes.c_void_p
 _lock = threading.Lock()
 _lib = None
@@ -244,6 +252,10 @@ def _bind(lib):
     lib.cimq_pending_jobs.argtypes = [ctypes.POINTER(Pending)]
     lib.cimq_module_prepare.restype = ctypes.c_int
     lib.cimq_module_prepare.argtypes = [ctypes.c_int, ctypes.POINTER(PrepareItem), _VP]
+    lib.cimq_shift_prepare_abi.restype = ctypes.c_int
+    lib.cimq_shift_prepare_abi.argtypes = []
+    lib.cimq_module_prepare_shift.restype = ctypes.c_int
+    lib.cimq_module_prepare_shift.argtypes = [ctypes.c_int, ctypes.POINTER(PrepareShiftItem), _VP]
     lib.cimq_module_shift_supported.restype = ctypes.c_int
     lib.cimq_module_shift_supported.argtypes = [ctypes.POINTER(ConvDesc)]
     lib.cimq_module_route.restype = ctypes.c_int

@@ -52,7 +52,8 @@ class Conv2dLSQCiM(_Conv2dQCiM):
 
     Evaluation: a forward under ``torch.no_grad()`` (or one no input of which requires a gradient) runs
     the library's forward-only mode -- the same output bit for bit, no backward state, nothing saved.
-    On the fused library-ADC path the layer then keeps the weight side it prepared (``_inf_prep``) and
+    On the fused library-ADC path, and on the fused shift path (beta_cim then counts among the parameters), the
+    layer then keeps the weight side it prepared (``_inf_prep``) and
     reuses it while the input shape and the parameters' versions and addresses are unchanged, so a whole
     evaluation quantises the weights once per input shape.  ``train(True)`` and ``load_state_dict`` drop
     it, a call made with grad enabled never reads it, and stochastic-ADC layers keep none.  An edit
@@ -138,10 +139,15 @@ class Conv2dLSQCiM(_Conv2dQCiM):
             self.binary_mask = self.binary_mask.to(x.device)
         if (self.fused and self.adc_shift and flags[0] and flags[1] and self._shift_fused(x)):
             # steady state of the shift ADC on libcimq's fused path (quantisers in the library)
+            wprep = None
+            if (not torch.is_grad_enabled() and x.is_cuda and
+                    inference_call(x, self.weight, self.alpha_act, self.alpha_weight, self.alpha_cim, self.beta_cim)):
+                # evaluation: the forward-only weight side (beta_cim in it), made once and kept while it matches
+                wprep = self._inf_prep = inference_weights(self, x.shape, self._inf_prep)
             out = cim_module_shift_conv(x, self.weight, self.alpha_act, self.alpha_weight, self.alpha_cim,
                                         self.beta_cim, self.binary_mask, self.signed_act, self.stride, self.padding,
                                         self.dilation, self.nbits_a, self.abitslice, self.nbits_w, self.wbitslice,
-                                        self.xbar, self.nbits_alpha)
+                                        self.xbar, self.nbits_alpha, wprep=wprep)
             return out if self.bias is None else out + self.bias  # lsq.py:583's broadcast
         if (self.fused and flags[0] and (flags[1] or self.alpha_cim is None) and self.adcbits != 0
                 and not self.adc_shift):
@@ -269,8 +275,8 @@ class Conv2dLSQCiM(_Conv2dQCiM):
         wprep = None
         if not self.adc_shift:
             self._last_x_shape = tuple(x.shape)
-            if not torch.is_grad_enabled() and not self.stochastic_quant:
-                wprep = self._inf_prep = inference_weights(self, x.shape, self._inf_prep)
+        if not torch.is_grad_enabled() and not self.stochastic_quant:
+            wprep = self._inf_prep = inference_weights(self, x.shape, self._inf_prep)
         if x.dtype != torch.uint8 and out_quant is None:
             if not keep_float:
                 raise ValueError("Conv2dLSQCiM.forward_fused: keep_float=False needs out_quant")

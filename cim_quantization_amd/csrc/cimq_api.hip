@@ -536,7 +536,8 @@ static ModulePrep module_prep_args(const Geo& g, const float* x, const float* we
 
 // the checks every module entry point shares, and the module form of the geometry (the output layout flag is
 // fixed here: every entry point plans with the same Geo from its first line); applies q->wprep.  shift: the
-// cimq_module_shift_* entry points (the shift ADC on the fast path, no prepared weight side)
+// cimq_module_shift_* entry points (the shift ADC on the fast path; a prepared weight side -- cimq_module_prepare_shift
+// -- in a forward-only call alone: the shift backward reads nothing prepared)
 static int module_geo(const cimq_conv_desc* d, const cimq_lsq_desc* q, Geo* g, LsqArgs* la, bool shift = false) {
   CIMQ_TRY(make_geo(d, g));
   if (g->input_kind != CIMQ_INPUT_RAW_LSQ) return fail(CIMQ_EINVAL, "module entry points take the raw activation");
@@ -545,7 +546,8 @@ static int module_geo(const cimq_conv_desc* d, const cimq_lsq_desc* q, Geo* g, L
     if (g->variant != VAR_SHIFT_ROUND || !route_of(*g).shift_stats)
       return fail(CIMQ_EUNSUPPORTED, "cimq_module_shift_*: the shift ADC on a fast-path layer only "
                                      "(adc_variant CIMQ_ADC_SHIFT_ROUND, adc 1.5, 2 or 3 equal slices, v7 shapes)");
-    if (q && q->wprep) return fail(CIMQ_EINVAL, "cimq_module_shift_*: no prepared weight side");
+    if (q && q->wprep && !g->inference)
+      return fail(CIMQ_EINVAL, "cimq_module_shift_*: no prepared weight side without CIMQ_OPT_INFERENCE");
   } else if (g->variant == VAR_SHIFT_ROUND || g->variant == VAR_SHIFT_SIGN) {
     return fail(CIMQ_EUNSUPPORTED, "the module entry points run the library / stochastic ADC only");
   }
@@ -1028,6 +1030,58 @@ int cimq_net_forward(const cimq_net_desc* net, const float* x, void* const* slot
   return net_walk(net, true, true, x, slot_float, slot_codes, logits, ws, stream, nullptr, nullptr, nullptr);
 }
 
+// one layer of cimq_module_prepare (beta null) or cimq_module_prepare_shift
+struct PrepView {
+  const cimq_conv_desc* desc;
+  const cimq_lsq_desc* lsq;
+  const float *weight, *alpha_act, *alpha_weight, *alpha_cim, *beta;
+  const int8_t* binary_mask;
+  void* wprep;
+};
+
+// the weight side of the layers in v, up to kPrepJobs of them per prep_weights_many_kernel launch
+static int prepare_run(const std::vector<PrepView>& v, bool shift, hipStream_t s) {
+  const int n = (int)v.size();
+  PrepPack pk;
+  memset(&pk, 0, sizeof(pk));
+  int grid = 0;
+  for (int i = 0; i < n; ++i) {
+    const PrepView& it = v[i];
+    Geo g;
+    LsqArgs la;
+    if (!it.lsq) return fail(CIMQ_EINVAL, "item %d: null LSQ descriptor", i);
+    cimq_lsq_desc q = *it.lsq;
+    q.flags = 0;
+    q.wprep = it.wprep;
+    CIMQ_TRY(module_geo(it.desc, &q, &g, &la, shift));
+    if (!it.weight || !it.alpha_act || !it.alpha_weight || !it.binary_mask || !it.wprep)
+      return fail(CIMQ_EINVAL, "item %d: null pointer argument", i);
+    CIMQ_TRY(check_alpha(g, &la, it.alpha_cim, nullptr, false));
+    PrepJob& j = pk.job[pk.n];
+    j.g = g;
+    j.q = la;
+    j.a = module_prep_args(g, nullptr, it.weight, it.alpha_act, it.alpha_weight, la.nbits_alpha ? it.alpha_cim : nullptr,
+                           it.binary_mask, nullptr, nullptr, &j.nwblk);
+    if (it.beta) {  // the shift ADC: beta into the thresholds, and the per-channel beta sums (as module_forward_impl)
+      j.a.beta = it.beta;
+      j.a.npp += g.Opad;
+      j.nwblk = std::max(1, std::min(cdiv(j.a.nwf + j.a.nwg + j.a.nwc + j.a.nw5 + j.a.nwx5 + j.a.nwx6 + j.a.npp, 256), 1024));
+    }
+    j.a.nact_blocks = 0;
+    pk.blk0[pk.n] = grid;
+    grid += j.nwblk;
+    ++pk.n;
+    if (pk.n == kPrepJobs || i == n - 1) {
+      pk.blk0[pk.n] = grid;
+      hipLaunchKernelGGL(prep_weights_many_kernel, dim3(grid), dim3(256), 0, s, pk);
+      CIMQ_TRY(check_hip("prep_weights_many"));
+      memset(&pk, 0, sizeof(pk));
+      grid = 0;
+    }
+  }
+  return CIMQ_OK;
+}
+
 static int module_backward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* grad_out,
                                 const float* x, const float* weight, const float* alpha_act,
                                 const float* alpha_weight, const float* alpha_cim, const int8_t* binary_mask,
@@ -1199,40 +1253,35 @@ int cimq_module_shift_backward(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
 
 int cimq_module_prepare(int n, const cimq_prepare_item* items, void* stream) {
   if (n < 0 || (n > 0 && !items)) return fail(CIMQ_EINVAL, "bad prepare item list");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  PrepPack pk;
-  memset(&pk, 0, sizeof(pk));
-  int grid = 0;
+  std::vector<PrepView> v((size_t)n);
   for (int i = 0; i < n; ++i) {
     const cimq_prepare_item& it = items[i];
-    Geo g;
-    LsqArgs la;
-    if (!it.lsq) return fail(CIMQ_EINVAL, "item %d: null LSQ descriptor", i);
-    cimq_lsq_desc q = *it.lsq;
-    q.flags = 0;
-    q.wprep = it.wprep;
-    CIMQ_TRY(module_geo(it.desc, &q, &g, &la));
-    if (!it.weight || !it.alpha_act || !it.alpha_weight || !it.binary_mask || !it.wprep)
-      return fail(CIMQ_EINVAL, "item %d: null pointer argument", i);
-    CIMQ_TRY(check_alpha(g, &la, it.alpha_cim, nullptr, false));
-    PrepJob& j = pk.job[pk.n];
-    j.g = g;
-    j.q = la;
-    j.a = module_prep_args(g, nullptr, it.weight, it.alpha_act, it.alpha_weight, la.nbits_alpha ? it.alpha_cim : nullptr,
-                           it.binary_mask, nullptr, nullptr, &j.nwblk);
-    j.a.nact_blocks = 0;
-    pk.blk0[pk.n] = grid;
-    grid += j.nwblk;
-    ++pk.n;
-    if (pk.n == kPrepJobs || i == n - 1) {
-      pk.blk0[pk.n] = grid;
-      hipLaunchKernelGGL(prep_weights_many_kernel, dim3(grid), dim3(256), 0, s, pk);
-      CIMQ_TRY(check_hip("prep_weights_many"));
-      memset(&pk, 0, sizeof(pk));
-      grid = 0;
-    }
+    v[i] = PrepView{it.desc, it.lsq, it.weight, it.alpha_act, it.alpha_weight, it.alpha_cim, nullptr, it.binary_mask, it.wprep};
   }
-  return CIMQ_OK;
+  return prepare_run(v, false, reinterpret_cast<hipStream_t>(stream));
+}
+
+int cimq_shift_prepare_abi(void) { return 1; }
+
+int cimq_module_prepare_shift(int n, const cimq_prepare_shift_item* items, void* stream) {
+  static const char who[] = "cimq_module_prepare_shift";
+  if (n < 0 || (n > 0 && !items)) return fail(CIMQ_EINVAL, "bad prepare item list");
+  std::vector<PrepView> v((size_t)n);
+  // (every refusal of the call's own before the first launch)
+  for (int i = 0; i < n; ++i) {
+    const cimq_prepare_shift_item& it = items[i];
+    if (!it.beta_cim || !it.alpha_cim) return fail(CIMQ_EINVAL, "%s: item %d: needs alpha_cim and beta_cim", who, i);
+    if (it.reserved[0] != 0 || it.reserved[1] != 0) return fail(CIMQ_EINVAL, "%s: item %d: reserved must be 0", who, i);
+    if (!it.desc) return fail(CIMQ_EINVAL, "%s: item %d: null descriptor", who, i);
+    if (!(it.desc->options & CIMQ_OPT_INFERENCE))
+      return fail(CIMQ_EINVAL, "%s: item %d: a CIMQ_OPT_INFERENCE descriptor only (the shift backward reads nothing "
+                               "prepared)", who, i);
+    if (!cimq_module_shift_supported(it.desc))
+      return fail(CIMQ_EUNSUPPORTED, "%s: item %d: not a layer of the fused shift path (cimq_module_shift_supported)", who, i);
+    v[i] = PrepView{it.desc, it.lsq, it.weight, it.alpha_act, it.alpha_weight, it.alpha_cim, it.beta_cim, it.binary_mask,
+                    it.wprep};
+  }
+  return prepare_run(v, true, reinterpret_cast<hipStream_t>(stream));
 }
 
 int cimq_alpha_init(const cimq_conv_desc* d, const float* x, const float* w_q, const float* sa,

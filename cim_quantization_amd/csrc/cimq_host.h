@@ -618,10 +618,12 @@ inline bool v7_bwd(const Geo& g) {
 
 // the LSQ activation quantiser can run in the forward's row staging: the v3 fast path with v7 state words (so
 // no later kernel reads the forward slice words), 4-byte slice words, the prologue's word table applicable, and
-// not the first conv (whose backward re-reads the forward words) or a shift layer (its statistics kernel does)
+// not the first conv (whose backward re-reads the forward words) or a shift layer in training (its statistics
+// kernel does; a forward-only shift layer of the fused shift path has no such reader)
 inline bool fwd_actq_ok(const Geo& g) {
   if (tune("ACTQ", 1) == 0) return false;
-  return g.input_kind == CIMQ_INPUT_RAW_LSQ && g.NBP == 4 && g.variant == VAR_LIBRARY && g.W % 4 == 0 &&
+  const bool adc_ok = g.variant == VAR_LIBRARY || (g.inference && g.variant == VAR_SHIFT_ROUND && shift_stats_ok(g));
+  return g.input_kind == CIMQ_INPUT_RAW_LSQ && g.NBP == 4 && adc_ok && g.W % 4 == 0 &&
          g.P % 64 == 0 && g.lsq_qp >= 0.f && g.lsq_qp < 255.f && v3_plan(g).ok && v7_bwd(g) && !c1_plan(g).ok;
 }
 
@@ -997,8 +999,9 @@ inline CtxLayout ctx_layout_compute(const Geo& g) {
   L.flags = o; o = align256(o + 16);
   L.lsq_scal = o; o = align256(o + 16 * 4);
   L.wbytes = o;
-  // forward slice bytes (none in a forward-only call whose forward quantises the activation itself)
-  L.xcode = o; o = align256(o + ((g.inference && r.actq) ? (size_t)0 : (size_t)g.Nin * g.NBP));
+  // forward slice bytes (none in a forward-only call whose forward quantises the activation itself; a shift layer
+  // keeps the region, unwritten there: its ctx_bytes are what they were before its forward staged the quantiser)
+  L.xcode = o; o = align256(o + ((g.inference && r.actq && g.variant == VAR_LIBRARY) ? (size_t)0 : (size_t)g.Nin * g.NBP));
   if (g.inference) {
     // forward only (CIMQ_OPT_INFERENCE): the ctx ends here -- no backward slice words, no code table, no state;
     // their offsets point at the end and nothing is written through them

@@ -187,7 +187,7 @@ __global__ __launch_bounds__(256) void prep_module_fwd_kernel(Geo g, LsqArgs q, 
 }
 
 // prep_module_fwd_kernel for an input that arrives as activation codes (cimq_module_forward_codes on the routes whose
-// forward reads slice words: general, dense, shift, and v3 without the fused quantiser): the activation blocks turn
+// forward reads slice words: general, dense, the NBP-8 shift layer, and v3 without the fused quantiser): the activation blocks turn
 // the bytes of xq into the forward slice words (act_range_codes); the weight side is prep_module_fwd_kernel's
 __global__ __launch_bounds__(256) void prep_module_fwd_codes_kernel(Geo g, LsqArgs q, ModulePrep a,
                                                                     const uint8_t* __restrict__ xq) {

@@ -490,7 +490,15 @@ def _module_descs(x_shape, weight, stride, padding, dilation, nbits_a, abitslice
 
 
 def _prepare_descs(m, shape, inference=False):
-    """The descriptor pair a prepared weight side of layer ``m`` is made for (input shape ``shape``)."""
+    """The descriptor pair a prepared weight side of layer ``m`` is made for (input shape ``shape``).  A shift-ADC
+    layer (``m.adc_shift``): the fused shift path's pair; the library prepares it forward only."""
+    if getattr(m, "adc_shift", False):
+        if not inference:
+            raise ValueError("a shift-ADC layer's weight side is prepared for forward-only calls alone")
+        desc, lsq = _shift_module_descs(shape, m.weight, m.stride, m.padding, m.dilation, m.nbits_a, m.abitslice,
+                                        m.nbits_w, m.wbitslice, m.xbar, m.nbits_alpha)
+        desc.options |= _lib.CIMQ_OPT_INFERENCE
+        return desc, lsq
     return _module_descs(shape, m.weight, m.stride, m.padding, m.dilation, m.nbits_a, m.abitslice,
                          m.nbits_w, m.wbitslice, m.adcbits, m.xbar, m.nbits_alpha, m.alpha_cim is not None, False,
                          bool(getattr(m, "recompute_psum", False)), inference)
@@ -500,16 +508,19 @@ def _prepare_item(m, shape, inference=False):
     """One layer's cimq_module_prepare item for input shape ``shape``, what it must keep alive until the
     call, and the WeightPrep the call fills.  ``inference``: for the forward-only descriptor."""
     has_alpha = m.alpha_cim is not None
+    shift = bool(getattr(m, "adc_shift", False))
     desc, lsq = _prepare_descs(m, shape, inference)
     sizes = _lib.query_sizes(desc)
     dev = m.weight.device
     buf = torch.empty(max(sizes.wprep_bytes, 1), device=dev, dtype=torch.uint8)
     bm = m.binary_mask.to(device=dev, dtype=torch.int8).contiguous()
     ps = (m.weight, m.alpha_act, m.alpha_weight, m.alpha_cim)
-    for t in ps:
+    for t in ps + ((m.beta_cim,) if shift else ()):
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
             raise ValueError("prepare_weights: parameters must be contiguous fp32")
-    it = _lib.PrepareItem()
+    it = _lib.PrepareShiftItem() if shift else _lib.PrepareItem()
+    if shift:  # cimq_module_prepare_shift's item: beta_cim as well
+        it.beta_cim = m.beta_cim.data_ptr()
     it.desc = ctypes.pointer(desc)
     it.lsq = ctypes.pointer(lsq)
     it.weight = m.weight.data_ptr()
@@ -518,23 +529,32 @@ def _prepare_item(m, shape, inference=False):
     it.alpha_cim = m.alpha_cim.data_ptr() if has_alpha else None
     it.binary_mask = bm.data_ptr()
     it.wprep = buf.data_ptr()
-    return it, (desc, lsq, bm), WeightPrep(buf, _prep_key(desc, lsq, shape), _versions(*ps, m.binary_mask))
+    return it, (desc, lsq, bm), WeightPrep(buf, _prep_key(desc, lsq, shape),
+                                           _versions(*ps, m.binary_mask, m.beta_cim if shift else None))
 
 
 def inference_weights(m, x_shape, cached=None):
     """The weight side of a forward-only call of the fused Conv2dLSQCiM ``m`` on input shape ``x_shape``:
     ``cached`` if that WeightPrep was made for this shape and the parameters as they are now (_prep_key,
     _versions -- an edit through ``p.data`` bumps no version: drop the cache after one), else a new one from
-    cimq_module_prepare with the forward roles only.  Conv2dLSQCiM keeps it across the batches of an evaluation."""
+    cimq_module_prepare with the forward roles only.  Conv2dLSQCiM keeps it across the batches of an evaluation.
+    A shift-ADC layer (``m.adc_shift``, one the fused shift path takes): the same through
+    cimq_module_prepare_shift, with beta_cim among the versions."""
+    shift = bool(getattr(m, "adc_shift", False))
     if cached is not None:
         desc, lsq = _prepare_descs(m, tuple(x_shape), inference=True)
         if (cached.key == _prep_key(desc, lsq, tuple(x_shape)) and cached.versions ==
-                _versions(m.weight, m.alpha_act, m.alpha_weight, m.alpha_cim, m.binary_mask)):
+                _versions(m.weight, m.alpha_act, m.alpha_weight, m.alpha_cim, m.binary_mask,
+                          m.beta_cim if shift else None)):
             return cached
     it, keep, wp = _prepare_item(m, tuple(x_shape), inference=True)
-    arr = (_lib.PrepareItem * 1)(it)
-    _lib.check(_lib.load().cimq_module_prepare(1, arr, torch.cuda.current_stream(m.weight.device).cuda_stream),
-               "cimq_module_prepare")
+    stream = torch.cuda.current_stream(m.weight.device).cuda_stream
+    if shift:
+        arr = (_lib.PrepareShiftItem * 1)(it)
+        _lib.check(_lib.load().cimq_module_prepare_shift(1, arr, stream), "cimq_module_prepare_shift")
+    else:
+        arr = (_lib.PrepareItem * 1)(it)
+        _lib.check(_lib.load().cimq_module_prepare(1, arr, stream), "cimq_module_prepare")
     del keep
     return wp
 
@@ -596,7 +616,7 @@ class _CimModuleConv(torch.autograd.Function):
         # a prepared weight side (prepare_weights / inference_weights) if it was made for exactly this call
         wprep_buf = None
         if (wprep is not None and not stochastic and wprep.key == _prep_key(desc, lsq, x.shape)
-                and wprep.versions == _versions(weight, alpha_act, alpha_weight, alpha_cim, binary_mask)):
+                and wprep.versions == _versions(weight, alpha_act, alpha_weight, alpha_cim, binary_mask, None)):
             lsq.wprep = wprep.buf.data_ptr()
             wprep_buf = wprep.buf
         sizes = _lib.query_sizes(desc)
@@ -771,15 +791,22 @@ class _CimModuleShiftConv(torch.autograd.Function):
 
     @staticmethod
     def _call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act, stride,
-              padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, xbar, nbits_alpha, inference=False):
-        """cimq_module_shift_forward; returns (out, desc, lsq, sizes, bufs)."""
+              padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, xbar, nbits_alpha, inference=False,
+              wprep=None):
+        """cimq_module_shift_forward; returns (out, desc, lsq, sizes, bufs).  ``wprep`` (a forward-only call alone):
+        a WeightPrep from inference_weights, used if it was made for exactly this call."""
         _require_device(x)
         dev = x.device
         B, C, H, W, O, KH, KW, st, pd = _geometry(x, weight, stride, padding, dilation)
         desc, lsq = _shift_module_descs(tuple(x.shape), weight, st, pd, dilation, nbits_a, abitslice, nbits_w,
                                         wbitslice, xbar, nbits_alpha)
+        keep = None
         if inference:
             desc.options |= _lib.CIMQ_OPT_INFERENCE
+            if (wprep is not None and wprep.key == _prep_key(desc, lsq, x.shape) and wprep.versions ==
+                    _versions(weight, alpha_act, alpha_weight, alpha_cim, binary_mask, beta_cim)):
+                lsq.wprep = wprep.buf.data_ptr()
+                keep = wprep.buf
         sizes = _lib.query_sizes(desc)
         xc = x.detach().to(torch.float32).contiguous()
         wc = weight.detach().to(torch.float32).contiguous()
@@ -798,6 +825,7 @@ class _CimModuleShiftConv(torch.autograd.Function):
                                                          aw.data_ptr(), ac.data_ptr(), bc.data_ptr(), bm.data_ptr(),
                                                          sg.data_ptr(), out.data_ptr(), cbuf.data_ptr(),
                                                          ws.data_ptr(), _stream()), "cimq_module_shift_forward")
+        del keep
         return out, desc, lsq, sizes, (xc, wc, aa, aw, ac, bc, bm, sg, cbuf)
 
     @staticmethod
@@ -832,13 +860,14 @@ class _CimModuleShiftConv(torch.autograd.Function):
 
 
 def cim_module_shift_conv(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act, stride,
-                          padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, xbar, nbits_alpha):
+                          padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, xbar, nbits_alpha, wprep=None):
     """NCHW output of a Conv2dLSQCiM(adc_shift=True, adcbits=1.5) layer with its quantisers fused
-    (module_shift_supported must hold).  Forward only for a call nothing can differentiate (inference_call)."""
+    (module_shift_supported must hold).  Forward only for a call nothing can differentiate (inference_call);
+    ``wprep`` then comes from inference_weights (a call that can be differentiated never reads it)."""
     if inference_call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim):
         return _CimModuleShiftConv._call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask,
                                          signed_act, stride, padding, dilation, nbits_a, abitslice, nbits_w,
-                                         wbitslice, xbar, nbits_alpha, inference=True)[0]
+                                         wbitslice, xbar, nbits_alpha, inference=True, wprep=wprep)[0]
     return _CimModuleShiftConv.apply(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask,
                                      signed_act, stride, padding, dilation, nbits_a, abitslice, nbits_w, wbitslice,
                                      xbar, nbits_alpha)
@@ -918,8 +947,8 @@ def _conv_epilogue(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, s
                                         wbitslice, xbar, nbits_alpha)
         desc.options |= _lib.CIMQ_OPT_INFERENCE
     keep = None
-    if (beta_cim is None and wprep is not None and not stochastic and wprep.key == _prep_key(desc, lsq, x.shape)
-            and wprep.versions == _versions(weight, alpha_act, alpha_weight, alpha_cim, binary_mask)):
+    if (wprep is not None and not stochastic and wprep.key == _prep_key(desc, lsq, x.shape)
+            and wprep.versions == _versions(weight, alpha_act, alpha_weight, alpha_cim, binary_mask, beta_cim)):
         lsq.wprep = wprep.buf.data_ptr()
         keep = wprep.buf
     sizes = _lib.query_sizes(desc)

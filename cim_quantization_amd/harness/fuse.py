@@ -113,9 +113,11 @@ class _NetPlan:
             probe = torch.empty(1, dtype=torch.uint8, device=dev).expand(shape)
             if not getattr(conv, "fused_epilogue_ready", lambda t: False)(probe):
                 raise _NoPlan("a conv is off the library path")
-            if conv.adc_shift or conv.stochastic_quant:
-                raise _NoPlan("shift-ADC and stochastic-ADC layers run in the loop")
-            ps = (conv.weight, conv.alpha_act, conv.alpha_weight, conv.alpha_cim)
+            if conv.stochastic_quant:
+                raise _NoPlan("stochastic-ADC layers run in the loop")
+            # (a shift-ADC layer that is ready is one the fused shift path takes: its prepared side carries beta_cim)
+            ps = (conv.weight, conv.alpha_act, conv.alpha_weight, conv.alpha_cim) + \
+                ((conv.beta_cim,) if conv.adc_shift else ())
             if any(t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev) for t in ps):
                 raise _NoPlan("parameters must be contiguous fp32 on the input's device")
             if conv.binary_mask.device != dev:
@@ -135,7 +137,7 @@ class _NetPlan:
             L.weight, L.alpha_act = conv.weight.data_ptr(), conv.alpha_act.data_ptr()
             L.alpha_weight = conv.alpha_weight.data_ptr()
             L.alpha_cim = None if conv.alpha_cim is None else conv.alpha_cim.data_ptr()
-            L.beta_cim = None
+            L.beta_cim = conv.beta_cim.data_ptr() if conv.adc_shift else None
             L.binary_mask, L.signed_act = bm.data_ptr(), sg.data_ptr()
             L.scale, L.shift, L.epi_flags = scale.data_ptr(), shift.data_ptr(), _lib.CIMQ_EPI_RELU
             L.in_slot = -1 if i == 0 else slot_of[i - 1]
@@ -250,7 +252,8 @@ class FusedEval(nn.Module):
     The plan (descriptors, prepared weight sides, folded tables, ctx buffers, one arena behind the activation slots,
     which are assigned by liveness: ``assign_slots``) is built once and reused while its key matches (``_net_state``).
     Every conv's output is bit for bit the loop's; the logits differ from the loop's by the summation order of the
-    pooling and of the classifier alone.  Where a conv is off the library path, the library refuses the plan or the
+    pooling and of the classifier alone.  Shift-ADC layers (``adc_shift``) on the fused shift path are plan layers
+    like any other; stochastic-ADC layers run in the loop.  Where a conv is off the library path, the library refuses the plan or the
     final map is not square, the loop runs: ``net_used`` says which of the two the last forward was."""
 
     def __init__(self, model, codes=False, net=False):
@@ -283,7 +286,8 @@ class FusedEval(nn.Module):
 
     def _net_state(self, x):
         """the key a plan is reused under: the input's shape and device, whether edges carry codes, and the
-        (_version, data_ptr) of every conv parameter, BatchNorm tensor and classifier tensor; None where a conv is
+        (_version, data_ptr) of every conv parameter (a shift layer's beta_cim among them), BatchNorm tensor and
+        classifier tensor; None where a conv is
         off the library path (the loop then runs, and says so)"""
         from ..functional import _versions
         chain, _ = self._chain_of()
@@ -295,7 +299,7 @@ class FusedEval(nn.Module):
             if bn.training:
                 raise RuntimeError("FusedEval: BatchNorm in training mode (call model.eval() first)")
             key.append(_versions(conv.weight, conv.alpha_act, conv.alpha_weight, conv.alpha_cim, conv.binary_mask,
-                                 conv.signed_act))
+                                 conv.signed_act, getattr(conv, "beta_cim", None)))
             key.append(_bn_versions(bn))
         lin = self.model.linear
         key.append(_versions(getattr(lin, "weight", None), getattr(lin, "bias", None)))

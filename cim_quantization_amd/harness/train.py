@@ -50,6 +50,9 @@ def get_base_parser():
     p.add_argument("--fused-net", action="store_true",
                    help="--fused-eval with each forward as one library call (FusedEval(model, net=True): "
                         "cimq_net_forward; combines with --fused-codes)")
+    p.add_argument("--adc-shift", action="store_true",
+                   help="Conv2dLSQCiM(adc_shift=True): the per-tile scale + shift ADC with a learnable beta_cim "
+                        "(adcbits 1 / 1.5; a launcher flag, not a prototxt field: the schema stays the reference's)")
     return p
 
 
@@ -128,8 +131,10 @@ def get_lr_scheduler(optimizer, hp):
     return GradualWarmup(optimizer, hp.warmup.multiplier, hp.warmup.epochs, nxt)
 
 
-def build_model(hp, device):
-    """Float ResNet -> weight file -> CiM replacement -> resume, as process_model."""
+def build_model(hp, device, adc_shift=False):
+    """Float ResNet -> weight file -> CiM replacement -> resume, as process_model.  ``adc_shift`` (--adc-shift):
+    every replaced conv is a Conv2dLSQCiM(adc_shift=True), with ``beta_cim`` in its state_dict; a resumed
+    checkpoint must then carry those keys (torch's own missing-key error otherwise)."""
     from .._modules.lsq import Conv2dLSQCiM
     if hp.model_source != eppb.HyperParam.ModelSource.Local:
         raise NotImplementedError("model_source must be Local (torchvision / pytorchcv are not available)")
@@ -138,20 +143,22 @@ def build_model(hp, device):
         model.load_state_dict(torch.load(hp.weight, map_location="cpu", weights_only=True))
     tool = ReplaceModuleTool(model, {"Conv2d": [Conv2dLSQCiM]}, True, nbits_w=hp.nbits_w, nbits_a=hp.nbits_a,
                              nbits_alpha=hp.nbits_alpha, wbitslice=hp.wbitslice, abitslice=hp.abitslice, xbar=hp.xbar,
-                             adcbits=hp.adcbits, signed_xbar=hp.signed_xbar, stochastic_quant=hp.stochastic_quant)
+                             adcbits=hp.adcbits, signed_xbar=hp.signed_xbar, stochastic_quant=hp.stochastic_quant,
+                             **({"adc_shift": True} if adc_shift else {}))
     tool.replace()
     arch = f"{hp.arch}_Conv2dLSQCiM"
     if hp.HasField("resume") and os.path.isfile(hp.resume):
         ck = torch.load(hp.resume, map_location="cpu", weights_only=True)
-        load_resume_state(model, ck.get("state_dict", ck))
+        load_resume_state(model, ck.get("state_dict", ck), require=("beta_cim",) if adc_shift else ())
     return model.to(device), arch
 
 
-def load_resume_state(model, state):
+def load_resume_state(model, state, require=()):
     """Resume from a checkpoint written here (the bare model's keys) or by the reference's
     main_lsq.py under DDP (main_lsq.py:121 saves the wrapped model, keys prefixed 'module.').
     The prefix is stripped or added to match ``model``; non-strict like the reference's resume,
-    but a checkpoint none of whose keys match is an error rather than a silent no-op."""
+    but a checkpoint none of whose keys match is an error rather than a silent no-op.  ``require``: parameter
+    names (last component) the checkpoint must not lack -- where it does, the strict load's own error is raised."""
     own = model.state_dict().keys()
     wrapped = any(k.startswith("module.") for k in own)
     fixed = {}
@@ -162,6 +169,8 @@ def load_resume_state(model, state):
     if fixed and len(res.unexpected_keys) == len(fixed):
         raise RuntimeError("resume: no checkpoint key matches the model (%d keys, e.g. %r)"
                            % (len(fixed), next(iter(fixed))))
+    if any(k.rsplit(".", 1)[-1] in require for k in res.missing_keys):
+        model.load_state_dict(fixed, strict=True)  # (raises: torch's own list of the missing keys)
     return res
 
 
@@ -251,7 +260,7 @@ def main(argv=None):
     if distributed:
         backend = hp.multi_gpu.dist_backend if hp.HasField("multi_gpu") else "nccl"
         dist.init_process_group(backend=backend, init_method="env://", world_size=world, rank=rank)
-    model, arch = build_model(hp, device)
+    model, arch = build_model(hp, device, adc_shift=args.adc_shift)
     batch = hp.batch_size // world if distributed else hp.batch_size
     if distributed:
         model = nn.parallel.DistributedDataParallel(model, device_ids=[local])

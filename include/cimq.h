@@ -224,9 +224,11 @@ int cimq_module_backward_params(const cimq_conv_desc* d, const cimq_lsq_desc* q,
  * Requires adc_variant = CIMQ_ADC_SHIFT_ROUND (no flags), adc_bits 1.5, input_kind =
  * CIMQ_INPUT_RAW_LSQ, nbw = nba = 2 or 3 and a layer the fast path takes (3x3, pad 1, stride 1 or 2,
  * power-of-two output width and channels); CIMQ_EUNSUPPORTED otherwise (the caller then quantises
- * in torch and calls cimq_shift_forward / cimq_shift_backward).  No prepared weight side
- * (q->wprep NULL), no CIMQ_LSQ_SKIP_TAIL.  beta_cim / grad_beta_cim: [1, T, nbw, nba, 1, O] like
- * alpha_cim; CIMQ_LSQ_ACCUMULATE_GRADS adds into grad_beta_cim as well.  Since ABI 8. */
+ * in torch and calls cimq_shift_forward / cimq_shift_backward).  A prepared weight side (q->wprep, made
+ * by cimq_module_prepare_shift) with a CIMQ_OPT_INFERENCE descriptor only: the backward reads nothing
+ * prepared, so a training descriptor with q->wprep set is CIMQ_EINVAL.  No CIMQ_LSQ_SKIP_TAIL.
+ * beta_cim / grad_beta_cim: [1, T, nbw, nba, 1, O] like alpha_cim; CIMQ_LSQ_ACCUMULATE_GRADS adds into
+ * grad_beta_cim as well.  Since ABI 8. */
 int cimq_module_shift_supported(const cimq_conv_desc* d); /* 1 if the two calls below take d, else 0 */
 
 /* Which kernels cimq_module_forward / cimq_module_backward run for d (the library ADC, the module entry
@@ -436,6 +438,35 @@ typedef struct cimq_prepare_item {
  * each optimizer step); the backward of that forward reads the buffer too, so it must not be
  * re-prepared in between. */
 int cimq_module_prepare(int n, const cimq_prepare_item* items, void* stream);
+
+/* One layer of cimq_module_prepare_shift: cimq_prepare_item's fields, and the shift ADC's beta_cim. */
+typedef struct cimq_prepare_shift_item {
+  const cimq_conv_desc* desc; /* CIMQ_OPT_INFERENCE set, adc_variant CIMQ_ADC_SHIFT_ROUND */
+  const cimq_lsq_desc* lsq;
+  const float* weight;
+  const float* alpha_act;
+  const float* alpha_weight;
+  const float* alpha_cim; /* required */
+  const int8_t* binary_mask;
+  void* wprep;
+  const float* beta_cim;  /* required, [1, T, nbw, nba, 1, O] */
+  int32_t reserved[2];    /* 0 */
+} cimq_prepare_shift_item;
+
+/* 1 where cimq_module_prepare_shift exists and the forward-only shift calls take q->wprep (a library from before
+ * them has no such symbol).  CIMQ_ABI_VERSION / _MINOR and cimq_net_abi() are unchanged. */
+int cimq_shift_prepare_abi(void);
+
+/* cimq_module_prepare for forward-only layers of the fused shift ADC (cimq_module_shift_supported): the same
+ * packing and the same wprep_bytes, with beta_cim folded into the ADC thresholds, the per-channel beta sums and the
+ * literal-ADC flag of a non-finite beta in the buffer.  cimq_module_shift_forward, cimq_module_forward_epilogue /
+ * _codes with beta_cim and a shift layer of a cimq_net_forward plan, given q->wprep = items[i].wprep, skip their
+ * weight blocks and write ``out`` / ``out_codes`` bit for bit as with q->wprep NULL; where the forward also
+ * quantises the activation in its own staging the layer is then one launch.  CIMQ_EINVAL: a NULL beta_cim or
+ * alpha_cim, a non-zero reserved, a descriptor without CIMQ_OPT_INFERENCE (the shift backward reads nothing
+ * prepared), a NULL among the other pointers.  CIMQ_EUNSUPPORTED: a descriptor cimq_module_shift_supported answers
+ * 0 for.  cimq_module_prepare itself refuses shift descriptors. */
+int cimq_module_prepare_shift(int n, const cimq_prepare_shift_item* items, void* stream);
 
 /* Opaque, caller-owned host memory for cimq_module_backward_chain: zero-initialise it once.
  * 16 KB since ABI 11. */

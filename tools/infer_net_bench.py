@@ -27,6 +27,12 @@ torch.cuda.max_memory_allocated of one forward of each.
     python tools/infer_net_bench.py --codes    # -> profiles/inference/infer_net_bench_codes_B256.json
     python tools/infer_net_bench.py --net --codes   # -> profiles/inference/infer_net_bench_net_B256.json
 
+Another network: ``--arch resnet56 --bits 2 --xbar 64 --adc-shift`` is BASELINE cfg4 (w2a2 on xbar 64 with the per-tile
+scale + shift ADC; -> profiles/inference/infer_net_bench_shift_B256.json).  ``--baseline-tree DIR``: side B (and its
+second window) comes from the package and the libcimq.so of another checkout of this repository, built there
+beforehand -- e.g. the parent commit's -- loaded into the same process under another name, on a model of its own
+made from the same seed; the other sides are this tree's.  The defaults, and the files they write, are unchanged.
+
 Needs the GPU: there is no CPU fallback and no number without a run.
 """
 from __future__ import annotations
@@ -50,12 +56,33 @@ from cim_quantization_amd.harness.fuse import FusedEval  # noqa: E402
 from cim_quantization_amd.harness.replace import ReplaceModuleTool  # noqa: E402
 
 
-def build_model(batch, dev):
+def load_baseline(tree):
+    """the cim_quantization_amd package of another checkout (with its own libcimq.so), imported as ``cimq_baseline``"""
+    import importlib.util
+    path = os.path.join(os.path.abspath(tree), "cim_quantization_amd")
+    if not os.path.exists(os.path.join(path, "libcimq.so")):
+        raise SystemExit(f"infer_net_bench: no libcimq.so in {path} (build that checkout first)")
+    spec = importlib.util.spec_from_file_location("cimq_baseline", os.path.join(path, "__init__.py"),
+                                                  submodule_search_locations=[path])
+    pkg = importlib.util.module_from_spec(spec)
+    sys.modules["cimq_baseline"] = pkg
+    spec.loader.exec_module(pkg)
+    return pkg
+
+
+def build_model(batch, dev, arch="resnet20", bits=3, xbar=bench.XBAR, adc_shift=False, pkg=None):
+    """``pkg``: the package to build the model from (load_baseline); default this tree's"""
+    mods, conv_cls, tool_cls = models, Conv2dLSQCiM, ReplaceModuleTool
+    if pkg is not None:
+        import importlib
+        mods = importlib.import_module(pkg.__name__ + ".harness.models")
+        conv_cls = importlib.import_module(pkg.__name__ + "._modules.lsq").Conv2dLSQCiM
+        tool_cls = importlib.import_module(pkg.__name__ + ".harness.replace").ReplaceModuleTool
     torch.manual_seed(20)
-    model = models.resnet20()
-    ReplaceModuleTool(model, {"Conv2d": [Conv2dLSQCiM]}, True, nbits_w=3, nbits_a=3, nbits_alpha=8, wbitslice=1,
-                      abitslice=1, xbar=bench.XBAR, adcbits=bench.ADC, signed_xbar=True,
-                      stochastic_quant=False).replace()
+    model = getattr(mods, arch)()
+    tool_cls(model, {"Conv2d": [conv_cls]}, True, nbits_w=bits, nbits_a=bits, nbits_alpha=8, wbitslice=1,
+             abitslice=1, xbar=xbar, adcbits=bench.ADC, signed_xbar=True, stochastic_quant=False,
+             **({"adc_shift": True} if adc_shift else {})).replace()
     model = model.to(dev).train()
     x = torch.randn(batch, 3, 32, 32, generator=torch.Generator().manual_seed(21)).to(dev)
     model(x)  # the first-step initialisation of every layer, and BatchNorm statistics that are not the defaults
@@ -97,15 +124,28 @@ def main(argv=None):
     ap.add_argument("--codes", action="store_true", help="add side C, FusedEval(model, codes=True): A, B, C, B per round")
     ap.add_argument("--net", action="store_true",
                     help="add side D, FusedEval(model, net=True) (with --codes also E, net=True and codes=True)")
+    ap.add_argument("--arch", default="resnet20", choices=("resnet20", "resnet32", "resnet44", "resnet56"))
+    ap.add_argument("--bits", type=int, default=3, help="weight and activation bits of every conv but the first")
+    ap.add_argument("--xbar", type=int, default=bench.XBAR)
+    ap.add_argument("--adc-shift", action="store_true", help="Conv2dLSQCiM(adc_shift=True) layers")
+    ap.add_argument("--baseline-tree", default=None,
+                    help="another checkout of this repository, built: side B runs its package and library")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("infer_net_bench: no ROCm device (there is no CPU fallback; nothing is measured)")
-    out_path = args.out or os.path.join(REPO, "profiles", "inference",
-                                        f"infer_net_bench{'_net' if args.net else '_codes' if args.codes else ''}_B{args.batch}.json")
+    tag = "_shift" if args.adc_shift else "_net" if args.net else "_codes" if args.codes else ""
+    out_path = args.out or os.path.join(REPO, "profiles", "inference", f"infer_net_bench{tag}_B{args.batch}.json")
     dev = torch.device("cuda:0")
-    model, x = build_model(args.batch, dev)
-    fused = FusedEval(model)
+    net_kw = dict(arch=args.arch, bits=args.bits, xbar=args.xbar, adc_shift=args.adc_shift)
+    model, x = build_model(args.batch, dev, **net_kw)
+    if args.baseline_tree:  # side B from the other checkout: its modules, its FusedEval, its library
+        import importlib
+        base = load_baseline(args.baseline_tree)
+        base_model, _ = build_model(args.batch, dev, pkg=base, **net_kw)
+        fused = importlib.import_module("cimq_baseline.harness.fuse").FusedEval(base_model)
+    else:
+        fused = FusedEval(model)
     sides = {"A": lambda: model(x), "B": lambda: fused(x)}
     order = ("A", "B", "A2")
     if args.codes:
@@ -164,8 +204,9 @@ def main(argv=None):
     twin = order[-1]  # the repeated side: the same code, the same call
     spread = max(abs(a - b) for a, b in zip(tot[twin[0]], tot[twin]))
     result = {
-        "workload": f"harness ResNet-20 evaluation forward (model(x) vs FusedEval(model)(x)), eval + no_grad, "
-                    f"B = {args.batch}, w3a3 (first conv w8a8), xbar {bench.XBAR}, adc {bench.ADC}, synthetic input",
+        "workload": f"harness ResNet-{args.arch[6:]} evaluation forward (model(x) vs FusedEval(model)(x)), eval + no_grad, "
+                    f"B = {args.batch}, w{args.bits}a{args.bits} (first conv w8a8), xbar {args.xbar}, adc {bench.ADC}"
+                    f"{', scale + shift ADC (adc_shift)' if args.adc_shift else ''}, synthetic input",
         "device": torch.cuda.get_device_name(0), "abi": _lib.ABI_VERSION,
         "passes_per_window": passes, "rounds": args.rounds,
         "forward_us": {k: round(v, 1) for k, v in med.items()},
@@ -177,6 +218,9 @@ def main(argv=None):
         "peak_memory_bytes": peak,
         "fused_vs_batchnorm_path": diff,
     }
+    if args.baseline_tree:
+        result["workload"] += "; side B (and B2) from the baseline checkout's package and libcimq.so, the others from this tree"
+        result["B_from_baseline_tree"] = True
     if args.codes:
         result["workload"] += "; side C = FusedEval(model, codes=True)(x)"
         result["abi_minor"] = _lib.ABI_MINOR

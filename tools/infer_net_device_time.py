@@ -11,6 +11,9 @@ device.  It is a profiler run, not a kernel trace with counters.
 
     python tools/infer_net_device_time.py [--batch 256] [--out profiles/inference/infer_net_device_time_B256.json]
 
+``--arch resnet56 --bits 2 --xbar 64 --adc-shift`` and ``--baseline-tree DIR`` as tools/infer_net_bench.py takes them
+(-> profiles/inference/infer_net_device_time_shift_B256.json; side B then comes from the other checkout).
+
 Needs the GPU: there is no CPU fallback and no number without a run.
 """
 from __future__ import annotations
@@ -62,16 +65,32 @@ def measure(fn, x, issue=50, profiled=5):
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--arch", default="resnet20", choices=("resnet20", "resnet32", "resnet44", "resnet56"))
+    ap.add_argument("--bits", type=int, default=3)
+    ap.add_argument("--xbar", type=int, default=nb.bench.XBAR)
+    ap.add_argument("--adc-shift", action="store_true")
+    ap.add_argument("--baseline-tree", default=None)
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("infer_net_device_time: no ROCm device (there is no CPU fallback; nothing is measured)")
-    out_path = args.out or os.path.join(REPO, "profiles", "inference", f"infer_net_device_time_B{args.batch}.json")
-    model, x = nb.build_model(args.batch, torch.device("cuda:0"))
+    out_path = args.out or os.path.join(REPO, "profiles", "inference",
+                                        f"infer_net_device_time{'_shift' if args.adc_shift else ''}_B{args.batch}.json")
+    net_kw = dict(arch=args.arch, bits=args.bits, xbar=args.xbar, adc_shift=args.adc_shift)
+    model, x = nb.build_model(args.batch, torch.device("cuda:0"), **net_kw)
+    loop = FusedEval(model)
+    if args.baseline_tree:  # side B from the other checkout: its modules, its FusedEval, its library
+        import importlib
+        base = nb.load_baseline(args.baseline_tree)
+        base_model, _ = nb.build_model(args.batch, torch.device("cuda:0"), pkg=base, **net_kw)
+        loop = importlib.import_module("cimq_baseline.harness.fuse").FusedEval(base_model)
     with torch.no_grad():
-        sides = {"B": measure(FusedEval(model), x), "C": measure(FusedEval(model, codes=True), x),
+        sides = {"B": measure(loop, x), "C": measure(FusedEval(model, codes=True), x),
                  "D": measure(FusedEval(model, net=True), x), "E": measure(FusedEval(model, net=True, codes=True), x)}
-    result = {"workload": f"harness ResNet-20 fused evaluation forward, B = {args.batch}: B = FusedEval(model), "
+    default = (args.arch, args.bits, args.xbar, args.adc_shift, args.baseline_tree) == ("resnet20", 3, nb.bench.XBAR, False, None)
+    cfg = "" if default else (f" (w{args.bits}a{args.bits}, xbar {args.xbar}{', adc_shift' if args.adc_shift else ''}"
+                              f"{'; side B from the baseline checkout' if args.baseline_tree else ''})")
+    result = {"workload": f"harness ResNet-{args.arch[6:]}{cfg} fused evaluation forward, B = {args.batch}: B = FusedEval(model), "
                           "C = FusedEval(model, codes=True), D = FusedEval(model, net=True), E = net=True and codes=True; "
                           "host issue and wall over 50 forwards, device kernel time "
                           "from torch.profiler over 5 forwards",
