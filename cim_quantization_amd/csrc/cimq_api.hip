@@ -491,6 +491,11 @@ static int lsq_args(const Geo& g, const cimq_lsq_desc* q, LsqArgs* a) {
   return CIMQ_OK;
 }
 
+// the module prologue's weight-side blocks: 256 items of its operands and parameter tables each, 1024 at the most
+static int prep_wblocks(const ModulePrep& a) {
+  return std::max(1, std::min(cdiv(a.nwf + a.nwg + a.nwc + a.nw5 + a.nwx5 + a.nwx6 + a.npp, 256), 1024));
+}
+
 // the module prologue's arguments: activation side into ctx c, weight side into wreg(g, c)
 static ModulePrep module_prep_args(const Geo& g, const float* x, const float* weight, const float* alpha_act,
                                    const float* alpha_weight, const float* alpha_cim, const int8_t* binary_mask,
@@ -530,7 +535,7 @@ static ModulePrep module_prep_args(const Geo& g, const float* x, const float* we
   a.wx6 = reinterpret_cast<v4i*>(wr + L.wx6);
   a.nwx6 = r.wx6 ? (int)(r6_frag_bytes(g) / 16) : 0;  // cim_bwd_r6_kernel's gx operand
   a.npp = g.T * g.nba * g.nbw * g.Opad + g.nbw * g.nba;
-  *nwblk = std::max(1, std::min(cdiv(a.nwf + a.nwg + a.nwc + a.nw5 + a.nwx5 + a.nwx6 + a.npp, 256), 1024));
+  *nwblk = prep_wblocks(a);
   return a;
 }
 
@@ -584,6 +589,11 @@ static int check_epilogue(const char* who, const cimq_epilogue* epi, const float
     return fail(CIMQ_EINVAL, "%s: residual must be 16-byte aligned", who);
   if (beta_cim && !alpha_cim) return fail(CIMQ_EINVAL, "%s: beta_cim needs alpha_cim", who);
   return CIMQ_OK;
+}
+
+// the kernels' form of a checked epilogue (codes and view fields zero)
+static Epi epi_of(const cimq_epilogue* epi) {
+  return Epi{epi->scale, epi->shift, epi->residual, (epi->flags & CIMQ_EPI_RELU) ? 1 : 0};
 }
 
 // a clamp maximum that codes can carry: an integer in [1, 254], so that the NaN code Qp + 1 fits a byte
@@ -658,7 +668,7 @@ static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
     if (beta_cim) {  // the shift ADC: beta into the thresholds, and the per-channel beta sums
       a.beta = beta_cim;
       a.npp += g.Opad;
-      nwblk = std::max(1, std::min(cdiv(a.nwf + a.nwg + a.nwc + a.nw5 + a.nwx5 + a.nwx6 + a.npp, 256), 1024));
+      nwblk = prep_wblocks(a);
     }
     if (g.wbase) nwblk = 0;  // weight side prepared (cimq_module_prepare): the activation quantiser only
     if (r.actq) a.nact_blocks = 0;  // the forward's row staging quantises (stage_rows_q)
@@ -700,10 +710,12 @@ prepared:
   float* bpo = reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(ws) + W.bpo);
   CIMQ_TRY(launch_fwd_any(g, c, scal + 1, scal, bpo, nullptr, nullptr, s));
   const dim3 tgrid(std::min(cdiv((long long)g.M * g.O, 256), 8192));
-  if (ep && ep->rvw1) hipLaunchKernelGGL(bpo_to_nchw_view_kernel, tgrid, dim3(256), 0, s, g, bpo, out, *ep);
-  else if (ep && oq) hipLaunchKernelGGL(bpo_to_nchw_codes_kernel, tgrid, dim3(256), 0, s, g, bpo, out, *ep);
-  else if (ep) hipLaunchKernelGGL(bpo_to_nchw_epi_kernel, tgrid, dim3(256), 0, s, g, bpo, out, *ep);
-  else hipLaunchKernelGGL(bpo_to_nchw_kernel, tgrid, dim3(256), 0, s, g, bpo, out);
+  switch (fwd_mode_of(g, ep)) {  // (of codes, out_codes alone get here: x_codes were cleared above)
+    case FwdMode::VIEW: hipLaunchKernelGGL(bpo_to_nchw_view_kernel, tgrid, dim3(256), 0, s, g, bpo, out, *ep); break;
+    case FwdMode::CODES: hipLaunchKernelGGL(bpo_to_nchw_codes_kernel, tgrid, dim3(256), 0, s, g, bpo, out, *ep); break;
+    case FwdMode::EPI: hipLaunchKernelGGL(bpo_to_nchw_epi_kernel, tgrid, dim3(256), 0, s, g, bpo, out, *ep); break;
+    default: hipLaunchKernelGGL(bpo_to_nchw_kernel, tgrid, dim3(256), 0, s, g, bpo, out);
+  }
   return check_hip("bpo_to_nchw");
 }
 
@@ -752,7 +764,7 @@ int cimq_module_forward_epilogue(const cimq_conv_desc* d, const cimq_lsq_desc* q
   // (the descriptor-independent refusals first, before any other argument is looked at)
   CIMQ_TRY(check_forward_only(who_epi, d));
   CIMQ_TRY(check_epilogue(who_epi, epi, alpha_cim, beta_cim));
-  const Epi ep{epi->scale, epi->shift, epi->residual, (epi->flags & CIMQ_EPI_RELU) ? 1 : 0};
+  const Epi ep = epi_of(epi);
   return module_forward_impl(d, q, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act,
                              out, ctx, ws, stream, &ep);
 }
@@ -789,7 +801,7 @@ static int forward_codes_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, c
   if (io->flags & ~CIMQ_CODES_NO_FLOAT) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: unknown flags 0x%x", io->flags);
   if (io->reserved != 0) return fail(CIMQ_EINVAL, "cimq_module_forward_codes: reserved must be 0");
   if (!io->x_codes && !io->out_codes && !io->flags) {  // no codes: cimq_module_forward_epilogue
-    Epi ep{epi->scale, epi->shift, epi->residual, (epi->flags & CIMQ_EPI_RELU) ? 1 : 0};
+    Epi ep = epi_of(epi);
     if (view) set_res_view(&ep, view->c0, view->cr, view->s, view->h, view->w);
     return module_forward_impl(d, q, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act,
                                out, ctx, ws, stream, &ep, dry);
@@ -804,7 +816,7 @@ static int forward_codes_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, c
   }
   if (reinterpret_cast<uintptr_t>(io->x_codes) % 16 != 0 || reinterpret_cast<uintptr_t>(io->out_codes) % 16 != 0)
     return fail(CIMQ_EINVAL, "cimq_module_forward_codes: code buffers must be 16-byte aligned");
-  Epi ep{epi->scale, epi->shift, epi->residual, (epi->flags & CIMQ_EPI_RELU) ? 1 : 0};
+  Epi ep = epi_of(epi);
   ep.nofloat = (io->flags & CIMQ_CODES_NO_FLOAT) ? 1 : 0;
   ep.xq = io->x_codes;
   ep.oq = io->out_codes;
@@ -1065,7 +1077,7 @@ static int prepare_run(const std::vector<PrepView>& v, bool shift, hipStream_t s
     if (it.beta) {  // the shift ADC: beta into the thresholds, and the per-channel beta sums (as module_forward_impl)
       j.a.beta = it.beta;
       j.a.npp += g.Opad;
-      j.nwblk = std::max(1, std::min(cdiv(j.a.nwf + j.a.nwg + j.a.nwc + j.a.nw5 + j.a.nwx5 + j.a.nwx6 + j.a.npp, 256), 1024));
+      j.nwblk = prep_wblocks(j.a);
     }
     j.a.nact_blocks = 0;
     pk.blk0[pk.n] = grid;

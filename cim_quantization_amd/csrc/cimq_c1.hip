@@ -5,7 +5,7 @@
 // The first conv has K = C*9 <= 32 rows and 64 slice pairs (36 live under the int8-wrapped
 // binary_mask): its forward's state words would be three 64-bit planes per (pixel, channel),
 // 24 B against 4 B of output, read back twice by the v7 backward.  Here the forward writes none
-// (cim_fwd_v3_kernel<8, 1, 9, 1>), and one workgroup per image walks it in steps of 128 output
+// (cim_fwd_v3_kernel<8, 1, 8, RECOMPUTE, TRAIN, 1>), and one workgroup per image walks it in steps of 128 output
 // pixels; each wave recomputes its 16 pixels' partial sums with the pixels as MFMA rows (lane: channel o,
 // 4 pixels: the layout of grad_w's B operand on v_mfma_f32_16x16x16_bf16 and of the grad_alpha code sums)
 // and takes the STE pass bits and ADC codes from the same integer thresholds as the forward (or the

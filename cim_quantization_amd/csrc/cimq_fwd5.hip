@@ -28,26 +28,21 @@ namespace cimq {
 // NOB 16-channel output blocks per block (512 threads each): the NOB halves share the block's staged
 // activation patch (f5_plan: NOB = 2 where OB16 is even, one 1024-thread block per CU)
 // WST: write the backward's state words and ctx (false where the module backward recomputes the partial sums,
-// cim_bwd_r6_kernel: the forward then writes only `out`, and its ADC epilogue skips the state-bit shifts)
-// EPI (forward only, with WST false): the output epilogue ep on the float4 about to be stored (epi_val4); the other
-// instances never read ep
-// NOBA: NOB = NOBA & 3; NOBA 4 + NOB (with EPI) is the code instance of cimq_module_forward_codes -- the staging
-// reads the input's codes (ep.xq: one byte per element, straight into the word table, no division) or fp32 x, and
-// the store writes the float4, the consumer's codes (ep.oq) or both: block-uniform branches on ep.  Encoded in
-// NOBA so that the other instances keep their symbols and their code.
-template <int NOBA, bool WST, bool EPI = false>
-__global__ __attribute__((amdgpu_flat_work_group_size(512 * (NOBA & 3), 512 * (NOBA & 3)), amdgpu_waves_per_eu(4, 4))) void cim_fwd5_kernel(
+// cim_bwd_r6_kernel, and in a forward-only call: the forward then writes only `out`, and its ADC epilogue skips the
+// state-bit shifts)
+// M (FwdMode; with WST false from EPI on): the output epilogue ep on the float4 about to be stored (epi_val4); with
+// codes, the staging reads the input's codes (ep.xq: one byte per element, straight into the word table, no division)
+// or fp32 x, and the store writes the float4, the consumer's codes (ep.oq) or both; with the view, the residual costs
+// four scalar loads per float4.  A forward-only call without an epilogue runs the WST false training instance.
+template <int NOB, bool WST, FwdMode M>
+__global__ __attribute__((amdgpu_flat_work_group_size(512 * NOB, 512 * NOB), amdgpu_waves_per_eu(4, 4))) void cim_fwd5_kernel(
     Geo g, F5 v, const v4i* __restrict__ wf5, Params pp, const float* __restrict__ sw_p,
     const float* __restrict__ sa_p, const float* __restrict__ x, const float* __restrict__ sgn_p,
     float* __restrict__ out, uint32_t* __restrict__ st, uint32_t* __restrict__ xcb, uint32_t* __restrict__ cal,
     Epi ep) {
-  constexpr int NOB = NOBA & 3;
-  constexpr bool COD = NOBA >= 4;
-  // NOBA 8 + NOB: the code instance with the residual read as a view (Epi::rvw0 / rvw1, cimq_net_forward's option-A
-  // shortcut: four scalar loads per float4) -- instances of their own, so that the 4 + NOB ones keep their code
-  constexpr bool VIEW = NOBA >= 8;
+  constexpr bool EPI = has_epi(M), COD = has_codes(M), VIEW = has_view(M);
+  static_assert(M != FwdMode::INFER, "forward only without an epilogue: the <NOB, false, TRAIN> instance as it is");
   static_assert(!(EPI && WST), "the epilogue instances are forward only");
-  static_assert(!COD || EPI, "the code instances carry the epilogue");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int obl = wave >> 3, pw = wave & 7;  // this wave's output block within the block, its pixel group

@@ -863,7 +863,8 @@ struct Route {
   int fwd, gx, gw;   // CIMQ_ROUTE_*; gx = gw = CIMQ_ROUTE_NONE in a forward-only call (CIMQ_OPT_INFERENCE)
   bool actq;         // the forward quantises the activation in its own row staging: no prologue pass over x
   StateFmt state;
-  int cst;           // cim_fwd_v3_kernel's CST instance for that format (forward only: the 10 + CST forms)
+  int cst;           // cim_fwd_v3_kernel's CST for the forward family's format (0 / 2 / 3 / 8), in any call
+  FwdState fst;      // ... and what it does with that format's words: RECOMPUTE is ST_C1's, in any call
   size_t st_bytes;   // the ctx's state-word region
   bool codes;        // the ctx holds one activation-code byte per element, not the 4-byte backward word
   bool lsq_fused;    // grad_x runs the act-LSQ backward too, leaving act_parts partials in the workspace
@@ -931,7 +932,8 @@ inline Route route_compute(const Geo& g) {
                      : g.NBP == 8            ? ST_PLANES
                                              : ST_V7;
   r.state = r.gx == CIMQ_ROUTE_R6 ? ST_NONE : fam;
-  r.cst = fam == ST_V7 ? g.nbw : fam == ST_PLANES ? 8 : fam == ST_C1 ? 9 : 0;
+  r.cst = fam == ST_V7 ? g.nbw : (fam == ST_PLANES || fam == ST_C1) ? 8 : 0;
+  r.fst = fam == ST_C1 ? FwdState::RECOMPUTE : FwdState::WRITE;
   // (the region holds any format of the shape: the v7 words are never larger than the per-k ones for nbw >= 2,
   // the max covers nbw == 1)
   r.st_bytes = r.state == ST_NONE ? (size_t)0
@@ -951,12 +953,20 @@ inline Route route_compute(const Geo& g) {
     r.gx = r.gw = CIMQ_ROUTE_NONE;
     r.state = ST_NONE;
     r.st_bytes = 0;
-    if (r.cst == 2 || r.cst == 3 || r.cst == 8) r.cst += 10;
+    if (r.cst != 0 && r.fst == FwdState::WRITE) r.fst = FwdState::NONE;  // (CST 0 writes no state as it is)
     r.codes = r.lsq_fused = r.gw_own = r.gxw5 = r.wgx = r.wcy = r.wg5 = r.wx6 = false;
   }
   return r;
 }
 inline Route route_of(const Geo& g) { return memo_geo<Route, route_compute>(g); }
+
+// which mode a forward call is: the one place that reads the call's Epi to decide a kernel instance (the launchers
+// of the three forward families, and the transposer after the general kernel).  It only classifies: what a route
+// cannot run is refused where the call is checked (module_forward_impl)
+inline FwdMode fwd_mode_of(const Geo& g, const Epi* ep) {
+  if (!ep) return g.inference ? FwdMode::INFER : FwdMode::TRAIN;
+  return ep->rvw1 ? FwdMode::VIEW : (ep->xq || ep->oq) ? FwdMode::CODES : FwdMode::EPI;
+}
 
 // the module entry points' form of a geometry: NCHW output where the fast forward runs, fixed before anything
 // is asked of it ([B, P, O] through the workspace for the dense and general forwards)

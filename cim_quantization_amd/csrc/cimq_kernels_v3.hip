@@ -25,11 +25,16 @@ namespace cimq {
 // ---------------------------------------------------------------------------------------
 
 // CST: compact state words (cimq_v7.hip) -- one uint32 per (tile i, pixel m, channel o) at
-// st32[(i*M + m)*O + o], bits 3*(k*nba + j) + {0: STE pass, 1: code != 0, 2: code < 0}.
+// st32[(i*M + m)*O + o], bits 3*(k*nba + j) + {0: STE pass, 1: code != 0, 2: code < 0}; 0: the per-k words.
 // CST > 0 also fixes nbw = nba = CST at compile time: the ternary-threshold path then runs
-// (CSTA = 9: CST 8 without writing the state words -- the first conv's backward recomputes them)
 // fully unrolled (every slice pair's MFMAs issued before its ADC work, state bits shifted in).
-template <int NBP, int KS, int CSTA, int OBM>
+// ST: what becomes of those words (FwdState).  M: what the store does (FwdMode) -- the epilogue ep on the float4
+// about to be stored (NCHW only); with codes, the row staging reads the input's codes (ep.xq: bytes straight into
+// the word table, stage_rows_qc) or quantises fp32 x as before, and the store writes the float4, the consumer's
+// codes (ep.oq) or both; the view costs four scalar loads per float4 and, inside the code instances, a wave per
+// SIMD of <4, 1, 0, WRITE, CODES, 2> (96 -> 97 VGPRs): hence instances of its own.
+// xin (module path, NBP 4): the activation quantiser fused into the row staging (stage_rows_q)
+template <int NBP, int KS, int CST, FwdState ST, FwdMode M, int OBM>
 __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint8_t* __restrict__ xcf,
                                                          const v4i* __restrict__ wfrag, Params pp,
                                                          const float* __restrict__ sw_p,
@@ -37,27 +42,15 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
                                                          uint8_t* __restrict__ st, const float* __restrict__ xin,
                                                          const float* __restrict__ sgn_p, uint8_t* __restrict__ xcb,
                                                          Epi ep) {
-  // CSTA 9: the w8a8 fast path of CST 8 without the state words (cimq_c1.hip recomputes them)
-  // CSTA 12 / 13 / 18: CST 2 / 3 / 8 forward only (CIMQ_OPT_INFERENCE) -- no state words, none of their bits on
-  // either ADC path, and no backward words through xcb.  (CST 0 writes no state as it is.)  Encoded in CSTA so
-  // that the training instances keep their symbols and their code.
-  // xin (module path, NBP 4): the activation quantiser fused into the row staging (stage_rows_q)
-  // CSTA 20 + s, s one of the stateless 0 / 9 / 12 / 13 / 18: the same with the output epilogue ep on the float4
-  // about to be stored (cimq_module_forward_epilogue, NCHW only); no other instance reads ep
-  // CSTA 40 + s: the code instance of CSTA 20 + s (cimq_module_forward_codes) -- the row staging reads the
-  // input's codes (ep.xq: bytes straight into the word table, stage_rows_qc) or quantises fp32 x as before, and the
-  // store writes the float4, the consumer's codes (ep.oq) or both: block-uniform branches on ep
-  // CSTA 60 + s: the code instance with the residual read as a view (Epi::rvw0 / rvw1, cimq_net_forward's
-  // option-A shortcut: four scalar loads per float4).  Instances of their own: inside the 40 + s ones the view cost
-  // cim_fwd_v3_kernel<4, 1, 40, 2> a wave per SIMD (96 -> 97 VGPRs)
-  constexpr bool VIEW = CSTA >= 60;
-  constexpr bool COD = CSTA >= 40;
-  constexpr bool EPI = CSTA >= 20;
-  constexpr int CSTB = VIEW ? CSTA - 60 : COD ? CSTA - 40 : EPI ? CSTA - 20 : CSTA;
-  static_assert(!EPI || CSTB == 0 || CSTB == 9 || CSTB >= 10, "the epilogue instances are forward only");
-  constexpr int CST = CSTB == 9 ? 8 : CSTB >= 10 ? CSTB - 10 : CSTB;
-  constexpr bool WST = CSTB < 9;
-  constexpr bool INF = CSTB >= 10;
+  constexpr bool VIEW = has_view(M), COD = has_codes(M), EPI = has_epi(M);
+  constexpr bool WST = ST == FwdState::WRITE;
+  constexpr bool INF = ST == FwdState::NONE;
+  static_assert(CST == 0 || CST == 2 || CST == 3 || CST == 8, "state formats: per-k words, w2a2, w3a3, w8a8 planes");
+  static_assert(CST != 0 || WST, "CST 0 writes no state words as it is: one form, spelled WRITE, for every call");
+  static_assert(ST != FwdState::RECOMPUTE || CST == 8, "the recomputing backward is the w8a8 first conv's");
+  static_assert(M != FwdMode::TRAIN || !INF, "a training instance leaves the backward its words, or recomputes them");
+  static_assert(M != FwdMode::INFER || INF, "forward only is the stateless form of a compact format");
+  static_assert(!EPI || CST == 0 || !WST, "the epilogue instances are forward only");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int og = blockIdx.y;
   const int NOB = min(OBM, g.OB16);
@@ -334,7 +327,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
                   const uint64_t mhi = __builtin_amdgcn_ballot_w64(ps[j][r] >= pv.x);
                   const uint64_t mlo = __builtin_amdgcn_ballot_w64(ps[j][r] <= pv.y);
                   acc[ob][r] += adc3(cf, mhi, mlo);
-                  if constexpr (!WST) continue;  // (CSTA 9: no state words -- and none of their bits)
+                  if constexpr (!WST) continue;  // (no state words -- and none of their bits)
                   const uint64_t mps = __builtin_amdgcn_ballot_w64((unsigned)(ps[j][r] - pv.z) <= (unsigned)pv.w);
                   const uint64_t mnz = mhi | mlo;
                   if constexpr (PLF) {

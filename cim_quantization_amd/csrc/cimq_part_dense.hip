@@ -107,13 +107,16 @@ __device__ inline uint32_t spread16(uint32_t x) {
 // ---------------------------------------------------------------------------------------------
 // forward: block = 64 rows x 64 channels, wave w = rows 16w..16w+15 x four 16-channel blocks (in turn)
 // ---------------------------------------------------------------------------------------------
-// WST false (the forward-only instances): no state planes, none of their bits
-// EPI (forward only): the output epilogue ep on each value about to be stored (P = 1: out is NCHW as it is)
-template <int NBW, int NBA, int KS, bool LIT, bool WST = true, bool EPI = false>
+// M (FwdMode, of the three forward kernels): forward only writes no state planes through st and none of their
+// bits; the epilogue ep goes on each value about to be stored (P = 1: out is NCHW as it is).  The dense route has
+// no code or view instances.
+template <int NBW, int NBA, int KS, bool LIT, FwdMode M>
 __device__ inline void dense_fwd_body(const Geo& g, const uint8_t* __restrict__ xcf, const v4i* __restrict__ wfrag,
                                       const Params& pp, float sw, float sa, float* __restrict__ out,
                                       uint2* __restrict__ st, int4* prm, float* cfl, float4* accs, int m0,
                                       int og, const Epi& ep) {
+  static_assert(!has_codes(M), "the dense route has no code or view instances");
+  constexpr bool WST = writes_state(M), EPI = has_epi(M);
   constexpr int NKJ = NBW * NBA;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r16 = lane & 15, g4 = lane >> 4;
@@ -234,22 +237,16 @@ __device__ inline void dense_fwd_body(const Geo& g, const uint8_t* __restrict__ 
 
 // The threshold path: one 64 x 64 tile per block.  Exits at once when the prologue set the
 // literal-ADC flag (dense_fwd_lit_kernel then does the work).
-// KSA (the three forward kernels): the K-steps per tile KS = KSA & 3; KSA >= 4 is the forward-only instance
-// (CIMQ_OPT_INFERENCE: no state planes through st) -- encoded there so that the training instances keep their
-// symbols and their code; KSA >= 8 (12 + KS) is the forward-only instance with the output epilogue ep
-template <int NBW, int NBA, int KSA>
+template <int NBW, int NBA, int KS, FwdMode M>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void dense_fwd_kernel(
     Geo g, const uint8_t* __restrict__ xcf, const v4i* __restrict__ wfrag, Params pp, const float* __restrict__ sw_p,
     const float* __restrict__ sa_p, float* __restrict__ out, uint2* __restrict__ st, Epi ep) {
-  constexpr int KS = KSA & 3;
-  constexpr bool WST = KSA < 4;
-  constexpr bool EPI = KSA >= 8;
   __shared__ int4 prm[NBW * NBA * 64];  // this tile's ADC / STE thresholds, [j][k][64 channels]
   __shared__ float cfl[NBW * NBA * 64];
   __shared__ float4 accs[4 * 4 * 64];
   if (__builtin_amdgcn_readfirstlane(pp.flags[0]) != 0) return;
-  dense_fwd_body<NBW, NBA, KS, false, WST, EPI>(g, xcf, wfrag, pp, 0.f, 0.f, out, st, prm, cfl, accs, blockIdx.x * 64,
-                                           blockIdx.y, ep);
+  dense_fwd_body<NBW, NBA, KS, false, M>(g, xcf, wfrag, pp, 0.f, 0.f, out, st, prm, cfl, accs, blockIdx.x * 64, blockIdx.y,
+                                         ep);
 }
 
 // The threshold path on 128 x 64 tiles (512 threads, wave w = rows 16w..16w+15): the weight fragments
@@ -258,13 +255,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void d
 // forward).  The weight fragments go in two halves (output blocks 0-1, then 2-3) so a block stays under
 // 80 KB of LDS: two blocks per CU.  Per partial sum the ADC / state bits are adc_ps, in the same order:
 // out and the state words are bit-identical to dense_fwd_kernel's.
-template <int NBW, int NBA, int KSA>
+template <int NBW, int NBA, int KS, FwdMode M>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void dense_fwd8_kernel(
     Geo g, const uint8_t* __restrict__ xcf, const v4i* __restrict__ wfrag, Params pp, float* __restrict__ out,
     uint2* __restrict__ st, Epi ep) {
-  constexpr int KS = KSA & 3;
-  constexpr bool WST = KSA < 4;
-  constexpr bool EPI = KSA >= 8;
+  static_assert(!has_codes(M), "the dense route has no code or view instances");
+  constexpr bool WST = writes_state(M), EPI = has_epi(M);
   constexpr int NKJ = NBW * NBA;
   constexpr int NWH = KS * NBW * 2 * 64;  // v4i of one half's weight fragments
   __shared__ int4 prm[NKJ * 64];          // [j][k][64 channels]: thi, tlo, mlo, span
@@ -381,22 +377,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4))) void d
 
 // Degenerate alpha_q / scales (flag set): the literal ADC per partial sum, a few blocks looping
 // over the tiles (its out-of-line calls kept out of the threshold kernel's register budget).
-template <int NBW, int NBA, int KSA>
+template <int NBW, int NBA, int KS, FwdMode M>
 __global__ __launch_bounds__(256) void dense_fwd_lit_kernel(Geo g, const uint8_t* __restrict__ xcf,
                                                             const v4i* __restrict__ wfrag, Params pp,
                                                             const float* __restrict__ sw_p,
                                                             const float* __restrict__ sa_p, float* __restrict__ out,
                                                             uint2* __restrict__ st, Epi ep) {
-  constexpr int KS = KSA & 3;
-  constexpr bool WST = KSA < 4;
-  constexpr bool EPI = KSA >= 8;
   __shared__ float4 accs[4 * 4 * 64];
   if (__builtin_amdgcn_readfirstlane(pp.flags[0]) == 0) return;
   const float sw = *sw_p, sa = *sa_p;
   const int nm = g.M / 64, ntile = nm * (g.O / 64);
   for (int t = blockIdx.x; t < ntile; t += gridDim.x)
-    dense_fwd_body<NBW, NBA, KS, true, WST, EPI>(g, xcf, wfrag, pp, sw, sa, out, st, nullptr, nullptr, accs, (t % nm) * 64,
-                                                 t / nm, ep);
+    dense_fwd_body<NBW, NBA, KS, true, M>(g, xcf, wfrag, pp, sw, sa, out, st, nullptr, nullptr, accs, (t % nm) * 64, t / nm,
+                                          ep);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -713,31 +706,31 @@ __global__ __launch_bounds__(512) void dense_gw_kernel(Geo g, int rows_per_chunk
 // ---------------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------------
+// NAME: kernel template K's instance for (g.KS, m); the dense route has TRAIN, INFER and EPI instances alone (codes
+// out and the view are refused before any launch, module_forward_impl)
+#define CIMQ_DENSE_FWD(NAME, K)                                                                                 \
+  auto NAME = g.KS == 1 ? (m == FwdMode::INFER ? K<NBW, NBA, 1, FwdMode::INFER> : K<NBW, NBA, 1, FwdMode::TRAIN>)  \
+                        : (m == FwdMode::INFER ? K<NBW, NBA, 2, FwdMode::INFER> : K<NBW, NBA, 2, FwdMode::TRAIN>); \
+  if (has_epi(m)) NAME = g.KS == 1 ? K<NBW, NBA, 1, FwdMode::EPI> : K<NBW, NBA, 2, FwdMode::EPI>;
+
 template <int NBW, int NBA>
 int launch_dense_fwd_n(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, hipStream_t s,
                        const Epi* ep) {
   CtxLayout L = ctx_layout(g);
-  // forward only (CIMQ_OPT_INFERENCE): the instances that write no state planes (KSA = 4 + KS), or those with
-  // the output epilogue as well (KSA = 12 + KS)
-  const bool inf = g.inference != 0;
-  if (ep && (!inf || g.P != 1)) return fail(CIMQ_EINVAL, "internal: output epilogue off the forward-only dense path");
+  const FwdMode m = fwd_mode_of(g, ep);
+  if (has_epi(m) && (!g.inference || g.P != 1))
+    return fail(CIMQ_EINVAL, "internal: output epilogue off the forward-only dense path");
   const Epi e = ep ? *ep : Epi{};
-  auto klit = g.KS == 1 ? (inf ? dense_fwd_lit_kernel<NBW, NBA, 5> : dense_fwd_lit_kernel<NBW, NBA, 1>)
-                        : (inf ? dense_fwd_lit_kernel<NBW, NBA, 6> : dense_fwd_lit_kernel<NBW, NBA, 2>);
-  if (ep) klit = g.KS == 1 ? dense_fwd_lit_kernel<NBW, NBA, 13> : dense_fwd_lit_kernel<NBW, NBA, 14>;
+  CIMQ_DENSE_FWD(klit, dense_fwd_lit_kernel)
   const uint8_t* wr = wreg(g, ctx);
   uint2* st = reinterpret_cast<uint2*>(ctx + L.st);
   const int slot = prof_begin(KID_FWD, g, s);
   if (tune("DENSE_FWD8", 1)) {  // 128-row blocks, weight side staged once per block (dense_plan: M % 128 == 0)
-    auto kern = g.KS == 1 ? (inf ? dense_fwd8_kernel<NBW, NBA, 5> : dense_fwd8_kernel<NBW, NBA, 1>)
-                          : (inf ? dense_fwd8_kernel<NBW, NBA, 6> : dense_fwd8_kernel<NBW, NBA, 2>);
-    if (ep) kern = g.KS == 1 ? dense_fwd8_kernel<NBW, NBA, 13> : dense_fwd8_kernel<NBW, NBA, 14>;
+    CIMQ_DENSE_FWD(kern, dense_fwd8_kernel)
     hipLaunchKernelGGL(kern, dim3(g.M / 128, g.O / 64), dim3(512), 0, s, g, ctx + L.xcode,
                        reinterpret_cast<const v4i*>(wr + L.wfrag), params_of(g, ctx), out, st, e);
   } else {
-    auto kern = g.KS == 1 ? (inf ? dense_fwd_kernel<NBW, NBA, 5> : dense_fwd_kernel<NBW, NBA, 1>)
-                          : (inf ? dense_fwd_kernel<NBW, NBA, 6> : dense_fwd_kernel<NBW, NBA, 2>);
-    if (ep) kern = g.KS == 1 ? dense_fwd_kernel<NBW, NBA, 13> : dense_fwd_kernel<NBW, NBA, 14>;
+    CIMQ_DENSE_FWD(kern, dense_fwd_kernel)
     hipLaunchKernelGGL(kern, dim3(g.M / 64, g.O / 64), dim3(256), 0, s, g, ctx + L.xcode,
                        reinterpret_cast<const v4i*>(wr + L.wfrag), params_of(g, ctx), sw, sa, out, st, e);
   }
@@ -746,6 +739,7 @@ int launch_dense_fwd_n(const Geo& g, uint8_t* ctx, const float* sw, const float*
                      params_of(g, ctx), sw, sa, out, st, e);
   return check_hip("dense_fwd");
 }
+#undef CIMQ_DENSE_FWD
 
 template <int NBW, int NBA>
 int launch_dense_bwd_n(const Geo& g, const uint8_t* ctx, const float* sw, const float* gout, float* gx, uint8_t* ws,

@@ -6,57 +6,63 @@
 
 namespace cimq {
 
+using Fwd3Kern = void (*)(Geo, V3, const uint8_t*, const v4i*, Params, const float*, const float*, float*, uint8_t*,
+                          const float*, const float*, uint8_t*, Epi);
+
+// the OBM 1 / 2 / 4 instances of one (format, state, mode), up to the widest one built
+template <int NBP, int KS, int CST, FwdState ST, FwdMode M, int OBMAX>
+Fwd3Kern fwd3_obm(int obm) {
+  if constexpr (OBMAX == 1) return cim_fwd_v3_kernel<NBP, KS, CST, ST, M, 1>;
+  else if constexpr (OBMAX == 2) return obm == 1 ? cim_fwd_v3_kernel<NBP, KS, CST, ST, M, 1> : cim_fwd_v3_kernel<NBP, KS, CST, ST, M, 2>;
+  else return obm == 1 ? cim_fwd_v3_kernel<NBP, KS, CST, ST, M, 1> : obm == 2 ? cim_fwd_v3_kernel<NBP, KS, CST, ST, M, 2>
+                                                                            : cim_fwd_v3_kernel<NBP, KS, CST, ST, M, 4>;
+}
+
+// cim_fwd_v3_kernel's instance of one mode for (format, state, OBM).  The compact formats' state in a mode is S: the
+// epilogue and later modes are forward only.  The first conv's training instance writes no state either, so every
+// forward-only call without an epilogue runs it as it is (named here, where the code object has always had it;
+// CST 0's, for the same reason, in launch_fwd_v3).  w2a2 with an epilogue: two blocks at the most (launch_fwd_v3)
+template <int NBP, int KS, FwdMode M>
+Fwd3Kern fwd3_kernel(int cst, FwdState st, int obm) {
+  constexpr FwdState S = M == FwdMode::TRAIN ? FwdState::WRITE : FwdState::NONE;
+  if constexpr (M != FwdMode::INFER)
+    if (cst == 0) return fwd3_obm<NBP, KS, 0, FwdState::WRITE, M, 4>(obm);
+  if constexpr (NBP == 8)  // v7_plan: w8a8 with one 16-channel block
+    return st == FwdState::RECOMPUTE ? fwd3_obm<8, KS, 8, FwdState::RECOMPUTE, M == FwdMode::INFER ? FwdMode::TRAIN : M, 1>(obm)
+                                     : fwd3_obm<8, KS, 8, S, M, 1>(obm);
+  else
+    return cst == 2 ? fwd3_obm<NBP, KS, 2, S, M, has_epi(M) ? 2 : 4>(obm) : fwd3_obm<NBP, KS, 3, S, M, 4>(obm);
+}
+
 template <int NBP, int KS>
 int launch_fwd_v3(const Geo& g, const Plan3& p, uint8_t* ctx, const float* sw, const float* sa, float* out,
                   hipStream_t s, const ActQ* aq, const Epi* ep = nullptr) {
   CtxLayout L = ctx_layout(g);
   // CST, fixed at compile time: 0 per-k state words (the general backward's), else the compact ones the v7-plan
-  // backwards read -- nbw = nba = CST (2, 3), 8 the w8a8 planes, 9 the first conv, whose backward recomputes
-  // them; forward only (CIMQ_OPT_INFERENCE): the same instances without the state words, their bits and the
-  // backward words (10 + CST; 0 and 9 write no state as they are); with an output epilogue (ep, forward only, NCHW)
-  // 20 + that; with activation codes in or out as well, 40 + that
+  // backwards read -- nbw = nba = CST (2, 3), 8 the w8a8 planes.  The first conv's backward recomputes them; a
+  // forward-only call (CIMQ_OPT_INFERENCE) runs the same instances without the state words, their bits and the
+  // backward words (CST 0 and the first conv's write no state as they are)
   const int cst = route_of(g).cst;
+  const FwdState st = route_of(g).fst;
+  FwdMode m = fwd_mode_of(g, ep);
+  if (has_epi(m) && (!g.inference || !g.onchw))
+    return fail(CIMQ_EINVAL, "internal: output epilogue off the forward-only module path");
+  if (m == FwdMode::INFER && cst == 0) m = FwdMode::TRAIN;
   // OBM: 16-channel output blocks per block (register arrays sized for exactly that)
   int obm = std::min(p.v.obm, g.OB16 <= 2 ? g.OB16 : 4);
   // (the w2a2 four-block instances sit at a VGPR step -- 127 and 160 -- and the epilogue's residual float4 would
   // cost them a wave per SIMD: with an epilogue those layers run the two-block instances, twice the blocks in y;
   // the plan's LDS figures, made for four blocks, cover two)
-  if (ep && route_of(g).cst == 12 && obm == 4) obm = 2;
-  void (*kern)(Geo, V3, const uint8_t*, const v4i*, Params, const float*, const float*, float*, uint8_t*,
-               const float*, const float*, uint8_t*, Epi);
-#define CIMQ_FWD3(CST) (obm == 1 ? cim_fwd_v3_kernel<NBP, KS, CST, 1> : obm == 2 ? cim_fwd_v3_kernel<NBP, KS, CST, 2> \
-                                                                     : cim_fwd_v3_kernel<NBP, KS, CST, 4>)
-  // (the instances in the order the code object has always had them: a kernel's place decides its addresses)
-  if (ep) {
-    if (!g.inference || !g.onchw) return fail(CIMQ_EINVAL, "internal: output epilogue off the forward-only module path");
-    if (ep->xq || ep->oq) {  // activation codes in or out (cimq_module_forward_codes): the code instances, 40 + that
-      if (cst == 0) kern = CIMQ_FWD3(40);
-      else if constexpr (NBP == 8) kern = cst == 9 ? cim_fwd_v3_kernel<8, KS, 49, 1> : cim_fwd_v3_kernel<8, KS, 58, 1>;
-      else if (cst == 12) kern = obm == 1 ? cim_fwd_v3_kernel<NBP, KS, 52, 1> : cim_fwd_v3_kernel<NBP, KS, 52, 2>;
-      else kern = CIMQ_FWD3(53);
-    } else if (cst == 0) kern = CIMQ_FWD3(20);
-    else if constexpr (NBP == 8) kern = cst == 9 ? cim_fwd_v3_kernel<8, KS, 29, 1> : cim_fwd_v3_kernel<8, KS, 38, 1>;
-    else if (cst == 12) kern = obm == 1 ? cim_fwd_v3_kernel<NBP, KS, 32, 1> : cim_fwd_v3_kernel<NBP, KS, 32, 2>;
-    else kern = CIMQ_FWD3(33);
-  } else if (cst != 0 && g.inference) {
-    if constexpr (NBP == 8) kern = cst == 9 ? cim_fwd_v3_kernel<8, KS, 9, 1> : cim_fwd_v3_kernel<8, KS, 18, 1>;
-    else kern = cst == 12 ? CIMQ_FWD3(12) : CIMQ_FWD3(13);
-  } else if (cst == 0) {
-    kern = CIMQ_FWD3(0);
-  } else if constexpr (NBP == 8) {  // v7_plan: w8a8 with one 16-channel block
-    kern = cst == 9 ? cim_fwd_v3_kernel<8, KS, 9, 1> : cim_fwd_v3_kernel<8, KS, 8, 1>;
-  } else {
-    kern = cst == 2 ? CIMQ_FWD3(2) : CIMQ_FWD3(3);
+  if (has_epi(m) && cst == 2 && st == FwdState::NONE && obm == 4) obm = 2;
+  // (the modes in the order the code object has always had its instances: a kernel's place decides its addresses)
+  Fwd3Kern kern = nullptr;
+  switch (m) {
+    case FwdMode::CODES: kern = fwd3_kernel<NBP, KS, FwdMode::CODES>(cst, st, obm); break;
+    case FwdMode::EPI: kern = fwd3_kernel<NBP, KS, FwdMode::EPI>(cst, st, obm); break;
+    case FwdMode::INFER: kern = fwd3_kernel<NBP, KS, FwdMode::INFER>(cst, st, obm); break;
+    case FwdMode::TRAIN: kern = fwd3_kernel<NBP, KS, FwdMode::TRAIN>(cst, st, obm); break;
+    case FwdMode::VIEW: kern = fwd3_kernel<NBP, KS, FwdMode::VIEW>(cst, st, obm); break;
   }
-  // the residual as a view (cimq_net_forward), with or without codes: the view instances, 60 + that (last, so that
-  // the others keep their order)
-  if (ep && ep->rvw1) {
-    if (cst == 0) kern = CIMQ_FWD3(60);
-    else if constexpr (NBP == 8) kern = cst == 9 ? cim_fwd_v3_kernel<8, KS, 69, 1> : cim_fwd_v3_kernel<8, KS, 78, 1>;
-    else if (cst == 12) kern = obm == 1 ? cim_fwd_v3_kernel<NBP, KS, 72, 1> : cim_fwd_v3_kernel<NBP, KS, 72, 2>;
-    else kern = CIMQ_FWD3(73);
-  }
-#undef CIMQ_FWD3
   // the fused activation quantiser's word table (after the kernel's other LDS)
   const size_t lds = p.lds_fwd + (aq ? (size_t)kActLutMax * 2 * 4 : 0);
   CIMQ_TRY(set_lds(kern, lds));

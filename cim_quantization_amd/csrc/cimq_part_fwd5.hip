@@ -14,13 +14,14 @@ int launch_fwd5(const Geo& g, const Plan5& p, uint8_t* ctx, const float* sw, con
   // not in a forward-only call, CIMQ_OPT_INFERENCE)
   const bool wst = r.state != ST_NONE;
   if (ep && wst) return fail(CIMQ_EINVAL, "internal: output epilogue on a forward that writes state");
-  auto kern = p.nob == 2 ? (wst ? cim_fwd5_kernel<2, true> : cim_fwd5_kernel<2, false>)
-                         : (wst ? cim_fwd5_kernel<1, true> : cim_fwd5_kernel<1, false>);
-  if (ep) kern = p.nob == 2 ? cim_fwd5_kernel<2, false, true> : cim_fwd5_kernel<1, false, true>;
-  // activation codes in or out (cimq_module_forward_codes): the code instances, NOBA = 4 + NOB
-  if (ep && (ep->xq || ep->oq)) kern = p.nob == 2 ? cim_fwd5_kernel<6, false, true> : cim_fwd5_kernel<5, false, true>;
-  // the residual as a view (cimq_net_forward), with or without codes: the view instances, NOBA = 8 + NOB
-  if (ep && ep->rvw1) kern = p.nob == 2 ? cim_fwd5_kernel<10, false, true> : cim_fwd5_kernel<9, false, true>;
+  const bool two = p.nob == 2;
+  const FwdMode m = fwd_mode_of(g, ep);
+  // (forward only without an epilogue runs the recompute training instance: it writes only out)
+  auto kern = two ? (wst ? cim_fwd5_kernel<2, true, FwdMode::TRAIN> : cim_fwd5_kernel<2, false, FwdMode::TRAIN>)
+                  : (wst ? cim_fwd5_kernel<1, true, FwdMode::TRAIN> : cim_fwd5_kernel<1, false, FwdMode::TRAIN>);
+  if (m == FwdMode::EPI) kern = two ? cim_fwd5_kernel<2, false, FwdMode::EPI> : cim_fwd5_kernel<1, false, FwdMode::EPI>;
+  if (m == FwdMode::CODES) kern = two ? cim_fwd5_kernel<2, false, FwdMode::CODES> : cim_fwd5_kernel<1, false, FwdMode::CODES>;
+  if (m == FwdMode::VIEW) kern = two ? cim_fwd5_kernel<2, false, FwdMode::VIEW> : cim_fwd5_kernel<1, false, FwdMode::VIEW>;
   CIMQ_TRY(set_lds(kern, p.lds));
   // 4 waves per SIMD: two 512-thread blocks per CU (one output block each) or one 1024-thread block (two),
   // a grid-stride walk over the 128-pixel m-tiles; the output-block groups in y

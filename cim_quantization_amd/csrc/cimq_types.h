@@ -91,6 +91,24 @@ inline void set_res_view(Epi* ep, int c0, int cr, int s, int h, int w) {
   ep->rvw1 = (uint32_t)h | (uint32_t)w << 15 | (uint32_t)(s - 1) << 30;
 }
 
+// What a forward kernel instance does with its output: a template argument of cim_fwd_v3_kernel, cim_fwd5_kernel and
+// dense_fwd*_kernel.  Each mode includes the one before it; fwd_mode_of (cimq_host.h) names a call's mode.
+enum class FwdMode : int {
+  TRAIN,  // out, and what the backward reads: the state words, the backward ctx words
+  INFER,  // forward only (CIMQ_OPT_INFERENCE): out alone -- no state words, none of their bits, no backward words
+  EPI,    // ... with the output epilogue (Epi) on the values about to be stored; no earlier mode reads the Epi
+  CODES,  // ... with activation codes in (Epi::xq), out (Epi::oq) or both: block-uniform branches on the Epi
+  VIEW,   // ... with the residual read as a view (Epi::rvw0 / rvw1, cimq_net_forward's option-A shortcut)
+};
+constexpr bool has_epi(FwdMode m) { return m >= FwdMode::EPI; }
+constexpr bool has_codes(FwdMode m) { return m >= FwdMode::CODES; }
+constexpr bool has_view(FwdMode m) { return m >= FwdMode::VIEW; }
+constexpr bool writes_state(FwdMode m) { return m == FwdMode::TRAIN; }
+// What cim_fwd_v3_kernel does with the state words of a compact format (CST 2 / 3 / 8): it writes them (also the
+// one form of CST 0, which writes none in any call); none, because cim_bwd_c1_kernel recomputes them (a training
+// instance that a forward-only call runs as it is); forward only: no state bits on either ADC path, no words via xcb
+enum class FwdState : int { WRITE, RECOMPUTE, NONE };
+
 __host__ __device__ inline int pidx(const Geo& g, int i, int j, int k, int o) {
   return ((i * g.nba + j) * g.nbw + k) * g.Opad + o;
 }

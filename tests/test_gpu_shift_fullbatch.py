@@ -8,8 +8,8 @@ module, lsq.py:511-588), and the layers outside the shift fast path.
   whole batch (the batch-summed gradients included), elementwise, plus run-to-run bit identity.
 * ResNet-56's first conv, forced to w8a8 by ReplaceModuleTool (utils/wrapper/replace_module.py:83-95):
   3 -> 16 @ 32, signed input, xbar 64 (K = 27, T = 1, 64 slice pairs, the int8-wrapped binary_mask),
-  at B = 2 and B = 256.  Since round 4 it runs the shift fast path's w8a8 form (cim_fwd_v3_kernel<8,1,8,1>
-  with plane state, the v7 backward pair and shift_stats8_kernel; test_abi_host.py asserts the routing);
+  at B = 2 and B = 256.  Since round 4 it runs the shift fast path's w8a8 form
+  (cim_fwd_v3_kernel<8,1,8,WRITE,TRAIN,1> with plane state, the v7 backward pair and shift_stats8_kernel; test_abi_host.py asserts the routing);
   a w8a8 shape that fast path refuses (C = 8, K = 72) keeps the general recompute kernels under test.
   Deterministic (fixed-order reductions, no atomics).
 * alpha only (adc_shift=False) at B = 256: the 32x32 stage, a stride-2 transition and the 8x8 stage.
