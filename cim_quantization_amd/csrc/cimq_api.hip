@@ -88,6 +88,7 @@ int dispatch_bwd_any(const Geo& g, const uint8_t* ctx, const float* sw, const fl
     case CIMQ_ROUTE_V7:
       if (g.NBP == 8) return launch_v7_n<8, 8>(g, v7_plan(g), ctx, sw, sa, gout, x, gx, ws, s, parts);
       if (g.nbw == 2) return launch_v7_n<2, 2>(g, v7_plan(g), ctx, sw, sa, gout, x, gx, ws, s, parts);
+      if (g.nbw == 4) return launch_v7_n<4, 4>(g, v7_plan(g), ctx, sw, sa, gout, x, gx, ws, s, parts);
       return launch_v7_n<3, 3>(g, v7_plan(g), ctx, sw, sa, gout, x, gx, ws, s, parts);
     case CIMQ_ROUTE_DENSE: return launch_dense_bwd(g, ctx, sw, gout, gx, ws, s, r.lsq_fused ? x : nullptr, sa);
     case CIMQ_ROUTE_GENERAL: return launch_bwd_general(g, ctx, sw, sa, signed_act, gout, x, gx, ws, s);
@@ -263,13 +264,15 @@ int cimq_debug_state_codes(const cimq_conv_desc* d, const void* ctx, int8_t* cod
   CIMQ_TRY(make_geo(d, &g));
   if (!ctx || !code_out || !pass_out) return fail(CIMQ_EINVAL, "null pointer argument");
   const StateFmt fmt = route_of(g).state;
-  if (fmt != ST_V7 && fmt != ST_PLANES)
-    return fail(CIMQ_EUNSUPPORTED, "this layer's forward writes no v7 state words (the first conv's backward recomputes them)");
+  if (fmt != ST_V7 && fmt != ST_V7X2 && fmt != ST_PLANES)
+    return fail(CIMQ_EUNSUPPORTED,
+                "this layer's forward writes no v7 state words: the hook decodes the 4-byte words of w2a2 / w3a3, "
+                "the 8-byte words of w4a4 and the w8a8 planes (the first conv's backward recomputes them)");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const uint8_t* c = reinterpret_cast<const uint8_t*>(ctx);
   const long long n = (long long)g.T * g.M * g.O;
   hipLaunchKernelGGL(decode_state_kernel, dim3(std::min(cdiv(n, 256), 8192)), dim3(256), 0, s, g,
-                     fmt == ST_PLANES ? 1 : 0, c + ctx_layout(g).st, code_out, pass_out);
+                     fmt == ST_PLANES ? 1 : fmt == ST_V7X2 ? 2 : 0, c + ctx_layout(g).st, code_out, pass_out);
   return check_hip("decode_state");
 }
 

@@ -22,6 +22,18 @@ __host__ __device__ constexpr uint32_t pass_mask_j(int j, int nbw, int nba) {
   return m;
 }
 
+// The state words a v7 slice-pair shape reads (host: StateFmt, v7_plan), named per shape -- the pair count alone
+// does not tell the 16 pairs of w4a4 from plane words:
+//   V7W_32      one uint32, bits 3*kj + {0 pass, 1 code != 0, 2 code < 0}, kj = k*nba + j            (w2a2, w3a3)
+//   V7W_32X2    a uint2 of two such words: .x weight slices 0-1 (kj 0..7), .y slices 2-3 (kj - 8)   (w4a4)
+//   V7W_PLANES  three 64-bit planes, bit kj each                                                     (w8a8)
+enum V7Words { V7W_32, V7W_32X2, V7W_PLANES };
+template <int NBW, int NBA> struct V7WordsOf;
+template <> struct V7WordsOf<2, 2> { static constexpr V7Words fmt = V7W_32; };
+template <> struct V7WordsOf<3, 3> { static constexpr V7Words fmt = V7W_32; };
+template <> struct V7WordsOf<4, 4> { static constexpr V7Words fmt = V7W_32X2; };
+template <> struct V7WordsOf<8, 8> { static constexpr V7Words fmt = V7W_PLANES; };
+
 // uniform (scalar-register) copies of values every lane computed identically
 __device__ inline float sgpr_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 __device__ inline uint64_t sgpr_u64(uint64_t v) {

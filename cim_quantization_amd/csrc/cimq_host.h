@@ -349,13 +349,23 @@ inline void gw_pitches(const Geo& g, V7& v) {
   plane_pitches(key, v.NSLOT * g.Wo + 8, v.CPL, tune("GW_PAD", 1) != 0, cycles, &v.CPITCH, &v.KWP);
 }
 
+// w4a4 in 1-bit slices trains on the v7 pair from 8-byte state words (ST_V7X2): the library ADC's training calls
+// only.  A forward-only call keeps the per-k family -- its route, its kernel instances and its sizes are what they
+// were before the format existed -- and so does every other ADC variant (their backward is the general one, which
+// reads no state words) and every four-slice layer of wider slices ("8/8 in 2/2")
+inline bool v7_w44(const Geo& g) {
+  return g.NBP == 4 && g.nbw == 4 && g.nba == 4 && g.bsw == 1 && g.bsa == 1 && g.variant == VAR_LIBRARY &&
+         !g.inference;
+}
+
 inline Plan7 v7_plan_compute(const Geo& g) {
   Plan7 p;
   memset(&p, 0, sizeof(p));
   const Plan3 p3 = v3_plan(g);
   if (!p3.ok) return p;
-  // instantiated slice pairs: w3a3 / w2a2 (interleaved state words) and w8a8 (plane state words)
-  if (g.NBP == 4 && !((g.nbw == 3 && g.nba == 3) || (g.nbw == 2 && g.nba == 2))) return p;
+  // instantiated slice pairs: w3a3 / w2a2 (interleaved state words), w4a4 in 1-bit slices (two interleaved
+  // half words, v7_w44) and w8a8 (plane state words)
+  if (g.NBP == 4 && !((g.nbw == 3 && g.nba == 3) || (g.nbw == 2 && g.nba == 2) || v7_w44(g))) return p;
   // w8a8: one 16-channel output block (the first conv of the CIFAR ResNets; wider blocks spill)
   // plane words: the w8a8 first layer only (grad_w: at most two 16-row groups, C*KHW <= 32)
   if (g.NBP == 8 && !(g.nbw == 8 && g.nba == 8 && g.OB16 == 1 && g.C * g.KHW <= 32)) return p;
@@ -619,9 +629,10 @@ inline bool v7_bwd(const Geo& g) {
 // the LSQ activation quantiser can run in the forward's row staging: the v3 fast path with v7 state words (so
 // no later kernel reads the forward slice words), 4-byte slice words, the prologue's word table applicable, and
 // not the first conv (whose backward re-reads the forward words) or a shift layer in training (its statistics
-// kernel does; a forward-only shift layer of the fused shift path has no such reader)
+// kernel does; a forward-only shift layer of the fused shift path has no such reader).  A w4a4 training forward
+// (v7_w44) keeps the prologue's pass: its no-grad twin runs the per-k family, which has no staged quantiser
 inline bool fwd_actq_ok(const Geo& g) {
-  if (tune("ACTQ", 1) == 0) return false;
+  if (tune("ACTQ", 1) == 0 || v7_w44(g)) return false;
   const bool adc_ok = g.variant == VAR_LIBRARY || (g.inference && g.variant == VAR_SHIFT_ROUND && shift_stats_ok(g));
   return g.input_kind == CIMQ_INPUT_RAW_LSQ && g.NBP == 4 && adc_ok && g.W % 4 == 0 &&
          g.P % 64 == 0 && g.lsq_qp >= 0.f && g.lsq_qp < 255.f && v3_plan(g).ok && v7_bwd(g) && !c1_plan(g).ok;
@@ -854,6 +865,7 @@ enum StateFmt {
   ST_NONE,    // none: the backward recomputes the partial sums (cim_bwd_r6_kernel), or a forward-only call
   ST_PERK,    // a word per (tile, weight slice, pixel, channel): the general kernels, cim_fwd_v3_kernel<CST 0>
   ST_V7,      // v7 compact words, 4 B per (tile, pixel, channel): w2a2 / w3a3
+  ST_V7X2,    // two such words, 8 B per (tile, pixel, channel): w4a4 in 1-bit slices (weight slices 0-1, 2-3)
   ST_PLANES,  // three 64-bit planes per (tile, pixel, channel): w8a8
   ST_C1,      // w8a8 first conv: its backward (cim_bwd_c1_kernel) recomputes them from the slice words
   ST_DENSE,   // a uint2 of three 16-bit planes per (tile, row, channel): the dense path
@@ -863,7 +875,7 @@ struct Route {
   int fwd, gx, gw;   // CIMQ_ROUTE_*; gx = gw = CIMQ_ROUTE_NONE in a forward-only call (CIMQ_OPT_INFERENCE)
   bool actq;         // the forward quantises the activation in its own row staging: no prologue pass over x
   StateFmt state;
-  int cst;           // cim_fwd_v3_kernel's CST for the forward family's format (0 / 2 / 3 / 8), in any call
+  int cst;           // cim_fwd_v3_kernel's CST for the forward family's format (0 / 2 / 3 / 4 / 8), in any call
   FwdState fst;      // ... and what it does with that format's words: RECOMPUTE is ST_C1's, in any call
   size_t st_bytes;   // the ctx's state-word region
   bool codes;        // the ctx holds one activation-code byte per element, not the 4-byte backward word
@@ -930,12 +942,13 @@ inline Route route_compute(const Geo& g) {
                      : !v7_plan(g).ok        ? ST_PERK
                      : r.gx == CIMQ_ROUTE_C1 ? ST_C1
                      : g.NBP == 8            ? ST_PLANES
+                     : g.nbw == 4            ? ST_V7X2
                                              : ST_V7;
   r.state = r.gx == CIMQ_ROUTE_R6 ? ST_NONE : fam;
-  r.cst = fam == ST_V7 ? g.nbw : (fam == ST_PLANES || fam == ST_C1) ? 8 : 0;
+  r.cst = (fam == ST_V7 || fam == ST_V7X2) ? g.nbw : (fam == ST_PLANES || fam == ST_C1) ? 8 : 0;
   r.fst = fam == ST_C1 ? FwdState::RECOMPUTE : FwdState::WRITE;
-  // (the region holds any format of the shape: the v7 words are never larger than the per-k ones for nbw >= 2,
-  // the max covers nbw == 1)
+  // (the region holds any format of the shape: the v7 words are never larger than the per-k ones for nbw >= 2 --
+  // the 8-byte ST_V7X2 words of four slices are exactly their size -- the max covers nbw == 1)
   r.st_bytes = r.state == ST_NONE ? (size_t)0
                                   : std::max({(size_t)g.T * g.nbw * g.M * g.O * (g.NBP == 4 ? 2 : 4),
                                               (size_t)g.T * g.M * g.O * (g.NBP == 4 ? 4 : 24),
@@ -1099,7 +1112,10 @@ inline WsLayout ws_layout_compute(const Geo& g) {
   W.wpart = o; o = align256(o + sizeof(float) * 2 * (size_t)cdiv((long long)g.T * g.FBT * 16 * g.Opad, 64));
   W.bpo = o; o = align256(o + sizeof(float) * (size_t)g.M * g.O);
   // the general backward's unfolded grad_x [M][K] (folded by fold_gx_kernel)
-  W.gxu = o; o = align256(o + (r.gx != CIMQ_ROUTE_GENERAL ? 0 : sizeof(float) * (size_t)g.M * g.K));
+  // (a w4a4 layer on the v7 pair keeps the region, unused: cimq_query_sizes answered one size for the forward and
+  // the backward workspace of such a descriptor before the v7 pair took it, and callers that sized their buffers
+  // from that answer -- the forward's among them -- find it unchanged)
+  W.gxu = o; o = align256(o + ((r.gx != CIMQ_ROUTE_GENERAL && !(r.gx == CIMQ_ROUTE_V7 && v7_w44(g))) ? 0 : sizeof(float) * (size_t)g.M * g.K));
   W.total = o;
   return W;
 }
@@ -1284,6 +1300,7 @@ int launch_r6(const Geo& g, const PlanR6& p, const uint8_t* ctx, const float* sw
               const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, uint32_t* st_dbg = nullptr);
 extern template CIMQ_V7_SIG(2, 2);
 extern template CIMQ_V7_SIG(3, 3);
+extern template CIMQ_V7_SIG(4, 4);  // cimq_part_v7_44.hip
 extern template CIMQ_V7_SIG(8, 8);
 
 }  // namespace cimq

@@ -28,6 +28,10 @@ namespace cimq {
 // st32[(i*M + m)*O + o], bits 3*(k*nba + j) + {0: STE pass, 1: code != 0, 2: code < 0}; 0: the per-k words.
 // CST > 0 also fixes nbw = nba = CST at compile time: the ternary-threshold path then runs
 // fully unrolled (every slice pair's MFMAs issued before its ADC work, state bits shifted in).
+// CST 4 (w4a4 in 1-bit slices, training only): 16 pairs in a uint2 per (i, m, o) at st64[(i*M + m)*O + o] -- .x the
+// pairs of weight slices 0-1 as above (kj 0..7), .y those of slices 2-3 at 3*(kj - 8).  Its unrolled path adds the
+// pairs to the output in CST 0's order (k, then j, ascending): the forward-only calls of such a layer run CST 0,
+// and the two forwards agree bit for bit.
 // ST: what becomes of those words (FwdState).  M: what the store does (FwdMode) -- the epilogue ep on the float4
 // about to be stored (NCHW only); with codes, the row staging reads the input's codes (ep.xq: bytes straight into
 // the word table, stage_rows_qc) or quantises fp32 x as before, and the store writes the float4, the consumer's
@@ -45,7 +49,9 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
   constexpr bool VIEW = has_view(M), COD = has_codes(M), EPI = has_epi(M);
   constexpr bool WST = ST == FwdState::WRITE;
   constexpr bool INF = ST == FwdState::NONE;
-  static_assert(CST == 0 || CST == 2 || CST == 3 || CST == 8, "state formats: per-k words, w2a2, w3a3, w8a8 planes");
+  static_assert(CST == 0 || CST == 2 || CST == 3 || CST == 4 || CST == 8,
+                "state formats: per-k words, w2a2, w3a3, w4a4 word pairs, w8a8 planes");
+  static_assert(CST != 4 || (NBP == 4 && WST && M == FwdMode::TRAIN), "w4a4 word pairs: the training forward only");
   static_assert(CST != 0 || WST, "CST 0 writes no state words as it is: one form, spelled WRITE, for every call");
   static_assert(ST != FwdState::RECOMPUTE || CST == 8, "the recomputing backward is the w8a8 first conv's");
   static_assert(M != FwdMode::TRAIN || !INF, "a training instance leaves the backward its words, or recomputes them");
@@ -256,6 +262,13 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
       for (int a = 0; a < OBM; ++a)
 #pragma unroll
         for (int c = 0; c < 4; ++c) stc[a][c] = 0u;
+      uint32_t stc2[CST == 4 ? OBM : 1][4];  // (CST 4: the word of weight slices 2-3)
+      if constexpr (CST == 4) {
+#pragma unroll
+        for (int a = 0; a < OBM; ++a)
+#pragma unroll
+          for (int c = 0; c < 4; ++c) stc2[a][c] = 0u;
+      }
       // plane state words (more than 10 slice pairs, NBP 8): per (i, m, o) three 64-bit planes
       // -- STE pass, code != 0, code < 0 -- bit k*nba + j each (cimq_v7.hip)
       constexpr bool PLF = (NBP == 8) && CST;
@@ -264,7 +277,59 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
       for (int a = 0; a < OBM; ++a)
 #pragma unroll
         for (int c = 0; c < 4; ++c) pl[a][c][0] = pl[a][c][1] = pl[a][c][2] = 0ull;
-      if (CST > 0 && !literal && std8) {
+      if constexpr (CST == 4) {
+        // fast path of the 16 pairs, in CST 0's order of additions: k ascending, per output block the four
+        // pairs' MFMAs, then j ascending.  Each word takes its 8 pairs' bits from the bottom -- pass, code != 0,
+        // code < 0 -- which leaves pair kj's at 23 - 3*(kj & 7) - {0, 1, 2}: a bit reversal and a shift by 8 put
+        // them at 3*(kj & 7) + {0, 1, 2}, where cimq_v7.hip reads them.
+        if (!literal) {
+          uint32_t sh[OBM][4][2];
+#pragma unroll
+          for (int a = 0; a < OBM; ++a)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) sh[a][c][0] = sh[a][c][1] = 0u;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+#pragma unroll
+            for (int ob = 0; ob < OBM; ++ob) {
+              if (ob < nob) {
+                v4i wk[KS];
+#pragma unroll
+                for (int ks = 0; ks < KS; ++ks) wk[ks] = wt[((k * NOB + ob) * KS + ks) * 64 + lane];
+                v4i ps[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                  ps[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xs[j][0], wk[0], v4i{0, 0, 0, 0}, 0, 0, 0);
+#pragma unroll
+                  for (int ks = 1; ks < KS; ++ks) ps[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xs[j][ks], wk[ks], ps[j], 0, 0, 0);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                  const int pcol = (j * 4 + k) * NOB * 16 + ob * 16 + r16;
+                  const int4 pv = pt[pcol];
+                  const float cf = ct[pcol];
+#pragma unroll
+                  for (int r = 0; r < 4; ++r) {
+                    const uint64_t mhi = __builtin_amdgcn_ballot_w64(ps[j][r] >= pv.x);
+                    const uint64_t mlo = __builtin_amdgcn_ballot_w64(ps[j][r] <= pv.y);
+                    acc[ob][r] += adc3(cf, mhi, mlo);
+                    const uint64_t mps = __builtin_amdgcn_ballot_w64((unsigned)(ps[j][r] - pv.z) <= (unsigned)pv.w);
+                    const uint64_t mnz = mhi | mlo;
+                    sh[ob][r][k >> 1] = shin(shin(shin(sh[ob][r][k >> 1], mps), mnz), mlo);
+                  }
+                }
+              }
+            }
+          }
+#pragma unroll
+          for (int a = 0; a < OBM; ++a)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+              stc[a][c] = __builtin_bitreverse32(sh[a][c][0]) >> 8;
+              stc2[CST == 4 ? a : 0][c] = __builtin_bitreverse32(sh[a][c][1]) >> 8;
+            }
+        }
+      } else if (CST > 0 && !literal && std8) {
         // fast path: slice pairs kj = k*CST + j in descending order, so that shifting each
         // state bit in from the bottom leaves bit 3*kj + {0,1,2} (interleaved words) or bit
         // kj of each 64-bit plane (PLF) where cimq_v7.hip reads it.  w8a8 (CST 8) runs it only
@@ -437,6 +502,12 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
               for (int r = 0; r < 4; ++r)
 #pragma unroll
                 for (int q = 0; q < 3; ++q) pl[ob][r][q] |= (uint64_t)tq[r][q] << (g.nba * k);
+            } else if constexpr (CST == 4) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                if (k < 2) stc[ob][r] |= stw[r] << (12 * k);
+                else stc2[CST == 4 ? ob : 0][r] |= stw[r] << (12 * (k - 2));
+              }
             } else if (CST) {
 #pragma unroll
               for (int r = 0; r < 4; ++r) stc[ob][r] |= stw[r] << (3 * g.nba * k);
@@ -450,7 +521,11 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
           const int o = (og * OBM + ob) * 16 + r16;
           if (ob < nob && o < g.O) {
             const size_t e0 = ((size_t)i * g.M + (size_t)mt * 64 + wave * 16 + 4 * g4) * g.O + o;
-            if (PLF) {
+            if constexpr (CST == 4) {
+              uint2* s64 = reinterpret_cast<uint2*>(st) + e0;
+#pragma unroll
+              for (int r = 0; r < 4; ++r) s64[(size_t)r * g.O] = make_uint2(stc[ob][r], stc2[CST == 4 ? ob : 0][r]);
+            } else if (PLF) {
               uint2* s64 = reinterpret_cast<uint2*>(st);
 #pragma unroll
               for (int r = 0; r < 4; ++r)

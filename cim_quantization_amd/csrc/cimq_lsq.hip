@@ -348,7 +348,8 @@ __global__ __launch_bounds__(256) void alpha_minmax_kernel(const float* __restri
 // layout changes for the general (non-fast-path) kernels in module mode
 // Parity hook: the ADC code and STE-pass bit of every partial sum, decoded from the state
 // words cim_fwd_v3_kernel<.., CST> wrote (compact: bits 3*(k*nba + j) + {0 pass, 1 code != 0,
-// 2 code < 0} of st32[(i*M + m)*O + o]; planes: bit k*nba + j of st64[((i*M + m)*O + o)*3 + q]),
+// 2 code < 0} of st32[(i*M + m)*O + o]; planes (1): bit k*nba + j of st64[((i*M + m)*O + o)*3 + q]; planes 2:
+// two compact words per element, pairs kj < 8 in st32[2 e], kj >= 8 at 3*(kj - 8) of st32[2 e + 1]),
 // in the reference's [B, T, nbw, nba, P, O] order.
 __global__ void decode_state_kernel(Geo g, int planes, const uint8_t* __restrict__ st, int8_t* __restrict__ code,
                                     uint8_t* __restrict__ pass) {
@@ -360,8 +361,11 @@ __global__ void decode_state_kernel(Geo g, int planes, const uint8_t* __restrict
     const int m = (int)(im % g.M), i = (int)(im / g.M);
     const int b = m / g.P, p = m - b * g.P;
     uint64_t ps = 0, nz = 0, ng = 0;
-    uint32_t w32 = 0;
-    if (planes) {
+    uint32_t w32 = 0, w32b = 0;
+    if (planes == 2) {
+      w32 = reinterpret_cast<const uint32_t*>(st)[2 * e];
+      w32b = reinterpret_cast<const uint32_t*>(st)[2 * e + 1];
+    } else if (planes) {
       const uint64_t* s64 = reinterpret_cast<const uint64_t*>(st) + e * 3;
       ps = s64[0]; nz = s64[1]; ng = s64[2];
     } else {
@@ -370,7 +374,11 @@ __global__ void decode_state_kernel(Geo g, int planes, const uint8_t* __restrict
     for (int kj = 0; kj < nkj; ++kj) {
       const int k = kj / g.nba, j = kj - k * g.nba;
       int bp, bz, bn;
-      if (planes) {
+      if (planes == 2) {
+        const uint32_t w = kj < 8 ? w32 : w32b;
+        const int sh = 3 * (kj & 7);
+        bp = (w >> sh) & 1; bz = (w >> (sh + 1)) & 1; bn = (w >> (sh + 2)) & 1;
+      } else if (planes) {
         bp = (int)((ps >> kj) & 1u); bz = (int)((nz >> kj) & 1u); bn = (int)((ng >> kj) & 1u);
       } else {
         bp = (w32 >> (3 * kj)) & 1; bz = (w32 >> (3 * kj + 1)) & 1; bn = (w32 >> (3 * kj + 2)) & 1;

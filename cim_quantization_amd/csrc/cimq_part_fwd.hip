@@ -30,8 +30,12 @@ Fwd3Kern fwd3_kernel(int cst, FwdState st, int obm) {
   if constexpr (NBP == 8)  // v7_plan: w8a8 with one 16-channel block
     return st == FwdState::RECOMPUTE ? fwd3_obm<8, KS, 8, FwdState::RECOMPUTE, M == FwdMode::INFER ? FwdMode::TRAIN : M, 1>(obm)
                                      : fwd3_obm<8, KS, 8, S, M, 1>(obm);
-  else
+  else if (cst != 4)
     return cst == 2 ? fwd3_obm<NBP, KS, 2, S, M, has_epi(M) ? 2 : 4>(obm) : fwd3_obm<NBP, KS, 3, S, M, 4>(obm);
+  // w4a4 word pairs: training only (v7_w44), two blocks at the most (named last: the older instances keep their
+  // places in the code object)
+  if constexpr (NBP == 4 && M == FwdMode::TRAIN) return fwd3_obm<4, KS, 4, FwdState::WRITE, FwdMode::TRAIN, 2>(obm);
+  return nullptr;
 }
 
 template <int NBP, int KS>
@@ -39,7 +43,7 @@ int launch_fwd_v3(const Geo& g, const Plan3& p, uint8_t* ctx, const float* sw, c
                   hipStream_t s, const ActQ* aq, const Epi* ep = nullptr) {
   CtxLayout L = ctx_layout(g);
   // CST, fixed at compile time: 0 per-k state words (the general backward's), else the compact ones the v7-plan
-  // backwards read -- nbw = nba = CST (2, 3), 8 the w8a8 planes.  The first conv's backward recomputes them; a
+  // backwards read -- nbw = nba = CST (2, 3, 4), 8 the w8a8 planes.  The first conv's backward recomputes them; a
   // forward-only call (CIMQ_OPT_INFERENCE) runs the same instances without the state words, their bits and the
   // backward words (CST 0 and the first conv's write no state as they are)
   const int cst = route_of(g).cst;
@@ -54,6 +58,11 @@ int launch_fwd_v3(const Geo& g, const Plan3& p, uint8_t* ctx, const float* sw, c
   // cost them a wave per SIMD: with an epilogue those layers run the two-block instances, twice the blocks in y;
   // the plan's LDS figures, made for four blocks, cover two)
   if (has_epi(m) && cst == 2 && st == FwdState::NONE && obm == 4) obm = 2;
+  // (w4a4 word pairs: 16 pairs of state bits per output block -- instances of one and two blocks)
+  if (cst == 4) {
+    if (m != FwdMode::TRAIN) return fail(CIMQ_EINVAL, "internal: the w4a4 state words outside a training forward");
+    if (obm == 4) obm = 2;
+  }
   // (the modes in the order the code object has always had its instances: a kernel's place decides its addresses)
   Fwd3Kern kern = nullptr;
   switch (m) {

@@ -2,7 +2,8 @@
 //
 // The forward (cim_fwd_v3_kernel<.., CST = true>) leaves one uint32 per (tile i, output
 // pixel m, channel o): for every slice pair (k, j) the STE pass bit (lsq.py:310-313) and the
-// ADC code (lsq.py:321-332) of that partial sum, 3 bits at 3*(k*nba + j).  Two kernels
+// ADC code (lsq.py:321-332) of that partial sum, 3 bits at 3*(k*nba + j) -- for the 16 pairs of w4a4 a uint2 of two
+// such words, weight slices 0-1 and 2-3 (V7WordsOf, cimq_bwd_dev.h).  Two kernels
 // consume them:
 //
 //  * cim_bwd_gx_v8_kernel -- grad_x as the UNFOLDED product, folded without atomics:
@@ -53,7 +54,8 @@ __global__ __launch_bounds__(256 * NPART) void cim_bwd_gx_v8_kernel(Geo g, V7 v,
                                                             float* __restrict__ gsa_part) {
   constexpr int NKS = (NBW * OBX + 1) / 2;
   constexpr int NKJ = NBW * NBA;
-  constexpr bool PLS = NKJ > 10;  // plane state words (cim_fwd_v3_kernel PLF)
+  constexpr bool PLS = V7WordsOf<NBW, NBA>::fmt == V7W_PLANES;  // plane state words (cim_fwd_v3_kernel PLF)
+  constexpr bool X2 = V7WordsOf<NBW, NBA>::fmt == V7W_32X2;     // two interleaved words (cim_fwd_v3_kernel CST 4)
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int bid = (int)blockIdx.x;
   const int b = bid / v.nbands, band = bid - b * v.nbands;
@@ -118,12 +120,24 @@ __global__ __launch_bounds__(256 * NPART) void cim_bwd_gx_v8_kernel(Geo g, V7 v,
       }
     for (int i = 0; i < g.T; ++i) {
       // state words of this lane's pixel, channels 4*g4 .. +3 of each o-block: interleaved
-      // (3 bits per slice pair) or, for more than 10 pairs, the 64-bit pass plane
+      // (3 bits per slice pair; sv2: the second word of the pairs of weight slices 2-3) or the 64-bit pass plane
       uint32_t sv[OBX][4];
+      uint32_t sv2[X2 ? OBX : 1][4];
       uint64_t sp[OBX][4];
 #pragma unroll
       for (int ob = 0; ob < OBX; ++ob) {
-        if constexpr (PLS) {
+        if constexpr (X2) {
+          uint4 sa4 = make_uint4(0u, 0u, 0u, 0u), sb4 = sa4;
+          if (pv) {
+            const uint4* s8 = reinterpret_cast<const uint4*>(st + 2 * (((size_t)i * g.M + m) * g.O + ob * 16 + 4 * g4));
+            sa4 = s8[0];
+            sb4 = s8[1];
+          }
+          sv[ob][0] = sa4.x; sv2[ob][0] = sa4.y; sv[ob][1] = sa4.z; sv2[ob][1] = sa4.w;
+          sv[ob][2] = sb4.x; sv2[ob][2] = sb4.y; sv[ob][3] = sb4.z; sv2[ob][3] = sb4.w;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) sp[ob][r] = 0ull;
+        } else if constexpr (PLS) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             uint2 w2 = make_uint2(0u, 0u);
@@ -162,6 +176,16 @@ __global__ __launch_bounds__(256 * NPART) void cim_bwd_gx_v8_kernel(Geo g, V7 v,
                 E = 0.f;
 #pragma unroll 1
                 for (int j = 0; j < NBA; ++j) E += ((fld >> j) & 1u) ? cel[k * NBA + j] : 0.f;
+              }
+            } else if constexpr (X2) {
+              // slice k's four pass bits sit in word k / 2 where a two-slice word has slice k % 2's
+              const uint32_t w = k < 2 ? sv[ob][r] : sv2[X2 ? ob : 0][r];
+              if (std_mask) {
+                E = ldexpf((float)__popc(w & pass_mask_k(k & 1, NBA)), g.bsw * k);
+              } else {
+                E = 0.f;
+#pragma unroll
+                for (int j = 0; j < NBA; ++j) E += ((w >> (3 * ((k & 1) * NBA + j))) & 1u) ? cel[k * NBA + j] : 0.f;
               }
             } else if (std_mask) {
               E = ldexpf((float)__popc(sv[ob][r] & pass_mask_k(k, NBA)), g.bsw * k);
@@ -358,7 +382,8 @@ __global__ __launch_bounds__(256, 2) void cim_bwd_gw_v7_kernel(Geo g, V7 v, cons
                                                             float* __restrict__ gw_slab,
                                                             float* __restrict__ ga_slab) {
   constexpr int NKJ = NBW * NBA;
-  constexpr bool PLS = NKJ > 10;  // plane state words (cim_fwd_v3_kernel PLF)
+  constexpr bool PLS = V7WordsOf<NBW, NBA>::fmt == V7W_PLANES;  // plane state words (cim_fwd_v3_kernel PLF)
+  constexpr bool X2 = V7WordsOf<NBW, NBA>::fmt == V7W_32X2;     // two interleaved words (cim_fwd_v3_kernel CST 4)
   constexpr int NGR = PLS ? 2 : 9;  // row groups of 16 per channel block (w8a8 plan: C*KHW <= 32)
   typedef typename std::conditional<(NBA > 4), uint2, uint32_t>::type XW;  // ctx slice bytes (NBP)
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -476,7 +501,8 @@ __global__ __launch_bounds__(256, 2) void cim_bwd_gw_v7_kernel(Geo g, V7 v, cons
   };
 
   // stride 2 keeps the per-stage LDS reduction: the registers would cost it a wave per SIMD
-  constexpr bool RGQ = !PLS && SS == 1;
+  // (nor the 16 pairs of w4a4: two tiles' 32 partials on top of four slices' B operands spill)
+  constexpr bool RGQ = !PLS && !X2 && SS == 1;
   constexpr int NGQ = RGQ ? NKJ : 1;
   float gq0[NGQ], gq1[NGQ];  // grad_alpha partials of tiles i_lo, i_lo + 1 (this lane's pixels)
 #pragma unroll
@@ -507,8 +533,13 @@ __global__ __launch_bounds__(256, 2) void cim_bwd_gw_v7_kernel(Geo g, V7 v, cons
     const int oh = pimg >> v.lw, ow0 = pimg & (Wo - 1);
     float gv[8];
     uint32_t sv0[8], sv1[8];
+    uint32_t sh0[X2 ? 8 : 1], sh1[X2 ? 8 : 1];  // (the second words: pairs of weight slices 2-3)
 #pragma unroll
     for (int e = 0; e < 8; ++e) { gv[e] = 0.f; sv0[e] = sv1[e] = 0u; }
+    if constexpr (X2) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sh0[e] = sh1[e] = 0u;
+    }
     if (kvalid) {
       if (g.onchw) {
         const float4* gp = reinterpret_cast<const float4*>(gout + ((size_t)b * g.O + o) * g.P + pimg);
@@ -519,7 +550,21 @@ __global__ __launch_bounds__(256, 2) void cim_bwd_gw_v7_kernel(Geo g, V7 v, cons
 #pragma unroll
         for (int e = 0; e < 8; ++e) gv[e] = gout[(mk8 + e) * g.O + o];
       }
-      if (!PLS) {
+      if constexpr (X2) {
+        const uint2* s2 = reinterpret_cast<const uint2*>(st);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+          const uint2 w = s2[((size_t)i_lo * g.M + mk8 + e) * g.O + o];
+          sv0[e] = w.x; sh0[e] = w.y;
+        }
+        if (ntl > 1) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const uint2 w = s2[((size_t)(i_lo + 1) * g.M + mk8 + e) * g.O + o];
+            sv1[e] = w.x; sh1[e] = w.y;
+          }
+        }
+      } else if (!PLS) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) sv0[e] = st[((size_t)i_lo * g.M + mk8 + e) * g.O + o];
         if (ntl > 1) {
@@ -682,7 +727,19 @@ __global__ __launch_bounds__(256, 2) void cim_bwd_gw_v7_kernel(Geo g, V7 v, cons
       } else if (!PLS && tl < ntl) {
         const int i = i_lo + tl;
         uint32_t sv[8];
-        if (tl < 2) {
+        uint32_t sh[X2 ? 8 : 1];
+        if constexpr (X2) {
+          if (tl < 2) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { sv[e] = tl == 0 ? sv0[e] : sv1[e]; sh[e] = tl == 0 ? sh0[e] : sh1[e]; }
+          } else {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              const uint2 w = reinterpret_cast<const uint2*>(st)[((size_t)i * g.M + mk8 + e) * g.O + o];
+              sv[e] = w.x; sh[e] = w.y;
+            }
+          }
+        } else if (tl < 2) {
 #pragma unroll
           for (int e = 0; e < 8; ++e) sv[e] = tl == 0 ? sv0[e] : sv1[e];
         } else {
@@ -699,7 +756,9 @@ __global__ __launch_bounds__(256, 2) void cim_bwd_gw_v7_kernel(Geo g, V7 v, cons
             for (int e = 0; e < 8; ++e) {
               // the code itself is the signed 2-bit field at bits 3kj+1 .. 3kj+2 ({nz, neg}: 01 = +1,
               // 11 = -1, 00 = 0): one v_bfe_i32, a convert and an fma (code * g is exact)
-              const int code = ((int)(sv[e] << (29 - 3 * kj))) >> 30;
+              int code;
+              if constexpr (X2) code = ((int)((kj < 8 ? sv[e] : sh[X2 ? e : 0]) << (29 - 3 * (kj & 7)))) >> 30;
+              else code = ((int)(sv[e] << (29 - 3 * kj))) >> 30;
               q = __builtin_fmaf((float)code, gv[e], q);
             }
             qv[kj] = q;
@@ -729,7 +788,18 @@ __global__ __launch_bounds__(256, 2) void cim_bwd_gw_v7_kernel(Geo g, V7 v, cons
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             float D;
-            if (std_mask) {
+            if constexpr (X2) {
+              // slice j's pass bits of both words (every third bit: the second word's fit one place up)
+              if (std_mask) {
+                const uint32_t mj = pass_mask_j(j, 2, NBA);
+                D = ldexpf((float)__popc((sv[e] & mj) | ((sh[X2 ? e : 0] & mj) << 1)), g.bsa * j);
+              } else {
+                D = 0.f;
+#pragma unroll
+                for (int k = 0; k < NBW; ++k)
+                  D += (((k < 2 ? sv[e] : sh[X2 ? e : 0]) >> (3 * ((k & 1) * NBA + j))) & 1u) ? cdl[k * NBA + j] : 0.f;
+              }
+            } else if (std_mask) {
               D = ldexpf((float)__popc(sv[e] & pass_mask_j(j, NBW, NBA)), g.bsa * j);
             } else {
               D = 0.f;
