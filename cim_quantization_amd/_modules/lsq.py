@@ -19,8 +19,8 @@ import torch.nn.functional as F
 
 from ..functional import (alpha_cim_init, cim_conv2d_lsq, cim_conv2d_lsq_shift, cim_module_conv,  # noqa: F401
                           act_codes_of, cim_module_conv_codes, cim_module_conv_epilogue, cim_module_shift_conv, get_adcless_cim_output, get_analog_partial_sums_autograd_ver2,
-                          get_cim_output_signed, inference_call, inference_weights, lsq_quantize,
-                          module_shift_supported, qconv2d)
+                          conv_out_hw, get_cim_output_signed, inference_call, inference_weights, lsq_quantize,
+                          module_descs, module_shift_supported, qconv2d)
 from ._quan_base import (_ActQ, _Conv2dQ, _Conv2dQCiM, _LinearQ, Qmodes, grad_scale,  # noqa: F401
                          round_pass)
 
@@ -88,6 +88,15 @@ class Conv2dLSQCiM(_Conv2dQCiM):
         self._inf_prep = None     # functional.inference_weights: the weight side the no-grad forwards share
         self._last_x_shape = None
 
+    def layer_config(self):
+        """(stride, padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha): the
+        configuration the functional entry points take positionally, as the attributes are now."""
+        return (self.stride, self.padding, self.dilation, self.nbits_a, self.abitslice, self.nbits_w, self.wbitslice,
+                self.adcbits, self.xbar, self.nbits_alpha)
+
+    def _out_hw(self, x_shape):
+        return conv_out_hw(x_shape[-2], x_shape[-1], *self.weight.shape[-2:], self.stride, self.padding)
+
     def _fused_ready(self):
         """True once the steady-state library path applies and an input shape is known
         (prepare_weights needs both)."""
@@ -100,9 +109,7 @@ class Conv2dLSQCiM(_Conv2dQCiM):
         """Whether libcimq's fused shift path takes input shape x.shape (cached per shape)."""
         key = tuple(x.shape)
         if getattr(self, "_shift_ok", None) is None or self._shift_ok[0] != key:
-            self._shift_ok = (key, x.is_cuda and module_shift_supported(
-                key, self.weight, self.stride, self.padding, self.dilation, self.nbits_a, self.abitslice,
-                self.nbits_w, self.wbitslice, self.adcbits, self.xbar, self.nbits_alpha))
+            self._shift_ok = (key, x.is_cuda and module_shift_supported(key, self.weight, *self.layer_config()))
         return self._shift_ok[1]
 
     def _load_from_state_dict(self, *args, **kwargs):
@@ -144,10 +151,10 @@ class Conv2dLSQCiM(_Conv2dQCiM):
                     inference_call(x, self.weight, self.alpha_act, self.alpha_weight, self.alpha_cim, self.beta_cim)):
                 # evaluation: the forward-only weight side (beta_cim in it), made once and kept while it matches
                 wprep = self._inf_prep = inference_weights(self, x.shape, self._inf_prep)
+            cfg = self.layer_config()
             out = cim_module_shift_conv(x, self.weight, self.alpha_act, self.alpha_weight, self.alpha_cim,
-                                        self.beta_cim, self.binary_mask, self.signed_act, self.stride, self.padding,
-                                        self.dilation, self.nbits_a, self.abitslice, self.nbits_w, self.wbitslice,
-                                        self.xbar, self.nbits_alpha, wprep=wprep)
+                                        self.beta_cim, self.binary_mask, self.signed_act, *cfg[:7], *cfg[8:],
+                                        wprep=wprep)  # (no adcbits: the fused shift path is 1.5-bit)
             return out if self.bias is None else out + self.bias  # lsq.py:583's broadcast
         if (self.fused and flags[0] and (flags[1] or self.alpha_cim is None) and self.adcbits != 0
                 and not self.adc_shift):
@@ -160,10 +167,8 @@ class Conv2dLSQCiM(_Conv2dQCiM):
                 # evaluation: the forward-only weight side, made once and kept while it matches
                 wprep = self._inf_prep = inference_weights(self, x.shape, self._inf_prep)
             out = cim_module_conv(x, self.weight, self.alpha_act, self.alpha_weight, self.alpha_cim,
-                                  self.binary_mask, self.signed_act, self.stride, self.padding, self.dilation,
-                                  self.nbits_a, self.abitslice, self.nbits_w, self.wbitslice, self.adcbits,
-                                  self.xbar, self.nbits_alpha, self.accumulate_grads_in_place,
-                                  bool(self.stochastic_quant),
+                                  self.binary_mask, self.signed_act, *self.layer_config(),
+                                  self.accumulate_grads_in_place, bool(self.stochastic_quant),
                                   self.tail_stream if self.accumulate_grads_in_place else None, wprep,
                                   self.recompute_psum)
             if self.bias is not None:
@@ -189,18 +194,14 @@ class Conv2dLSQCiM(_Conv2dQCiM):
         if self.adcbits == 0:                                                          # lsq.py:584-585
             x_q = round_pass((x / sa).clamp(qn_a, qp_a)) * sa
             return F.conv2d(x_q, w_q, self.bias, self.stride, self.padding, self.dilation)
+        cfg = self.layer_config()[:9]  # (these two take no nbits_alpha: alpha_q is quantised above)
         if self.adc_shift:
-            out = cim_conv2d_lsq_shift(x, w_q, sa, sw, alpha_q, self.beta_cim, self.binary_mask, self.signed_act,
-                                       self.stride, self.padding, self.dilation, self.nbits_a, self.abitslice,
-                                       self.nbits_w, self.wbitslice, self.adcbits, self.xbar)
+            out = cim_conv2d_lsq_shift(x, w_q, sa, sw, alpha_q, self.beta_cim, self.binary_mask, self.signed_act, *cfg)
         else:
-            out = cim_conv2d_lsq(x, w_q, sa, sw, alpha_q, self.binary_mask, self.signed_act, self.stride,
-                                 self.padding, self.dilation, self.nbits_a, self.abitslice, self.nbits_w,
-                                 self.wbitslice, self.adcbits, self.xbar, bool(self.stochastic_quant))
+            out = cim_conv2d_lsq(x, w_q, sa, sw, alpha_q, self.binary_mask, self.signed_act, *cfg,
+                                 bool(self.stochastic_quant))
         # lsq.py:123's fold_x, per axis (the same number twice for the reference's square layers)
-        ho = (x.shape[-2] - self.weight.shape[-2] + 2 * self.padding[0]) // self.stride[0] + 1
-        wo = (x.shape[-1] - self.weight.shape[-1] + 2 * self.padding[1]) // self.stride[1] + 1
-        out = out.transpose(1, 2).view(x.shape[0], self.out_channels, ho, wo)         # lsq.py:580-581
+        out = out.transpose(1, 2).view(x.shape[0], self.out_channels, *self._out_hw(x.shape))  # lsq.py:580-581
         if self.bias is not None:
             out = out + self.bias  # broadcasts over the last axis, as lsq.py:583
         return out
@@ -233,16 +234,8 @@ class Conv2dLSQCiM(_Conv2dQCiM):
         hit = getattr(self, "_codes_ok", None)
         if hit is None or hit[0] != key:
             from .. import _lib
-            from ..functional import _module_descs, _shift_module_descs
-            # (a query of the route alone: never the stochastic form, which would draw a seed)
-            if self.adc_shift:
-                desc, _ = _shift_module_descs(key, self.weight, self.stride, self.padding, self.dilation, self.nbits_a,
-                                              self.abitslice, self.nbits_w, self.wbitslice, self.xbar, self.nbits_alpha)
-            else:
-                desc, _ = _module_descs(key, self.weight, self.stride, self.padding, self.dilation, self.nbits_a,
-                                        self.abitslice, self.nbits_w, self.wbitslice, self.adcbits, self.xbar,
-                                        self.nbits_alpha, self.alpha_cim is not None, False, self.recompute_psum, True)
-            desc.options |= _lib.CIMQ_OPT_INFERENCE
+            # (a query of the route alone: module_descs never builds the stochastic form, which would draw a seed)
+            desc, _ = module_descs(self, key, inference=True)
             hit = self._codes_ok = (key, _lib.codes_supported(desc))
         return hit[1]
 
@@ -282,19 +275,16 @@ class Conv2dLSQCiM(_Conv2dQCiM):
                 raise ValueError("Conv2dLSQCiM.forward_fused: keep_float=False needs out_quant")
             return cim_module_conv_epilogue(
                 x, self.weight, self.alpha_act, self.alpha_weight, self.alpha_cim, self.binary_mask, self.signed_act,
-                self.stride, self.padding, self.dilation, self.nbits_a, self.abitslice, self.nbits_w, self.wbitslice,
-                self.adcbits, self.xbar, self.nbits_alpha, scale, shift, residual=residual, relu=relu,
+                *self.layer_config(), scale, shift, residual=residual, relu=relu,
                 beta_cim=self.beta_cim if self.adc_shift else None, stochastic=bool(self.stochastic_quant),
                 wprep=wprep, recompute=self.recompute_psum)
         oq = None
         if out_quant is not None:
-            ho = (x.shape[-2] - self.weight.shape[-2] + 2 * self.padding[0]) // self.stride[0] + 1
-            wo = (x.shape[-1] - self.weight.shape[-1] + 2 * self.padding[1]) // self.stride[1] + 1
+            ho, wo = self._out_hw(x.shape)
             oq = out_quant._code_quant(x.shape[0] * self.out_channels * ho * wo)
         return cim_module_conv_codes(
             x, self.weight, self.alpha_act, self.alpha_weight, self.alpha_cim, self.binary_mask, self.signed_act,
-            self.stride, self.padding, self.dilation, self.nbits_a, self.abitslice, self.nbits_w, self.wbitslice,
-            self.adcbits, self.xbar, self.nbits_alpha, scale, shift, residual=residual, relu=relu,
+            *self.layer_config(), scale, shift, residual=residual, relu=relu,
             beta_cim=self.beta_cim if self.adc_shift else None, stochastic=bool(self.stochastic_quant), wprep=wprep,
             recompute=self.recompute_psum, out_quant=oq, keep_float=keep_float)
 

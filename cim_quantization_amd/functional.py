@@ -18,12 +18,17 @@ the same ``out`` bit for bit, no backward state written, a ctx of the weight tab
 saved.  The choice is made before ``Function.apply`` (inside ``forward`` grad mode is always off and
 ``needs_input_grad`` is all True, whatever the caller's mode).
 
+One marshalling path: every conv call takes its sizes from ``_geometry``, its tensors from ``_operands`` (an
+``Operands``, which is also every Function's ``ctx.bufs``) and, at the module entry points, its descriptors,
+prepared weight side and buffers from ``_layer_call``; a backward places its gradients with ``_grads``.
+
 Device-only: CPU tensors raise (there is no CPU fallback in the product path).
 """
 from __future__ import annotations
 
 import contextlib
 import ctypes
+import inspect
 import math
 
 import torch
@@ -62,23 +67,135 @@ def stochastic_seed() -> int:
     return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
 
 
+def _dense(t, device, dtype):
+    """``t`` detached, contiguous, of ``dtype`` on ``device``.  A tensor that already is all that comes back as a
+    view of its own storage (what ``.to().contiguous()`` gives too, without their dispatch cost on every call)."""
+    if not isinstance(t, torch.Tensor):
+        t = torch.tensor(t)
+    if t.dtype is dtype and t.device == device and t.is_contiguous():
+        return t.detach()
+    return t.detach().to(device=device, dtype=dtype).contiguous()
+
+
 def _f32(t, device):
-    t = t if torch.is_tensor(t) else torch.tensor(t)
-    return t.detach().to(device=device, dtype=torch.float32).contiguous()
+    return _dense(t, device, torch.float32)
+
+
+def _one(t, device):
+    """A scalar argument (a step size, signed_act) as the fp32 tensor whose first element the library reads."""
+    t = _dense(t, device, torch.float32)
+    return t if t.numel() == 1 else t.reshape(-1)[:1].contiguous()
+
+
+def _ptrs(*ts):
+    """The device addresses of consecutive library arguments (None for an absent one)."""
+    return [None if t is None else t.data_ptr() for t in ts]
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _ubuf(nbytes, device):
+    return torch.empty(max(nbytes, 1), device=device, dtype=torch.uint8)
+
+
+def conv_out_hw(H, W, KH, KW, stride, padding):
+    """Output height and width of the CiM conv (dilation 1; lsq.py:123's fold_x, per axis)."""
+    return (H + 2 * padding[0] - KH) // stride[0] + 1, (W + 2 * padding[1] - KW) // stride[1] + 1
+
+
+def out_hw(desc):
+    """conv_out_hw of a ``_lib.ConvDesc``."""
+    return conv_out_hw(desc.in_h, desc.in_w, desc.kernel_h, desc.kernel_w, (desc.stride_h, desc.stride_w),
+                       (desc.pad_h, desc.pad_w))
 
 
 def _geometry(x, w, stride, padding, dilation):
-    stride = tuple(stride) if isinstance(stride, (tuple, list)) else (stride, stride)
-    padding = tuple(padding) if isinstance(padding, (tuple, list)) else (padding, padding)
-    dilation = tuple(dilation) if isinstance(dilation, (tuple, list)) else (dilation, dilation)
-    if tuple(dilation) != (1, 1):
+    """(B, C, H, W, O, KH, KW, stride pair, padding pair, Ho, Wo) of one conv call."""
+    stride, padding = _pair(stride), _pair(padding)
+    if _pair(dilation) != (1, 1):
         # lsq.py:141 unfolds without dilation while lsq.py:382 folds with it; only 1 is consistent
         raise NotImplementedError("CiM conv supports dilation 1 only (as the reference's unfold)")
     B, C, H, W = x.shape
     O, Cw, KH, KW = w.shape
     if Cw != C:
         raise ValueError(f"weight in_channels {Cw} != input channels {C} (groups are not supported)")
-    return B, C, H, W, O, KH, KW, stride, padding
+    return (B, C, H, W, O, KH, KW, stride, padding) + conv_out_hw(H, W, KH, KW, stride, padding)
+
+
+class Operands:
+    """The tensors of one conv call as the library reads them, by name; every Function's ``ctx.bufs``.
+    ``sa`` / ``sw``: the activation / weight step sizes (the module entry points' alpha_act / alpha_weight);
+    ``alpha`` / ``beta``: alpha_cim / beta_cim, or None; ``ctx``: the call's ctx buffer (uint8)."""
+
+    __slots__ = ("x", "w", "sa", "sw", "alpha", "beta", "mask", "sgn", "ctx")
+
+
+def _operands(x, w, sa, sw, alpha, beta, mask, sgn, x_codes=False):
+    """Operands of a call on ``x``'s device: contiguous fp32 tensors, [1] scalars, an int8 mask; ``ctx`` is left
+    to the caller.  A contiguous fp32 tensor already there passes through as a view of its own storage, so the
+    library reads a parameter where it lives (_versions and the one-call plan rely on that).  ``x_codes``: x
+    holds uint8 activation codes, taken as they are."""
+    dev, f32 = x.device, torch.float32
+    o = Operands()
+    o.x = x.detach().contiguous() if x_codes else _dense(x, dev, f32)
+    o.w = _dense(w, dev, f32)
+    o.sa, o.sw = _one(sa, dev), _one(sw, dev)
+    o.alpha = None if alpha is None else _dense(alpha, dev, f32)
+    o.beta = None if beta is None else _dense(beta, dev, f32)
+    o.mask = _dense(mask, dev, torch.int8)
+    o.sgn = _one(sgn, dev)
+    o.ctx = None
+    return o
+
+
+def _arg_names(forward):
+    """The argument names of a Function's ``forward`` after ctx: its backward returns one gradient for each."""
+    return tuple(inspect.signature(forward).parameters)[1:]
+
+
+def _grads(names, **by_name):
+    """A backward's result: the given gradients at their arguments' positions among ``names``, None elsewhere
+    (a name the forward does not have raises)."""
+    out = [None] * len(names)
+    for k, g in by_name.items():
+        out[names.index(k)] = g
+    return tuple(out)
+
+
+def _cim_forward(x, w, sa, sw, alpha, binary_mask, signed_act, stride, padding, dilation, act_bits, act_bs, w_bits,
+                 w_bs, adc_bits, arr, stochastic, input_kind, qp_a, inference=False):
+    """cimq_forward on quantised values (CIMQ_INPUT_XQ) or on the raw activation (CIMQ_INPUT_RAW_LSQ, clamp
+    maximum ``qp_a``); returns (out, desc, sizes, operands).  ``inference``: CIMQ_OPT_INFERENCE."""
+    _require_device(x)
+    B, C, H, W, O, KH, KW, st, pd, Ho, Wo = _geometry(x, w, stride, padding, dilation)
+    desc = _lib.make_desc(B, C, H, W, O, KH, KW, st, pd, arr, w_bits, act_bits, w_bs, act_bs, adc_bits, input_kind,
+                          qp_a, _lib.CIMQ_ADC_STOCHASTIC if stochastic else _lib.CIMQ_ADC_LIBRARY,
+                          stochastic_seed() if stochastic else 0, _lib.CIMQ_OPT_INFERENCE if inference else 0)
+    sizes = _lib.query_sizes(desc)
+    o = _operands(x, w, sa, sw, alpha, None, binary_mask, signed_act)
+    out = torch.empty(B, Ho * Wo, O, device=x.device, dtype=torch.float32)
+    o.ctx = _ubuf(sizes.ctx_bytes, x.device)
+    _lib.check(_lib.load().cimq_forward(desc, *_ptrs(o.x, o.w, o.sa, o.sw, o.alpha, o.mask, o.sgn, out, o.ctx), None,
+                                        _stream()), "cimq_forward")
+    return out, desc, sizes, o
+
+
+def _cim_backward(ctx, grad_output, want_gsa):
+    """cimq_backward of a _cim_forward ctx; returns (grad_x, grad_w, grad_alpha or None, grad_sa or None)."""
+    ctx.saved_tensors  # noqa: B018 -- raises if x / w changed in place since the forward
+    o = ctx.bufs
+    dev = o.x.device
+    g = _f32(grad_output, dev)
+    gx = torch.empty_like(o.x)
+    gw = torch.empty_like(o.w)
+    gsa = torch.empty(1, device=dev, dtype=torch.float32) if want_gsa else None
+    ga = None if o.alpha is None else torch.empty_like(o.alpha)
+    ws = _ubuf(ctx.sizes.bwd_workspace_bytes, dev)
+    _lib.check(_lib.load().cimq_backward(ctx.desc, *_ptrs(g, o.x, o.sa, o.sw, o.alpha, o.mask, o.sgn, o.ctx, gx, gw,
+                                                          ga, gsa, ws), _stream()), "cimq_backward")
+    return gx, gw, ga, gsa
 
 
 class get_cim_output_signed(torch.autograd.Function):
@@ -96,67 +213,28 @@ class get_cim_output_signed(torch.autograd.Function):
     def _call(x, w, conv_stride, conv_padding, conv_dilation, act_bits, act_bit_slice,
               weight_bits, weight_bit_slice, adc_bits, arr, binary_mask, alpha_cim,
               weight_scaling_factor, act_scaling_factor, stochastic, signed_act, inference=False):
-        """cimq_forward; returns (out, desc, sizes, bufs, wq).  ``inference``: CIMQ_OPT_INFERENCE."""
         if stochastic:
             assert adc_bits == 1.5  # lsq.py:136-137
-        _require_device(x)
-        dev = x.device
-        B, C, H, W, O, KH, KW, st, pd = _geometry(x, w, conv_stride, conv_padding, conv_dilation)
-        desc = _lib.make_desc(B, C, H, W, O, KH, KW, st, pd, arr, weight_bits, act_bits,
-                              weight_bit_slice, act_bit_slice, adc_bits, _lib.CIMQ_INPUT_XQ,
-                              adc_variant=_lib.CIMQ_ADC_STOCHASTIC if stochastic else _lib.CIMQ_ADC_LIBRARY,
-                              seed=stochastic_seed() if stochastic else 0,
-                              options=_lib.CIMQ_OPT_INFERENCE if inference else 0)
-        sizes = _lib.query_sizes(desc)
-        xq = x.detach().to(torch.float32).contiguous()
-        wq = w.detach().to(torch.float32).contiguous()
-        sa = _f32(act_scaling_factor, dev).reshape(-1)[:1].contiguous()
-        sw = _f32(weight_scaling_factor, dev).reshape(-1)[:1].contiguous()
-        bm = binary_mask.detach().to(device=dev, dtype=torch.int8).contiguous()
-        sg = _f32(signed_act, dev).reshape(-1)[:1].contiguous()
-        al = None if alpha_cim is None else alpha_cim.detach().to(device=dev, dtype=torch.float32).contiguous()
-        Ho = (H + 2 * pd[0] - KH) // st[0] + 1
-        Wo = (W + 2 * pd[1] - KW) // st[1] + 1
-        out = torch.empty(B, Ho * Wo, O, device=dev, dtype=torch.float32)
-        cbuf = torch.empty(max(sizes.ctx_bytes, 1), device=dev, dtype=torch.uint8)
-        lib = _lib.load()
-        _lib.check(lib.cimq_forward(desc, xq.data_ptr(), wq.data_ptr(), sa.data_ptr(), sw.data_ptr(),
-                                    None if al is None else al.data_ptr(), bm.data_ptr(), sg.data_ptr(),
-                                    out.data_ptr(), cbuf.data_ptr(), None, _stream()), "cimq_forward")
-        return out, desc, sizes, (xq, sa, sw, al, bm, sg, cbuf), wq
+        return _cim_forward(x, w, act_scaling_factor, weight_scaling_factor, alpha_cim, binary_mask, signed_act,
+                            conv_stride, conv_padding, conv_dilation, act_bits, act_bit_slice, weight_bits,
+                            weight_bit_slice, adc_bits, arr, stochastic, _lib.CIMQ_INPUT_XQ, 0.0, inference)
 
     @staticmethod
     def forward(ctx, x, w, conv_stride, conv_padding, conv_dilation, act_bits, act_bit_slice,
                 weight_bits, weight_bit_slice, adc_bits, arr, binary_mask, alpha_cim,
                 weight_scaling_factor, act_scaling_factor, stochastic, signed_act):
-        out, desc, sizes, bufs, wq = get_cim_output_signed._call(
+        out, ctx.desc, ctx.sizes, ctx.bufs = get_cim_output_signed._call(
             x, w, conv_stride, conv_padding, conv_dilation, act_bits, act_bit_slice, weight_bits, weight_bit_slice,
             adc_bits, arr, binary_mask, alpha_cim, weight_scaling_factor, act_scaling_factor, stochastic, signed_act)
-        xq = bufs[0]
-        ctx.desc, ctx.sizes = desc, sizes
-        ctx.bufs = bufs
         ctx.save_for_backward(x, w)  # autograd's version check: in-place edits before backward raise
-        ctx.wshape, ctx.xshape = wq.shape, xq.shape
-        ctx.has_alpha = alpha_cim is not None
         return out
+
+    _ARGS = _arg_names(forward.__func__)
 
     @staticmethod
     def backward(ctx, grad_output):
-        ctx.saved_tensors  # noqa: B018 -- raises if x / w changed in place since the forward
-        xq, sa, sw, al, bm, sg, cbuf = ctx.bufs
-        dev = xq.device
-        g = grad_output.detach().to(torch.float32).contiguous()
-        gx = torch.empty(ctx.xshape, device=dev, dtype=torch.float32)
-        gw = torch.empty(ctx.wshape, device=dev, dtype=torch.float32)
-        ga = torch.empty_like(al) if (ctx.has_alpha and al is not None) else None
-        ws = torch.empty(max(ctx.sizes.bwd_workspace_bytes, 1), device=dev, dtype=torch.uint8)
-        lib = _lib.load()
-        _lib.check(lib.cimq_backward(ctx.desc, g.data_ptr(), xq.data_ptr(), sa.data_ptr(), sw.data_ptr(),
-                                     None if al is None else al.data_ptr(), bm.data_ptr(), sg.data_ptr(),
-                                     cbuf.data_ptr(), gx.data_ptr(), gw.data_ptr(),
-                                     None if ga is None else ga.data_ptr(), None, ws.data_ptr(),
-                                     _stream()), "cimq_backward")
-        return (gx, gw) + (None,) * 10 + (ga,) + (None,) * 4
+        gx, gw, ga, _ = _cim_backward(ctx, grad_output, False)
+        return _grads(get_cim_output_signed._ARGS, x=gx, w=gw, alpha_cim=ga)
 
 
 class _CimConv2dLSQ(torch.autograd.Function):
@@ -165,65 +243,25 @@ class _CimConv2dLSQ(torch.autograd.Function):
     @staticmethod
     def _call(x, w_q, sa, sw, alpha_q, binary_mask, signed_act, stride, padding, dilation,
               nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, stochastic=False, inference=False):
-        """cimq_forward on the raw activation; returns (out, desc, sizes, bufs, wq)."""
-        _require_device(x)
-        dev = x.device
-        B, C, H, W, O, KH, KW, st, pd = _geometry(x, w_q, stride, padding, dilation)
-        qp_a = float(2 ** nbits_a - 1)
-        desc = _lib.make_desc(B, C, H, W, O, KH, KW, st, pd, xbar, nbits_w, nbits_a, wbitslice,
-                              abitslice, adcbits, _lib.CIMQ_INPUT_RAW_LSQ, qp_a,
-                              _lib.CIMQ_ADC_STOCHASTIC if stochastic else _lib.CIMQ_ADC_LIBRARY,
-                              stochastic_seed() if stochastic else 0,
-                              _lib.CIMQ_OPT_INFERENCE if inference else 0)
-        sizes = _lib.query_sizes(desc)
-        xc = x.detach().to(torch.float32).contiguous()
-        wq = w_q.detach().to(torch.float32).contiguous()
-        sa_ = sa.detach().to(torch.float32).reshape(-1)[:1].contiguous()
-        sw_ = sw.detach().to(torch.float32).reshape(-1)[:1].contiguous()
-        al = None if alpha_q is None else alpha_q.detach().to(torch.float32).contiguous()
-        bm = binary_mask.to(device=dev, dtype=torch.int8).contiguous()
-        sg = signed_act.detach().to(device=dev, dtype=torch.float32).reshape(-1)[:1].contiguous()
-        Ho = (H + 2 * pd[0] - KH) // st[0] + 1
-        Wo = (W + 2 * pd[1] - KW) // st[1] + 1
-        out = torch.empty(B, Ho * Wo, O, device=dev, dtype=torch.float32)
-        cbuf = torch.empty(max(sizes.ctx_bytes, 1), device=dev, dtype=torch.uint8)
-        lib = _lib.load()
-        _lib.check(lib.cimq_forward(desc, xc.data_ptr(), wq.data_ptr(), sa_.data_ptr(), sw_.data_ptr(),
-                                    None if al is None else al.data_ptr(), bm.data_ptr(), sg.data_ptr(),
-                                    out.data_ptr(), cbuf.data_ptr(), None, _stream()), "cimq_forward")
-        return out, desc, sizes, (xc, sa_, sw_, al, bm, sg, cbuf), wq
+        return _cim_forward(x, w_q, sa, sw, alpha_q, binary_mask, signed_act, stride, padding, dilation, nbits_a,
+                            abitslice, nbits_w, wbitslice, adcbits, xbar, stochastic, _lib.CIMQ_INPUT_RAW_LSQ,
+                            float(2 ** nbits_a - 1), inference)
 
     @staticmethod
     def forward(ctx, x, w_q, sa, sw, alpha_q, binary_mask, signed_act, stride, padding, dilation,
                 nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, stochastic=False):
-        out, desc, sizes, bufs, wq = _CimConv2dLSQ._call(x, w_q, sa, sw, alpha_q, binary_mask, signed_act, stride,
-                                                         padding, dilation, nbits_a, abitslice, nbits_w, wbitslice,
-                                                         adcbits, xbar, stochastic)
-        ctx.desc, ctx.sizes = desc, sizes
-        ctx.bufs = bufs
+        out, ctx.desc, ctx.sizes, ctx.bufs = _CimConv2dLSQ._call(
+            x, w_q, sa, sw, alpha_q, binary_mask, signed_act, stride, padding, dilation, nbits_a, abitslice, nbits_w,
+            wbitslice, adcbits, xbar, stochastic)
         ctx.save_for_backward(x, w_q)
-        ctx.wshape = wq.shape
-        ctx.has_alpha = alpha_q is not None
         return out
+
+    _ARGS = _arg_names(forward.__func__)
 
     @staticmethod
     def backward(ctx, grad_output):
-        ctx.saved_tensors  # noqa: B018 -- version check of x / w_q
-        xc, sa, sw, al, bm, sg, cbuf = ctx.bufs
-        dev = xc.device
-        g = grad_output.detach().to(torch.float32).contiguous()
-        gx = torch.empty_like(xc)
-        gw = torch.empty(ctx.wshape, device=dev, dtype=torch.float32)
-        gsa = torch.empty(1, device=dev, dtype=torch.float32)
-        ga = torch.empty_like(al) if (ctx.has_alpha and al is not None) else None
-        ws = torch.empty(max(ctx.sizes.bwd_workspace_bytes, 1), device=dev, dtype=torch.uint8)
-        lib = _lib.load()
-        _lib.check(lib.cimq_backward(ctx.desc, g.data_ptr(), xc.data_ptr(), sa.data_ptr(), sw.data_ptr(),
-                                     None if al is None else al.data_ptr(), bm.data_ptr(), sg.data_ptr(),
-                                     cbuf.data_ptr(), gx.data_ptr(), gw.data_ptr(),
-                                     None if ga is None else ga.data_ptr(), gsa.data_ptr(), ws.data_ptr(),
-                                     _stream()), "cimq_backward")
-        return (gx, gw, gsa, None, ga) + (None,) * 12
+        gx, gw, ga, gsa = _cim_backward(ctx, grad_output, True)
+        return _grads(_CimConv2dLSQ._ARGS, x=gx, w_q=gw, sa=gsa, alpha_q=ga)
 
 
 def cim_conv2d_lsq(x, w_q, sa, sw, alpha_q, binary_mask, signed_act, stride, padding, dilation,
@@ -253,54 +291,38 @@ def _shift_forward(ctx, x, w, sa, sw, alpha, beta, binary_mask, signed_act, stri
                    act_bits, act_bs, w_bits, w_bs, adc_bits, arr, variant, input_kind, qp_a):
     _require_device(x)
     dev = x.device
-    B, C, H, W, O, KH, KW, st, pd = _geometry(x, w, stride, padding, dilation)
+    B, C, H, W, O, KH, KW, st, pd, Ho, Wo = _geometry(x, w, stride, padding, dilation)
     desc = _lib.make_desc(B, C, H, W, O, KH, KW, st, pd, arr, w_bits, act_bits, w_bs, act_bs, adc_bits,
                           input_kind, qp_a, variant)
     sizes = _lib.query_sizes(desc)
-    xc = x.detach().to(torch.float32).contiguous()
-    wc = w.detach().to(torch.float32).contiguous()
-    sa_ = _f32(sa, dev).reshape(-1)[:1].contiguous()
-    sw_ = _f32(sw, dev).reshape(-1)[:1].contiguous()
-    al = _f32(alpha, dev)
-    be = _f32(beta, dev)
+    o = _operands(x, w, sa, sw, alpha, beta, _mask_int8(binary_mask, dev), signed_act)
     T = num_xbars(C, (KH, KW), arr)
     nbw, nba = int(w_bits / w_bs), int(act_bits / act_bs)
-    if al.numel() != T * nbw * nba * O or be.numel() != T * nbw * nba * O:
-        al = al.expand(1, T, nbw, nba, 1, O).contiguous()
-        be = be.expand(1, T, nbw, nba, 1, O).contiguous()
-    bm = _mask_int8(binary_mask, dev)
-    sg = _f32(signed_act, dev).reshape(-1)[:1].contiguous()
-    Ho = (H + 2 * pd[0] - KH) // st[0] + 1
-    Wo = (W + 2 * pd[1] - KW) // st[1] + 1
+    if o.alpha.numel() != T * nbw * nba * O or o.beta.numel() != T * nbw * nba * O:
+        o.alpha = o.alpha.expand(1, T, nbw, nba, 1, O).contiguous()
+        o.beta = o.beta.expand(1, T, nbw, nba, 1, O).contiguous()
     out = torch.empty(B, Ho * Wo, O, device=dev, dtype=torch.float32)
-    cbuf = torch.empty(max(sizes.ctx_bytes, 1), device=dev, dtype=torch.uint8)
-    lib = _lib.load()
-    _lib.check(lib.cimq_shift_forward(desc, xc.data_ptr(), wc.data_ptr(), sa_.data_ptr(), sw_.data_ptr(),
-                                      al.data_ptr(), be.data_ptr(), bm.data_ptr(), sg.data_ptr(), out.data_ptr(),
-                                      cbuf.data_ptr(), None, _stream()), "cimq_shift_forward")
-    ctx.desc, ctx.sizes = desc, sizes
-    ctx.bufs = (xc, sa_, sw_, al, be, bm, sg, cbuf)
-    ctx.shapes = (wc.shape, alpha.shape if torch.is_tensor(alpha) else al.shape,
-                  beta.shape if torch.is_tensor(beta) else be.shape)
+    o.ctx = _ubuf(sizes.ctx_bytes, dev)
+    _lib.check(_lib.load().cimq_shift_forward(desc, *_ptrs(o.x, o.w, o.sa, o.sw, o.alpha, o.beta, o.mask, o.sgn, out,
+                                                           o.ctx), None, _stream()), "cimq_shift_forward")
+    ctx.desc, ctx.sizes, ctx.bufs = desc, sizes, o
     return out
 
 
 def _shift_backward(ctx, grad_output):
-    xc, sa, sw, al, be, bm, sg, cbuf = ctx.bufs
-    dev = xc.device
-    wshape, ashape, bshape = ctx.shapes
-    g = grad_output.detach().to(torch.float32).contiguous()
-    gx = torch.empty_like(xc)
-    gw = torch.empty(wshape, device=dev, dtype=torch.float32)
-    ga = torch.empty_like(al)
-    gb = torch.empty_like(be)
+    ctx.saved_tensors  # noqa: B018 -- version check of x / w
+    o = ctx.bufs
+    dev = o.x.device
+    g = _f32(grad_output, dev)
+    gx = torch.empty_like(o.x)
+    gw = torch.empty_like(o.w)
+    ga = torch.empty_like(o.alpha)
+    gb = torch.empty_like(o.beta)
     gsa = torch.empty(1, device=dev, dtype=torch.float32)
-    ws = torch.empty(max(ctx.sizes.bwd_workspace_bytes, 1), device=dev, dtype=torch.uint8)
-    lib = _lib.load()
-    _lib.check(lib.cimq_shift_backward(ctx.desc, g.data_ptr(), xc.data_ptr(), sa.data_ptr(), sw.data_ptr(),
-                                       al.data_ptr(), be.data_ptr(), bm.data_ptr(), sg.data_ptr(), cbuf.data_ptr(),
-                                       gx.data_ptr(), gw.data_ptr(), ga.data_ptr(), gb.data_ptr(), gsa.data_ptr(),
-                                       ws.data_ptr(), _stream()), "cimq_shift_backward")
+    ws = _ubuf(ctx.sizes.bwd_workspace_bytes, dev)
+    _lib.check(_lib.load().cimq_shift_backward(ctx.desc, *_ptrs(g, o.x, o.sa, o.sw, o.alpha, o.beta, o.mask, o.sgn,
+                                                                o.ctx, gx, gw, ga, gb, gsa, ws), _stream()),
+               "cimq_shift_backward")
     # full [1, T, nbw, nba, 1, O]: autograd sums them down to a broadcast alpha / beta's own shape
     return gx, gw, ga, gb, gsa
 
@@ -324,10 +346,9 @@ class _ShiftTestFunction:
                               adc_bits, arr, variant, _lib.CIMQ_INPUT_XQ, 0.0)
 
     @staticmethod
-    def _bwd(ctx, grad_output):
-        ctx.saved_tensors  # noqa: B018 -- version check of x_int / w_int
+    def _bwd(ctx, grad_output, names):
         gx, gw, ga, gb, _ = _shift_backward(ctx, grad_output)
-        return (gx, gw) + (None,) * 10 + (ga, gb)
+        return _grads(names, x_int=gx, w_int=gw, alpha_cim=ga, beta_cim=gb)
 
 
 class get_analog_partial_sums_autograd_ver2(torch.autograd.Function):
@@ -343,9 +364,11 @@ class get_analog_partial_sums_autograd_ver2(torch.autograd.Function):
                                        act_bit_slice, weight_bits, weight_bit_slice, adc_bits, arr, binary_mask,
                                        alpha_cim, beta_cim)
 
+    _ARGS = _arg_names(forward.__func__)
+
     @staticmethod
     def backward(ctx, grad_output):
-        return _ShiftTestFunction._bwd(ctx, grad_output)
+        return _ShiftTestFunction._bwd(ctx, grad_output, get_analog_partial_sums_autograd_ver2._ARGS)
 
 
 class get_adcless_cim_output(torch.autograd.Function):
@@ -362,9 +385,11 @@ class get_adcless_cim_output(torch.autograd.Function):
                                        act_bit_slice, weight_bits, weight_bit_slice, adc_bits, arr, binary_mask,
                                        alpha_cim, beta_cim)
 
+    _ARGS = _arg_names(forward.__func__)
+
     @staticmethod
     def backward(ctx, grad_output):
-        return _ShiftTestFunction._bwd(ctx, grad_output)
+        return _ShiftTestFunction._bwd(ctx, grad_output, get_adcless_cim_output._ARGS)
 
 
 class _CimConv2dLSQShift(torch.autograd.Function):
@@ -380,11 +405,12 @@ class _CimConv2dLSQShift(torch.autograd.Function):
                               dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, variant,
                               _lib.CIMQ_INPUT_RAW_LSQ, float(2 ** nbits_a - 1))
 
+    _ARGS = _arg_names(forward.__func__)
+
     @staticmethod
     def backward(ctx, grad_output):
-        ctx.saved_tensors  # noqa: B018
         gx, gw, ga, gb, gsa = _shift_backward(ctx, grad_output)
-        return (gx, gw, gsa, None, ga, gb) + (None,) * 11
+        return _grads(_CimConv2dLSQShift._ARGS, x=gx, w_q=gw, sa=gsa, alpha_q=ga, beta=gb)
 
 
 def cim_conv2d_lsq_shift(x, w_q, sa, sw, alpha_q, beta, binary_mask, signed_act, stride, padding, dilation,
@@ -452,7 +478,7 @@ def chained_epilogues(device=None):
 class WeightPrep:
     """The weight side of one Conv2dLSQCiM forward, computed ahead by ``prepare_weights``
     (cimq_module_prepare): the buffer, the descriptors it was made for and the parameter
-    versions it saw.  A forward takes it once (``take``) if all three still match."""
+    versions it saw.  A forward takes it once (``_take_wprep``) if all three still match."""
 
     __slots__ = ("buf", "key", "versions")
 
@@ -471,15 +497,36 @@ def _versions(*ts):
     return tuple(-1 if t is None else (t._version, t.data_ptr()) for t in ts)
 
 
+def _layer_params(m):
+    """The tensors a prepared weight side of layer ``m`` depends on, in _versions' order (beta_cim for a
+    shift-ADC layer alone)."""
+    return (m.weight, m.alpha_act, m.alpha_weight, m.alpha_cim, m.binary_mask,
+            m.beta_cim if getattr(m, "adc_shift", False) else None)
+
+
+def _wprep_matches(wprep, desc, lsq, x_shape, params):
+    """Whether ``wprep`` was made for exactly these descriptors, this input shape and the tensors ``params``
+    (weight, alpha_act, alpha_weight, alpha_cim, binary_mask, beta_cim or None) as they are now."""
+    return (wprep is not None and wprep.key == _prep_key(desc, lsq, x_shape)
+            and wprep.versions == _versions(*params))
+
+
+def _take_wprep(wprep, desc, lsq, x_shape, params, stochastic):
+    """Hand a matching prepared weight side (prepare_weights / inference_weights) to the call ``lsq`` describes;
+    returns the buffer the caller keeps alive across the call, or None.  A stochastic call never reads one."""
+    if stochastic or not _wprep_matches(wprep, desc, lsq, x_shape, params):
+        return None
+    lsq.wprep = wprep.buf.data_ptr()
+    return wprep.buf
+
+
 def _module_descs(x_shape, weight, stride, padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits,
                   xbar, nbits_alpha, has_alpha, stochastic, recompute=False, inference=False):
     B, C, H, W = x_shape
     O, _, KH, KW = weight.shape
-    st = tuple(stride) if isinstance(stride, (tuple, list)) else (stride, stride)
-    pd = tuple(padding) if isinstance(padding, (tuple, list)) else (padding, padding)
     qp_a = float(2 ** nbits_a - 1)
     qn_w, qp_w = -(2 ** (nbits_w - 1)), 2 ** (nbits_w - 1) - 1
-    desc = _lib.make_desc(B, C, H, W, O, KH, KW, st, pd, xbar, nbits_w, nbits_a, wbitslice,
+    desc = _lib.make_desc(B, C, H, W, O, KH, KW, _pair(stride), _pair(padding), xbar, nbits_w, nbits_a, wbitslice,
                           abitslice, adcbits, _lib.CIMQ_INPUT_RAW_LSQ, qp_a,
                           _lib.CIMQ_ADC_STOCHASTIC if stochastic else _lib.CIMQ_ADC_LIBRARY,
                           stochastic_seed() if stochastic else 0,
@@ -489,33 +536,53 @@ def _module_descs(x_shape, weight, stride, padding, dilation, nbits_a, abitslice
     return desc, lsq
 
 
-def _prepare_descs(m, shape, inference=False):
-    """The descriptor pair a prepared weight side of layer ``m`` is made for (input shape ``shape``).  A shift-ADC
-    layer (``m.adc_shift``): the fused shift path's pair; the library prepares it forward only."""
-    if getattr(m, "adc_shift", False):
-        if not inference:
-            raise ValueError("a shift-ADC layer's weight side is prepared for forward-only calls alone")
-        desc, lsq = _shift_module_descs(shape, m.weight, m.stride, m.padding, m.dilation, m.nbits_a, m.abitslice,
-                                        m.nbits_w, m.wbitslice, m.xbar, m.nbits_alpha)
-        desc.options |= _lib.CIMQ_OPT_INFERENCE
+def _shift_module_descs(x_shape, weight, stride, padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, xbar,
+                        nbits_alpha):
+    desc, lsq = _module_descs(tuple(x_shape), weight, stride, padding, dilation, nbits_a, abitslice, nbits_w,
+                              wbitslice, 1.5, xbar, nbits_alpha, True, False)
+    desc.adc_variant = _lib.CIMQ_ADC_SHIFT_ROUND
+    return desc, lsq
+
+
+def _layer_descs(x_shape, weight, cfg, has_alpha, shift, stochastic=False, recompute=False, inference=False):
+    """The descriptor pair of one module-entry-point call.  ``cfg``: (stride, padding, dilation, nbits_a, abitslice,
+    nbits_w, wbitslice, adcbits, xbar, nbits_alpha), Conv2dLSQCiM.layer_config's order; ``shift``: the fused shift
+    path's pair (adc 1.5, never stochastic, no recompute form)."""
+    if shift:
+        desc, lsq = _shift_module_descs(x_shape, weight, *cfg[:7], *cfg[8:])
+        if inference:
+            desc.options |= _lib.CIMQ_OPT_INFERENCE
         return desc, lsq
-    return _module_descs(shape, m.weight, m.stride, m.padding, m.dilation, m.nbits_a, m.abitslice,
-                         m.nbits_w, m.wbitslice, m.adcbits, m.xbar, m.nbits_alpha, m.alpha_cim is not None, False,
-                         bool(getattr(m, "recompute_psum", False)), inference)
+    return _module_descs(x_shape, weight, *cfg, has_alpha, stochastic, recompute, inference)
+
+
+def module_descs(m, x_shape, inference=False):
+    """The descriptor pair of layer ``m`` (a Conv2dLSQCiM) for input shape ``x_shape``: what its forward builds,
+    what a prepared weight side is made for and what a route or size query asks about.  A shift-ADC layer
+    (``m.adc_shift``): the fused shift path's pair.  Never the stochastic form, which would draw a seed."""
+    return _layer_descs(x_shape, m.weight, m.layer_config(), m.alpha_cim is not None,
+                        bool(getattr(m, "adc_shift", False)), False, bool(getattr(m, "recompute_psum", False)),
+                        inference)
+
+
+_prepare_descs = module_descs  # the name it had while it was private: kept for callers written against it
 
 
 def _prepare_item(m, shape, inference=False):
     """One layer's cimq_module_prepare item for input shape ``shape``, what it must keep alive until the
-    call, and the WeightPrep the call fills.  ``inference``: for the forward-only descriptor."""
+    call, and the WeightPrep the call fills.  ``inference``: for the forward-only descriptor (the only one the
+    library prepares a shift-ADC layer for)."""
     has_alpha = m.alpha_cim is not None
     shift = bool(getattr(m, "adc_shift", False))
-    desc, lsq = _prepare_descs(m, shape, inference)
+    if shift and not inference:
+        raise ValueError("a shift-ADC layer's weight side is prepared for forward-only calls alone")
+    desc, lsq = module_descs(m, shape, inference)
     sizes = _lib.query_sizes(desc)
     dev = m.weight.device
-    buf = torch.empty(max(sizes.wprep_bytes, 1), device=dev, dtype=torch.uint8)
+    buf = _ubuf(sizes.wprep_bytes, dev)
     bm = m.binary_mask.to(device=dev, dtype=torch.int8).contiguous()
-    ps = (m.weight, m.alpha_act, m.alpha_weight, m.alpha_cim)
-    for t in ps + ((m.beta_cim,) if shift else ()):
+    params = _layer_params(m)
+    for t in params[:4] + params[5:]:
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
             raise ValueError("prepare_weights: parameters must be contiguous fp32")
     it = _lib.PrepareShiftItem() if shift else _lib.PrepareItem()
@@ -529,27 +596,23 @@ def _prepare_item(m, shape, inference=False):
     it.alpha_cim = m.alpha_cim.data_ptr() if has_alpha else None
     it.binary_mask = bm.data_ptr()
     it.wprep = buf.data_ptr()
-    return it, (desc, lsq, bm), WeightPrep(buf, _prep_key(desc, lsq, shape),
-                                           _versions(*ps, m.binary_mask, m.beta_cim if shift else None))
+    return it, (desc, lsq, bm), WeightPrep(buf, _prep_key(desc, lsq, shape), _versions(*params))
 
 
 def inference_weights(m, x_shape, cached=None):
     """The weight side of a forward-only call of the fused Conv2dLSQCiM ``m`` on input shape ``x_shape``:
-    ``cached`` if that WeightPrep was made for this shape and the parameters as they are now (_prep_key,
-    _versions -- an edit through ``p.data`` bumps no version: drop the cache after one), else a new one from
+    ``cached`` if that WeightPrep was made for this shape and the parameters as they are now (_wprep_matches
+    -- an edit through ``p.data`` bumps no version: drop the cache after one), else a new one from
     cimq_module_prepare with the forward roles only.  Conv2dLSQCiM keeps it across the batches of an evaluation.
     A shift-ADC layer (``m.adc_shift``, one the fused shift path takes): the same through
     cimq_module_prepare_shift, with beta_cim among the versions."""
-    shift = bool(getattr(m, "adc_shift", False))
-    if cached is not None:
-        desc, lsq = _prepare_descs(m, tuple(x_shape), inference=True)
-        if (cached.key == _prep_key(desc, lsq, tuple(x_shape)) and cached.versions ==
-                _versions(m.weight, m.alpha_act, m.alpha_weight, m.alpha_cim, m.binary_mask,
-                          m.beta_cim if shift else None)):
-            return cached
-    it, keep, wp = _prepare_item(m, tuple(x_shape), inference=True)
+    x_shape = tuple(x_shape)
+    if cached is not None and _wprep_matches(cached, *module_descs(m, x_shape, inference=True), x_shape,
+                                             _layer_params(m)):
+        return cached
+    it, keep, wp = _prepare_item(m, x_shape, inference=True)
     stream = torch.cuda.current_stream(m.weight.device).cuda_stream
-    if shift:
+    if getattr(m, "adc_shift", False):
         arr = (_lib.PrepareShiftItem * 1)(it)
         _lib.check(_lib.load().cimq_module_prepare_shift(1, arr, stream), "cimq_module_prepare_shift")
     else:
@@ -587,6 +650,51 @@ def prepare_weights(modules, stream=None):
     return len(items)
 
 
+class _LayerCall:
+    """One call of a module entry point, ready to issue: the descriptor pair, the sizes, the operands (their ctx
+    allocated), ``out`` (NCHW, ``out_shape``; None where the caller wants none), the forward workspace and the
+    prepared weight side's buffer the call reads (``keep``, None without one)."""
+
+    __slots__ = ("desc", "lsq", "sizes", "ops", "out", "out_shape", "ws", "keep")
+
+
+def _layer_call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act, cfg,
+                stochastic=False, wprep=None, recompute=False, inference=False, x_codes=False, want_out=True):
+    """What cimq_module_forward, cimq_module_shift_forward (``beta_cim`` given), cimq_module_forward_epilogue and
+    cimq_module_forward_codes have in common, for a layer of configuration ``cfg`` (_layer_descs).  ``wprep``: a
+    WeightPrep, used only if it matches this call; a shift call that can be differentiated never reads one (the
+    library's shift backward reads nothing prepared).  The ctx is the module entry points' (module_ctx_bytes:
+    no per-partial-sum state words where the backward recomputes them, ABI 13)."""
+    _require_device(x)
+    dev = x.device
+    B, _, _, _, O, _, _, st, pd, Ho, Wo = _geometry(x, weight, cfg[0], cfg[1], cfg[2])
+    shift = beta_cim is not None
+    c = _LayerCall()
+    c.desc, c.lsq = _layer_descs(tuple(x.shape), weight, (st, pd) + cfg[2:], alpha_cim is not None, shift,
+                                 stochastic, recompute, inference)
+    c.keep = None
+    if inference or not shift:
+        c.keep = _take_wprep(wprep, c.desc, c.lsq, x.shape,
+                             (weight, alpha_act, alpha_weight, alpha_cim, binary_mask, beta_cim), stochastic)
+    c.sizes = _lib.query_sizes(c.desc)
+    c.ops = _operands(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act, x_codes)
+    c.out_shape = (B, O, Ho, Wo)
+    c.out = torch.empty(c.out_shape, device=dev, dtype=torch.float32) if want_out else None
+    c.ops.ctx = _ubuf(c.sizes.module_ctx_bytes, dev)
+    c.ws = _ubuf(c.sizes.fwd_workspace_bytes, dev)
+    return c
+
+
+def _param_grad_bufs(o):
+    """Fresh gradient buffers for weight, alpha_act, alpha_weight, alpha_cim and beta_cim (None where the layer
+    has none) of a module backward on the operands ``o``."""
+    dev = o.x.device
+    return (torch.empty_like(o.w), torch.empty(1, device=dev, dtype=torch.float32),
+            torch.empty(1, device=dev, dtype=torch.float32),
+            None if o.alpha is None else torch.empty_like(o.alpha),
+            None if o.beta is None else torch.empty_like(o.beta))
+
+
 class _CimModuleConv(torch.autograd.Function):
     """A whole Conv2dLSQCiM layer after its first-step init (lsq.py:544-581): the activation,
     weight and alpha_cim quantisers run inside libcimq on the raw parameters (no torch ops,
@@ -606,56 +714,34 @@ class _CimModuleConv(torch.autograd.Function):
     def _call(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding, dilation,
               nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha, stochastic=False, wprep=None,
               recompute=False, inference=False):
-        """cimq_module_forward; returns (out, desc, lsq, sizes, bufs, wprep_buf).  ``inference``:
-        CIMQ_OPT_INFERENCE (the small ctx and the forward workspace, dropped by the caller)."""
-        _require_device(x)
-        dev = x.device
-        B, C, H, W, O, KH, KW, st, pd = _geometry(x, weight, stride, padding, dilation)
-        desc, lsq = _module_descs(tuple(x.shape), weight, st, pd, dilation, nbits_a, abitslice, nbits_w, wbitslice,
-                                  adcbits, xbar, nbits_alpha, alpha_cim is not None, stochastic, recompute, inference)
-        # a prepared weight side (prepare_weights / inference_weights) if it was made for exactly this call
-        wprep_buf = None
-        if (wprep is not None and not stochastic and wprep.key == _prep_key(desc, lsq, x.shape)
-                and wprep.versions == _versions(weight, alpha_act, alpha_weight, alpha_cim, binary_mask, None)):
-            lsq.wprep = wprep.buf.data_ptr()
-            wprep_buf = wprep.buf
-        sizes = _lib.query_sizes(desc)
-        xc = x.detach().to(torch.float32).contiguous()
-        wc = weight.detach().to(torch.float32).contiguous()
-        aa = alpha_act.detach().to(torch.float32).reshape(-1)[:1].contiguous()
-        aw = alpha_weight.detach().to(torch.float32).reshape(-1)[:1].contiguous()
-        ac = None if alpha_cim is None else alpha_cim.detach().to(torch.float32).contiguous()
-        bm = binary_mask.to(device=dev, dtype=torch.int8).contiguous()
-        sg = signed_act.detach().to(device=dev, dtype=torch.float32).reshape(-1)[:1].contiguous()
-        Ho = (H + 2 * pd[0] - KH) // st[0] + 1
-        Wo = (W + 2 * pd[1] - KW) // st[1] + 1
-        out = torch.empty(B, O, Ho, Wo, device=dev, dtype=torch.float32)
-        # the module ctx: no per-partial-sum state words where the backward recomputes them (ABI 13)
-        cbuf = torch.empty(max(sizes.module_ctx_bytes, 1), device=dev, dtype=torch.uint8)
-        ws = torch.empty(max(sizes.fwd_workspace_bytes, 1), device=dev, dtype=torch.uint8)
-        lib = _lib.load()
-        _lib.check(lib.cimq_module_forward(desc, lsq, xc.data_ptr(), wc.data_ptr(), aa.data_ptr(), aw.data_ptr(),
-                                           None if ac is None else ac.data_ptr(), bm.data_ptr(), sg.data_ptr(),
-                                           out.data_ptr(), cbuf.data_ptr(), ws.data_ptr(), _stream()),
+        """cimq_module_forward; returns its _LayerCall.  ``inference``: CIMQ_OPT_INFERENCE (the small ctx and the
+        forward workspace, dropped by the caller)."""
+        c = _layer_call(x, weight, alpha_act, alpha_weight, alpha_cim, None, binary_mask, signed_act,
+                        (stride, padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha),
+                        stochastic, wprep, recompute, inference)
+        o = c.ops
+        _lib.check(_lib.load().cimq_module_forward(c.desc, c.lsq, *_ptrs(o.x, o.w, o.sa, o.sw, o.alpha, o.mask, o.sgn,
+                                                                         c.out, o.ctx, c.ws), _stream()),
                    "cimq_module_forward")
-        return out, desc, lsq, sizes, (xc, wc, aa, aw, ac, bm, sg, cbuf), wprep_buf
+        return c
 
     @staticmethod
     def forward(ctx, x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding,
                 dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha, accumulate=False,
                 stochastic=False, tail_stream=None, wprep=None, recompute=False):
-        out, desc, lsq, sizes, bufs, ctx.wprep_buf = _CimModuleConv._call(
+        c = _CimModuleConv._call(
             x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding, dilation, nbits_a,
             abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha, stochastic, wprep, recompute)
-        ctx.desc, ctx.lsq, ctx.sizes = desc, lsq, sizes
-        ctx.bufs = bufs
+        ctx.desc, ctx.lsq, ctx.sizes, ctx.bufs, ctx.wprep_buf = c.desc, c.lsq, c.sizes, c.ops, c.keep
         ctx.module_path = True  # a cimq_module_forward ctx (debug_state_codes)
         # the backward reads x and the raw parameters again (act-LSQ / weight-LSQ STE); saving
         # them lets autograd's version counters catch an in-place change in between
         ctx.save_for_backward(x, weight, alpha_act, alpha_weight, alpha_cim)
         ctx.params = (weight, alpha_act, alpha_weight, alpha_cim) if accumulate else None
         ctx.tail_stream = tail_stream if accumulate else None
-        return out
+        return c.out
+
+    _ARGS = _arg_names(forward.__func__)
 
     @staticmethod
     def _grad_targets(ctx):
@@ -677,10 +763,10 @@ class _CimModuleConv(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_output):
         ctx.saved_tensors  # noqa: B018 -- version check of x and the parameters
-        xc, wc, aa, aw, ac, bm, sg, cbuf = ctx.bufs
-        dev = xc.device
-        g = grad_output.detach().to(torch.float32).contiguous()
-        gx = torch.empty_like(xc)
+        o = ctx.bufs
+        dev = o.x.device
+        g = _f32(grad_output, dev)
+        gx = torch.empty_like(o.x)
         targets = _CimModuleConv._grad_targets(ctx)
         lsq = ctx.lsq
         side = ctx.tail_stream if targets is not None else None
@@ -690,12 +776,12 @@ class _CimModuleConv(torch.autograd.Function):
                                      _lib.CIMQ_LSQ_ACCUMULATE_GRADS | (_lib.CIMQ_LSQ_DEFER_GW if side else 0),
                                      lsq.wprep)
         else:
-            gw = torch.empty_like(wc)
-            gaa = torch.empty(1, device=dev, dtype=torch.float32)
-            gaw = torch.empty(1, device=dev, dtype=torch.float32)
-            gac = None if ac is None else torch.empty_like(ac)
-        ws = torch.empty(max(ctx.sizes.bwd_workspace_bytes, 1), device=dev, dtype=torch.uint8)
+            gw, gaa, gaw, gac, _ = _param_grad_bufs(o)
+        ws = _ubuf(ctx.sizes.bwd_workspace_bytes, dev)
         lib = _lib.load()
+        # cimq_module_backward's arguments up to the workspace; cimq_module_backward_chain takes the same
+        args = [ctx.desc, lsq] + _ptrs(g, o.x, o.w, o.sa, o.sw, o.alpha, o.mask, o.sgn, o.ctx, gx, gw, gaa, gaw, gac,
+                                       ws)
         if targets is not None and side is None and CHAIN_EPILOGUES:
             # chained: this layer's epilogue waits in the pending list; the flush launches all of
             # them packed into a few launches
@@ -707,38 +793,25 @@ class _CimModuleConv(torch.autograd.Function):
                 torch.autograd.Variable._execution_engine.queue_callback(ch.flush)
                 ch.queued = True
             ch.stream = stream
-            _lib.check(lib.cimq_module_backward_chain(ctx.desc, lsq, g.data_ptr(), xc.data_ptr(), wc.data_ptr(),
-                                                      aa.data_ptr(), aw.data_ptr(),
-                                                      None if ac is None else ac.data_ptr(), bm.data_ptr(),
-                                                      sg.data_ptr(), cbuf.data_ptr(), gx.data_ptr(), gw.data_ptr(),
-                                                      gaa.data_ptr(), gaw.data_ptr(),
-                                                      None if gac is None else gac.data_ptr(), ws.data_ptr(),
-                                                      ch.pending, stream), "cimq_module_backward_chain")
-            ch.add((ws, cbuf, wc, ac, gw, gaa, gaw, gac, ctx.wprep_buf))
-            return (gx,) + (None,) * 21
-        _lib.check(lib.cimq_module_backward(ctx.desc, lsq, g.data_ptr(), xc.data_ptr(), wc.data_ptr(),
-                                            aa.data_ptr(), aw.data_ptr(), None if ac is None else ac.data_ptr(),
-                                            bm.data_ptr(), sg.data_ptr(), cbuf.data_ptr(), gx.data_ptr(),
-                                            gw.data_ptr(), gaa.data_ptr(), gaw.data_ptr(),
-                                            None if gac is None else gac.data_ptr(), ws.data_ptr(), _stream()),
-                   "cimq_module_backward")
+            _lib.check(lib.cimq_module_backward_chain(*args, ch.pending, stream), "cimq_module_backward_chain")
+            ch.add((ws, o.ctx, o.w, o.alpha, gw, gaa, gaw, gac, ctx.wprep_buf))
+            return _grads(_CimModuleConv._ARGS, x=gx)
+        _lib.check(lib.cimq_module_backward(*args, _stream()), "cimq_module_backward")
         if side is not None:
             # the parameter-gradient half (the grad_w kernel of the v7 layers, then the epilogue) on
             # the bucket's stream: the next layer's backward does not wait for it; grad_out / ws /
             # ctx stay alive until that stream is done with them
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
-                _lib.check(lib.cimq_module_backward_params(ctx.desc, lsq, g.data_ptr(), wc.data_ptr(),
-                                                           None if ac is None else ac.data_ptr(), cbuf.data_ptr(),
-                                                           gw.data_ptr(), gaa.data_ptr(), gaw.data_ptr(),
-                                                           None if gac is None else gac.data_ptr(), ws.data_ptr(),
-                                                           side.cuda_stream), "cimq_module_backward_params")
-            for t in (g, ws, cbuf, wc) + ((ac,) if ac is not None else ()) + \
-                    ((ctx.wprep_buf,) if ctx.wprep_buf is not None else ()):
-                t.record_stream(side)
+                _lib.check(lib.cimq_module_backward_params(ctx.desc, lsq, *_ptrs(g, o.w, o.alpha, o.ctx, gw, gaa, gaw,
+                                                                                 gac, ws), side.cuda_stream),
+                           "cimq_module_backward_params")
+            for t in (g, ws, o.ctx, o.w, o.alpha, ctx.wprep_buf):
+                if t is not None:
+                    t.record_stream(side)
         if targets is not None:
-            return (gx,) + (None,) * 21
-        return (gx, gw, gaa, gaw, gac) + (None,) * 17
+            return _grads(_CimModuleConv._ARGS, x=gx)
+        return _grads(_CimModuleConv._ARGS, x=gx, weight=gw, alpha_act=gaa, alpha_weight=gaw, alpha_cim=gac)
 
 
 def cim_module_conv(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding,
@@ -754,18 +827,10 @@ def cim_module_conv(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, 
     if inference_call(x, weight, alpha_act, alpha_weight, alpha_cim):
         return _CimModuleConv._call(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride,
                                     padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar,
-                                    nbits_alpha, stochastic, wprep, recompute, inference=True)[0]
+                                    nbits_alpha, stochastic, wprep, recompute, inference=True).out
     return _CimModuleConv.apply(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride,
                                 padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar,
                                 nbits_alpha, accumulate, stochastic, tail_stream, wprep, recompute)
-
-
-def _shift_module_descs(x_shape, weight, stride, padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, xbar,
-                        nbits_alpha):
-    desc, lsq = _module_descs(tuple(x_shape), weight, stride, padding, dilation, nbits_a, abitslice, nbits_w,
-                              wbitslice, 1.5, xbar, nbits_alpha, True, False)
-    desc.adc_variant = _lib.CIMQ_ADC_SHIFT_ROUND
-    return desc, lsq
 
 
 def module_shift_supported(x_shape, weight, stride, padding, dilation, nbits_a, abitslice, nbits_w, wbitslice,
@@ -775,8 +840,7 @@ def module_shift_supported(x_shape, weight, stride, padding, dilation, nbits_a, 
     torch and calls the unfused shift entry points."""
     if adcbits != 1.5 or len(x_shape) != 4:
         return False
-    dl = tuple(dilation) if isinstance(dilation, (tuple, list)) else (dilation, dilation)
-    if dl != (1, 1):
+    if _pair(dilation) != (1, 1):
         return False
     desc, _ = _shift_module_descs(x_shape, weight, stride, padding, dilation, nbits_a, abitslice, nbits_w, wbitslice,
                                   xbar, nbits_alpha)
@@ -793,70 +857,43 @@ class _CimModuleShiftConv(torch.autograd.Function):
     def _call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act, stride,
               padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, xbar, nbits_alpha, inference=False,
               wprep=None):
-        """cimq_module_shift_forward; returns (out, desc, lsq, sizes, bufs).  ``wprep`` (a forward-only call alone):
-        a WeightPrep from inference_weights, used if it was made for exactly this call."""
-        _require_device(x)
-        dev = x.device
-        B, C, H, W, O, KH, KW, st, pd = _geometry(x, weight, stride, padding, dilation)
-        desc, lsq = _shift_module_descs(tuple(x.shape), weight, st, pd, dilation, nbits_a, abitslice, nbits_w,
-                                        wbitslice, xbar, nbits_alpha)
-        keep = None
-        if inference:
-            desc.options |= _lib.CIMQ_OPT_INFERENCE
-            if (wprep is not None and wprep.key == _prep_key(desc, lsq, x.shape) and wprep.versions ==
-                    _versions(weight, alpha_act, alpha_weight, alpha_cim, binary_mask, beta_cim)):
-                lsq.wprep = wprep.buf.data_ptr()
-                keep = wprep.buf
-        sizes = _lib.query_sizes(desc)
-        xc = x.detach().to(torch.float32).contiguous()
-        wc = weight.detach().to(torch.float32).contiguous()
-        aa = alpha_act.detach().to(torch.float32).reshape(-1)[:1].contiguous()
-        aw = alpha_weight.detach().to(torch.float32).reshape(-1)[:1].contiguous()
-        ac = alpha_cim.detach().to(torch.float32).contiguous()
-        bc = beta_cim.detach().to(torch.float32).contiguous()
-        bm = binary_mask.to(device=dev, dtype=torch.int8).contiguous()
-        sg = signed_act.detach().to(device=dev, dtype=torch.float32).reshape(-1)[:1].contiguous()
-        Ho = (H + 2 * pd[0] - KH) // st[0] + 1
-        Wo = (W + 2 * pd[1] - KW) // st[1] + 1
-        out = torch.empty(B, O, Ho, Wo, device=dev, dtype=torch.float32)
-        cbuf = torch.empty(max(sizes.ctx_bytes, 1), device=dev, dtype=torch.uint8)
-        ws = torch.empty(max(sizes.fwd_workspace_bytes, 1), device=dev, dtype=torch.uint8)
-        _lib.check(_lib.load().cimq_module_shift_forward(desc, lsq, xc.data_ptr(), wc.data_ptr(), aa.data_ptr(),
-                                                         aw.data_ptr(), ac.data_ptr(), bc.data_ptr(), bm.data_ptr(),
-                                                         sg.data_ptr(), out.data_ptr(), cbuf.data_ptr(),
-                                                         ws.data_ptr(), _stream()), "cimq_module_shift_forward")
-        del keep
-        return out, desc, lsq, sizes, (xc, wc, aa, aw, ac, bc, bm, sg, cbuf)
+        """cimq_module_shift_forward; returns its _LayerCall.  ``wprep`` (a forward-only call alone): a WeightPrep
+        from inference_weights, used if it was made for exactly this call."""
+        c = _layer_call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act,
+                        (stride, padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, 1.5, xbar, nbits_alpha),
+                        wprep=wprep, inference=inference)
+        o = c.ops
+        _lib.check(_lib.load().cimq_module_shift_forward(
+            c.desc, c.lsq, *_ptrs(o.x, o.w, o.sa, o.sw, o.alpha, o.beta, o.mask, o.sgn, c.out, o.ctx, c.ws), _stream()),
+            "cimq_module_shift_forward")
+        return c
 
     @staticmethod
     def forward(ctx, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act, stride,
                 padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, xbar, nbits_alpha):
-        out, desc, lsq, sizes, bufs = _CimModuleShiftConv._call(
+        c = _CimModuleShiftConv._call(
             x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act, stride, padding,
             dilation, nbits_a, abitslice, nbits_w, wbitslice, xbar, nbits_alpha)
-        ctx.desc, ctx.lsq, ctx.sizes = desc, lsq, sizes
-        ctx.bufs = bufs
+        ctx.desc, ctx.lsq, ctx.sizes, ctx.bufs = c.desc, c.lsq, c.sizes, c.ops
         ctx.save_for_backward(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim)
-        return out
+        return c.out
+
+    _ARGS = _arg_names(forward.__func__)
 
     @staticmethod
     def backward(ctx, grad_output):
         ctx.saved_tensors  # noqa: B018 -- version check of x and the parameters
-        xc, wc, aa, aw, ac, bc, bm, sg, cbuf = ctx.bufs
-        dev = xc.device
-        g = grad_output.detach().to(torch.float32).contiguous()
-        gx = torch.empty_like(xc)
-        gw = torch.empty_like(wc)
-        gaa = torch.empty(1, device=dev, dtype=torch.float32)
-        gaw = torch.empty(1, device=dev, dtype=torch.float32)
-        gac = torch.empty_like(ac)
-        gbc = torch.empty_like(bc)
-        ws = torch.empty(max(ctx.sizes.bwd_workspace_bytes, 1), device=dev, dtype=torch.uint8)
+        o = ctx.bufs
+        dev = o.x.device
+        g = _f32(grad_output, dev)
+        gx = torch.empty_like(o.x)
+        gw, gaa, gaw, gac, gbc = _param_grad_bufs(o)
+        ws = _ubuf(ctx.sizes.bwd_workspace_bytes, dev)
         _lib.check(_lib.load().cimq_module_shift_backward(
-            ctx.desc, ctx.lsq, g.data_ptr(), xc.data_ptr(), wc.data_ptr(), aa.data_ptr(), aw.data_ptr(), ac.data_ptr(),
-            bc.data_ptr(), bm.data_ptr(), sg.data_ptr(), cbuf.data_ptr(), gx.data_ptr(), gw.data_ptr(), gaa.data_ptr(),
-            gaw.data_ptr(), gac.data_ptr(), gbc.data_ptr(), ws.data_ptr(), _stream()), "cimq_module_shift_backward")
-        return (gx, gw, gaa, gaw, gac, gbc) + (None,) * 11
+            ctx.desc, ctx.lsq, *_ptrs(g, o.x, o.w, o.sa, o.sw, o.alpha, o.beta, o.mask, o.sgn, o.ctx, gx, gw, gaa, gaw,
+                                      gac, gbc, ws), _stream()), "cimq_module_shift_backward")
+        return _grads(_CimModuleShiftConv._ARGS, x=gx, weight=gw, alpha_act=gaa, alpha_weight=gaw, alpha_cim=gac,
+                      beta_cim=gbc)
 
 
 def cim_module_shift_conv(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act, stride,
@@ -867,7 +904,7 @@ def cim_module_shift_conv(x, weight, alpha_act, alpha_weight, alpha_cim, beta_ci
     if inference_call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim):
         return _CimModuleShiftConv._call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask,
                                          signed_act, stride, padding, dilation, nbits_a, abitslice, nbits_w,
-                                         wbitslice, xbar, nbits_alpha, inference=True, wprep=wprep)[0]
+                                         wbitslice, xbar, nbits_alpha, inference=True, wprep=wprep).out
     return _CimModuleShiftConv.apply(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask,
                                      signed_act, stride, padding, dilation, nbits_a, abitslice, nbits_w, wbitslice,
                                      xbar, nbits_alpha)
@@ -938,70 +975,44 @@ def _conv_epilogue(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, s
     if out_quant is None and not keep_float:
         raise ValueError(f"{who}: keep_float=False needs out_quant")
     dev = x.device
-    B, C, H, W, O, KH, KW, st, pd = _geometry(x, weight, stride, padding, dilation)
-    if beta_cim is None:
-        desc, lsq = _module_descs(tuple(x.shape), weight, st, pd, dilation, nbits_a, abitslice, nbits_w, wbitslice,
-                                  adcbits, xbar, nbits_alpha, alpha_cim is not None, stochastic, recompute, True)
-    else:
-        desc, lsq = _shift_module_descs(tuple(x.shape), weight, st, pd, dilation, nbits_a, abitslice, nbits_w,
-                                        wbitslice, xbar, nbits_alpha)
-        desc.options |= _lib.CIMQ_OPT_INFERENCE
-    keep = None
-    if (wprep is not None and not stochastic and wprep.key == _prep_key(desc, lsq, x.shape)
-            and wprep.versions == _versions(weight, alpha_act, alpha_weight, alpha_cim, binary_mask, beta_cim)):
-        lsq.wprep = wprep.buf.data_ptr()
-        keep = wprep.buf
-    sizes = _lib.query_sizes(desc)
-    f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()  # noqa: E731
-    xc, wc = (x.detach().contiguous() if x_codes else f32(x)), f32(weight)
-    aa, aw = f32(alpha_act).reshape(-1)[:1].contiguous(), f32(alpha_weight).reshape(-1)[:1].contiguous()
-    ac = None if alpha_cim is None else f32(alpha_cim)
-    bc = None if beta_cim is None else f32(beta_cim)
-    bm = binary_mask.to(device=dev, dtype=torch.int8).contiguous()
-    sg = f32(signed_act).reshape(-1)[:1].contiguous()
-    sc, sh = f32(scale).reshape(-1), f32(shift).reshape(-1)
+    c = _layer_call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act,
+                    (stride, padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha),
+                    stochastic, wprep, recompute, True, x_codes, keep_float)
+    o, O = c.ops, c.out_shape[1]
+    sc, sh = _f32(scale, dev).reshape(-1), _f32(shift, dev).reshape(-1)
     if sc.numel() != O or sh.numel() != O:
         raise ValueError(f"{who}: scale / shift need {O} elements (one per output channel)")
-    Ho = (H + 2 * pd[0] - KH) // st[0] + 1
-    Wo = (W + 2 * pd[1] - KW) // st[1] + 1
     rs = None
     if residual is not None:
-        if tuple(residual.shape) != (B, O, Ho, Wo):
+        if tuple(residual.shape) != c.out_shape:
             raise ValueError(f"{who}: residual {tuple(residual.shape)} is not the output's "
-                             f"{(B, O, Ho, Wo)}")
-        rs = f32(residual)
-    out = torch.empty(B, O, Ho, Wo, device=dev, dtype=torch.float32) if keep_float else None
-    cbuf = torch.empty(max(sizes.ctx_bytes, 1), device=dev, dtype=torch.uint8)
-    ws = torch.empty(max(sizes.fwd_workspace_bytes, 1), device=dev, dtype=torch.uint8)
-    epi = _lib.make_epilogue(sc.data_ptr(), sh.data_ptr(), None if rs is None else rs.data_ptr(), relu)
+                             f"{c.out_shape}")
+        rs = _f32(residual, dev)
+    epi = _lib.make_epilogue(*_ptrs(sc, sh, rs), relu)
+    # the operands every one of the two entry points takes between its leading arguments and the epilogue
+    args = _ptrs(o.w, o.sa, o.sw, o.alpha, o.beta, o.mask, o.sgn) + [ctypes.byref(epi)] + _ptrs(c.out, o.ctx, c.ws) + \
+        [_stream()]
     if not codes:
-        _lib.check(_lib.load().cimq_module_forward_epilogue(
-            desc, lsq, xc.data_ptr(), wc.data_ptr(), aa.data_ptr(), aw.data_ptr(),
-            None if ac is None else ac.data_ptr(), None if bc is None else bc.data_ptr(), bm.data_ptr(),
-            sg.data_ptr(), ctypes.byref(epi), out.data_ptr(), cbuf.data_ptr(), ws.data_ptr(), _stream()),
-            "cimq_module_forward_epilogue")
-        del keep
-        return out
+        _lib.check(_lib.load().cimq_module_forward_epilogue(c.desc, c.lsq, o.x.data_ptr(), *args),
+                   "cimq_module_forward_epilogue")
+        return c.out
     oq = oa = None
     if out_quant is None:
-        io = _lib.make_act_codes(x_codes=xc.data_ptr() if x_codes else None)
+        io = _lib.make_act_codes(x_codes=o.x.data_ptr() if x_codes else None)
     else:
         o_alpha, o_gs, o_qp = out_quant
         oa = o_alpha  # (a layer's own fp32 parameter on this device is read where it is)
         if not (oa.dtype == torch.float32 and oa.device == dev and oa.is_contiguous()):
-            oa = f32(o_alpha).reshape(-1)[:1].contiguous()
-        oq = torch.empty(B, O, Ho, Wo, device=dev, dtype=torch.uint8)
-        io = _lib.make_act_codes(xc.data_ptr() if x_codes else None, oq.data_ptr(), oa.data_ptr(), float(o_gs),
+            oa = _one(o_alpha, dev)
+        oq = torch.empty(c.out_shape, device=dev, dtype=torch.uint8)
+        io = _lib.make_act_codes(o.x.data_ptr() if x_codes else None, oq.data_ptr(), oa.data_ptr(), float(o_gs),
                                  float(o_qp), not keep_float)
-    _lib.check(_lib.load().cimq_module_forward_codes(
-        desc, lsq, ctypes.byref(io), None if x_codes else xc.data_ptr(), wc.data_ptr(), aa.data_ptr(), aw.data_ptr(),
-        None if ac is None else ac.data_ptr(), None if bc is None else bc.data_ptr(), bm.data_ptr(), sg.data_ptr(),
-        ctypes.byref(epi), None if out is None else out.data_ptr(), cbuf.data_ptr(), ws.data_ptr(), _stream()),
-        "cimq_module_forward_codes")
-    del keep
+    _lib.check(_lib.load().cimq_module_forward_codes(c.desc, c.lsq, ctypes.byref(io),
+                                                     None if x_codes else o.x.data_ptr(), *args),
+               "cimq_module_forward_codes")
     if oq is None:
-        return out
-    return (out, oq) if keep_float else oq
+        return c.out
+    return (c.out, oq) if keep_float else oq
 
 
 def net_sizes(net):
@@ -1026,24 +1037,17 @@ def alpha_cim_init(x, w_q, sa, sw, binary_mask, signed_act, stride, padding, nbi
     """First-step alpha_cim initialisation on the device (lsq.py:557-563, 35-87)."""
     _require_device(x)
     dev = x.device
-    B, C, H, W, O, KH, KW, st, pd = _geometry(x, w_q, stride, padding, (1, 1))
+    B, C, H, W, O, KH, KW, st, pd, _, _ = _geometry(x, w_q, stride, padding, (1, 1))
     desc = _lib.make_desc(B, C, H, W, O, KH, KW, st, pd, xbar, nbits_w, nbits_a, wbitslice, abitslice,
                           adcbits, _lib.CIMQ_INPUT_RAW_LSQ, float(2 ** nbits_a - 1))
     sizes = _lib.query_sizes(desc)
     nbw, nba = int(nbits_w / wbitslice), int(nbits_a / abitslice)
     out = torch.empty(1, num_xbars, nbw, nba, 1, O, device=dev, dtype=torch.float32)
-    cbuf = torch.empty(max(sizes.ctx_bytes, 1), device=dev, dtype=torch.uint8)
-    ws = torch.empty(max(sizes.fwd_workspace_bytes, 1), device=dev, dtype=torch.uint8)
-    xc = x.detach().to(torch.float32).contiguous()
-    wq = w_q.detach().to(torch.float32).contiguous()
-    sa_ = sa.detach().reshape(-1)[:1].contiguous()
-    sw_ = sw.detach().reshape(-1)[:1].contiguous()
-    bm = binary_mask.to(device=dev, dtype=torch.int8).contiguous()
-    sg = signed_act.detach().to(device=dev, dtype=torch.float32).reshape(-1)[:1].contiguous()
-    lib = _lib.load()
-    _lib.check(lib.cimq_alpha_init(desc, xc.data_ptr(), wq.data_ptr(), sa_.data_ptr(), sw_.data_ptr(),
-                                   bm.data_ptr(), sg.data_ptr(), out.data_ptr(), cbuf.data_ptr(),
-                                   ws.data_ptr(), _stream()), "cimq_alpha_init")
+    o = _operands(x, w_q, sa, sw, None, None, binary_mask, signed_act)
+    o.ctx = _ubuf(sizes.ctx_bytes, dev)
+    ws = _ubuf(sizes.fwd_workspace_bytes, dev)
+    _lib.check(_lib.load().cimq_alpha_init(desc, *_ptrs(o.x, o.w, o.sa, o.sw, o.mask, o.sgn, out, o.ctx, ws),
+                                           _stream()), "cimq_alpha_init")
     return out
 
 
@@ -1056,32 +1060,21 @@ def debug_partial_sums(x_q, w_q, conv_stride, conv_padding, act_bits, act_bit_sl
     draws the stochastic ADC of lsq.py:205-221."""
     _require_device(x_q)
     dev = x_q.device
-    B, C, H, W, O, KH, KW, st, pd = _geometry(x_q, w_q, conv_stride, conv_padding, (1, 1))
+    B, C, H, W, O, KH, KW, st, pd, Ho, Wo = _geometry(x_q, w_q, conv_stride, conv_padding, (1, 1))
     desc = _lib.make_desc(B, C, H, W, O, KH, KW, st, pd, arr, weight_bits, act_bits, weight_bit_slice,
                           act_bit_slice, adc_bits, _lib.CIMQ_INPUT_XQ,
                           adc_variant=_lib.CIMQ_ADC_STOCHASTIC if stochastic else _lib.CIMQ_ADC_LIBRARY,
                           seed=(stochastic_seed() if seed is None else seed) if stochastic else 0)
     sizes = _lib.query_sizes(desc)
     nbw, nba = int(weight_bits / weight_bit_slice), int(act_bits / act_bit_slice)
-    T = int(math.ceil(C * KH * KW / arr))
-    Ho = (H + 2 * pd[0] - KH) // st[0] + 1
-    Wo = (W + 2 * pd[1] - KW) // st[1] + 1
+    T = num_xbars(C, (KH, KW), arr)
     out = torch.empty(B, Ho * Wo, O, device=dev, dtype=torch.float32)
     ps = torch.zeros(B, T, nbw, nba, Ho * Wo, O, device=dev, dtype=torch.int32)
     adc = torch.zeros(B, T, nbw, nba, Ho * Wo, O, device=dev, dtype=torch.float32)
-    cbuf = torch.empty(max(sizes.ctx_bytes, 1), device=dev, dtype=torch.uint8)
-    xq = x_q.detach().float().contiguous()
-    wq = w_q.detach().float().contiguous()
-    sa = _f32(act_scaling_factor, dev).reshape(-1)[:1].contiguous()
-    sw = _f32(weight_scaling_factor, dev).reshape(-1)[:1].contiguous()
-    bm = binary_mask.to(device=dev, dtype=torch.int8).contiguous()
-    sg = _f32(signed_act, dev).reshape(-1)[:1].contiguous()
-    al = None if alpha_cim is None else _f32(alpha_cim, dev)
-    lib = _lib.load()
-    _lib.check(lib.cimq_debug_partial_sums(desc, xq.data_ptr(), wq.data_ptr(), sa.data_ptr(), sw.data_ptr(),
-                                           None if al is None else al.data_ptr(), bm.data_ptr(), sg.data_ptr(),
-                                           out.data_ptr(), ps.data_ptr(), adc.data_ptr(), cbuf.data_ptr(),
-                                           _stream()), "cimq_debug_partial_sums")
+    o = _operands(x_q, w_q, act_scaling_factor, weight_scaling_factor, alpha_cim, None, binary_mask, signed_act)
+    o.ctx = _ubuf(sizes.ctx_bytes, dev)
+    _lib.check(_lib.load().cimq_debug_partial_sums(desc, *_ptrs(o.x, o.w, o.sa, o.sw, o.alpha, o.mask, o.sgn, out, ps,
+                                                                adc, o.ctx), _stream()), "cimq_debug_partial_sums")
     return out, ps, adc
 
 
@@ -1095,33 +1088,28 @@ def debug_state_codes(out):
         ctx = ctx.next_functions[0][0] if ctx.next_functions else None
     if ctx is None:
         raise RuntimeError("no libcimq forward context behind this tensor")
-    d = ctx.desc
-    cbuf = ctx.bufs[-1]
+    d, o = ctx.desc, ctx.bufs
+    dev = o.ctx.device
     nbw, nba = int(d.bits_w / d.bs_w), int(d.bits_a / d.bs_a)
     T = num_xbars(d.in_channels, (d.kernel_h, d.kernel_w), d.xbar)
-    Ho = (d.in_h + 2 * d.pad_h - d.kernel_h) // d.stride_h + 1
-    Wo = (d.in_w + 2 * d.pad_w - d.kernel_w) // d.stride_w + 1
+    Ho, Wo = out_hw(d)
     shape = (d.batch, T, nbw, nba, Ho * Wo, d.out_channels)
-    code = torch.empty(shape, device=cbuf.device, dtype=torch.int8)
-    passed = torch.empty(shape, device=cbuf.device, dtype=torch.uint8)
+    code = torch.empty(shape, device=dev, dtype=torch.int8)
+    passed = torch.empty(shape, device=dev, dtype=torch.uint8)
     if getattr(ctx, "module_path", False) and _lib.module_route(d)[1] == _lib.CIMQ_ROUTE_R6:
         # a module layer whose backward recomputes the partial sums: its forward left no state words, so the
         # codes come from the recomputing backward's own code path (cimq_debug_recompute_codes)
-        xc, sg = ctx.bufs[0], ctx.bufs[6]
-        st = torch.empty(T * d.batch * Ho * Wo * d.out_channels * 4, device=cbuf.device, dtype=torch.uint8)
-        _lib.check(_lib.load().cimq_debug_recompute_codes(d, xc.data_ptr(), sg.data_ptr(), cbuf.data_ptr(),
-                                                          st.data_ptr(), code.data_ptr(), passed.data_ptr(),
-                                                          _stream()), "cimq_debug_recompute_codes")
+        st = torch.empty(T * d.batch * Ho * Wo * d.out_channels * 4, device=dev, dtype=torch.uint8)
+        _lib.check(_lib.load().cimq_debug_recompute_codes(d, *_ptrs(o.x, o.sgn, o.ctx, st, code, passed), _stream()),
+                   "cimq_debug_recompute_codes")
         return code, passed
-    _lib.check(_lib.load().cimq_debug_state_codes(d, cbuf.data_ptr(), code.data_ptr(), passed.data_ptr(), _stream()),
-               "cimq_debug_state_codes")
+    _lib.check(_lib.load().cimq_debug_state_codes(d, *_ptrs(o.ctx, code, passed), _stream()), "cimq_debug_state_codes")
     return code, passed
 
 
 def logical_macs(B, C, H, W, O, KH, KW, stride, padding) -> int:
     """ptflops convention B*Ho*Wo*O*C*KH*KW (utils/ptflops/flops_counter.py:314-318)."""
-    Ho = (H + 2 * padding[0] - KH) // stride[0] + 1
-    Wo = (W + 2 * padding[1] - KW) // stride[1] + 1
+    Ho, Wo = conv_out_hw(H, W, KH, KW, stride, padding)
     return B * Ho * Wo * O * C * KH * KW
 
 

@@ -45,6 +45,13 @@ def _bn_versions(bn):
                  for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
 
 
+def _out_shape(conv, in_shape):
+    """NCHW output shape of the CiM conv ``conv`` for input shape ``in_shape``."""
+    from ..functional import conv_out_hw
+    return (in_shape[0], conv.out_channels) + conv_out_hw(in_shape[2], in_shape[3], *conv.weight.shape[2:],
+                                                          conv.stride, conv.padding)
+
+
 def assign_slots(steps):
     """Activation slots by liveness.  ``steps``: the plan in execution order, each ``(reads, write)`` -- the values
     the step reads and the one it writes (None: the head).  Returns ``({value: slot}, n_slots)``: a value keeps its
@@ -122,11 +129,11 @@ class _NetPlan:
                 raise _NoPlan("parameters must be contiguous fp32 on the input's device")
             if conv.binary_mask.device != dev:
                 conv.binary_mask = conv.binary_mask.to(dev)
-            desc, lsq = CF._prepare_descs(conv, shape, inference=True)
+            desc, lsq = CF.module_descs(conv, shape, inference=True)
             wp = conv._inf_prep = CF.inference_weights(conv, shape, conv._inf_prep)
             lsq.wprep = wp.buf.data_ptr()
             sizes = _lib.query_sizes(desc)
-            ctx = torch.empty(max(sizes.ctx_bytes, 1), device=dev, dtype=torch.uint8)
+            ctx = torch.empty(max(sizes.module_ctx_bytes, 1), device=dev, dtype=torch.uint8)
             bm = conv.binary_mask.to(device=dev, dtype=torch.int8).contiguous()
             sg = conv.signed_act.detach().to(device=dev, dtype=torch.float32).reshape(-1)[:1].contiguous()
             scale, shift = fused.tables(bn)
@@ -146,9 +153,7 @@ class _NetPlan:
             L.ctx = ctx.data_ptr()
             if i > 0 and blk is None:
                 block_shape = shape  # a block's first conv: its input feeds the block's shortcut too
-            ho = (shape[2] + 2 * conv.padding[0] - conv.weight.shape[2]) // conv.stride[0] + 1
-            wo = (shape[3] + 2 * conv.padding[1] - conv.weight.shape[3]) // conv.stride[1] + 1
-            out_shape = (shape[0], conv.out_channels, ho, wo)
+            out_shape = _out_shape(conv, shape)
             if blk is not None:  # the shortcut: the block's input (value i - 2) as a view
                 L.res_slot = slot_of[i - 2]
                 if isinstance(blk.shortcut, PadShortcut):
@@ -381,10 +386,7 @@ class FusedEval(nn.Module):
                 key = (i, tuple(src.shape), src.device)
                 probe = self._probe.get(key)
                 if probe is None:
-                    ho = (src.shape[2] + 2 * conv.padding[0] - conv.weight.shape[2]) // conv.stride[0] + 1
-                    wo = (src.shape[3] + 2 * conv.padding[1] - conv.weight.shape[3]) // conv.stride[1] + 1
-                    probe = torch.empty(1, dtype=torch.uint8, device=src.device).expand(src.shape[0], conv.out_channels,
-                                                                                        ho, wo)
+                    probe = torch.empty(1, dtype=torch.uint8, device=src.device).expand(_out_shape(conv, src.shape))
                     self._probe[key] = probe
                 hand = conv.codes_ready(src)[1] and nxt.codes_ready(probe)[0]
             if not hand:

@@ -238,10 +238,12 @@ def test_skip_tail_then_backward_tail_equals_plain_backward(cuda_device, recompu
     lib = L.load()
 
     def run(split):
-        out, desc, lsq, sizes, (xc, wc, aa, aw, ac, bm, sg, cbuf), _ = _CimModuleConv._call(
+        c = _CimModuleConv._call(
             x, m.weight, m.alpha_act, m.alpha_weight, m.alpha_cim, m.binary_mask, m.signed_act, m.stride, m.padding,
             m.dilation, m.nbits_a, m.abitslice, m.nbits_w, m.wbitslice, m.adcbits, m.xbar, m.nbits_alpha,
             recompute=recompute)
+        desc, lsq, sizes, o = c.desc, c.lsq, c.sizes, c.ops
+        xc, wc, aa, aw, ac, bm, sg, cbuf = o.x, o.w, o.sa, o.sw, o.alpha, o.mask, o.sgn, o.ctx
         route = (ctypes.c_int * 3)()
         L.check(lib.cimq_module_route(desc, route), "cimq_module_route")
         assert tuple(L.ROUTE_NAMES[v] for v in route) == (("fwd5", "r6", "r6") if recompute else ("fwd5", "gx5", "gw5"))

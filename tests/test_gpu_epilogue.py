@@ -127,13 +127,7 @@ def _raw_epi(m, x, scale, shift, res, relu, out=None):
     """cimq_module_forward_epilogue through ctypes on module m's parameters"""
     F, L = _F(), _L()
     dev = x.device
-    if m.adc_shift:
-        desc, lsq = F._shift_module_descs(tuple(x.shape), m.weight, m.stride, m.padding, m.dilation, m.nbits_a,
-                                          m.abitslice, m.nbits_w, m.wbitslice, m.xbar, m.nbits_alpha)
-    else:
-        desc, lsq = F._module_descs(tuple(x.shape), m.weight, m.stride, m.padding, m.dilation, m.nbits_a, m.abitslice,
-                                    m.nbits_w, m.wbitslice, m.adcbits, m.xbar, m.nbits_alpha, m.alpha_cim is not None,
-                                    False)
+    desc, lsq = F.module_descs(m, tuple(x.shape))
     desc.options = INF
     sizes = L.query_sizes(desc)
     B, O = x.shape[0], m.weight.shape[0]

@@ -129,13 +129,7 @@ def _raw(m, x, options, ctx_bytes=None, fill=None, variant=None, seed=0):
     descriptor; returns (out, ctx buffer, sizes, desc, lsq, argument tensors)"""
     F, L = _F(), _L()
     dev = x.device
-    if m.adc_shift:
-        desc, lsq = F._shift_module_descs(tuple(x.shape), m.weight, m.stride, m.padding, m.dilation, m.nbits_a,
-                                          m.abitslice, m.nbits_w, m.wbitslice, m.xbar, m.nbits_alpha)
-    else:
-        desc, lsq = F._module_descs(tuple(x.shape), m.weight, m.stride, m.padding, m.dilation, m.nbits_a, m.abitslice,
-                                    m.nbits_w, m.wbitslice, m.adcbits, m.xbar, m.nbits_alpha, m.alpha_cim is not None,
-                                    False)
+    desc, lsq = F.module_descs(m, tuple(x.shape))
     desc.options = options
     if variant is not None:
         desc.adc_variant = variant

@@ -69,13 +69,7 @@ class _Plan:
     def layer(self, m, in_shape, scale, shift, relu, in_slot, out_slot, out_mode=1, consumer=0, in_codes=0,
               res_slot=-1, res_c0=0, res_stride=1):
         F, L = _F(), _L()
-        if m.adc_shift:
-            desc, lsq = F._shift_module_descs(tuple(in_shape), m.weight, m.stride, m.padding, m.dilation, m.nbits_a,
-                                              m.abitslice, m.nbits_w, m.wbitslice, m.xbar, m.nbits_alpha)
-        else:
-            desc, lsq = F._module_descs(tuple(in_shape), m.weight, m.stride, m.padding, m.dilation, m.nbits_a,
-                                        m.abitslice, m.nbits_w, m.wbitslice, m.adcbits, m.xbar, m.nbits_alpha,
-                                        m.alpha_cim is not None, False)
+        desc, lsq = F.module_descs(m, tuple(in_shape))
         desc.options = INF
         sizes = L.query_sizes(desc)
         ctx = torch.empty(max(sizes.ctx_bytes, 1), device=self.dev, dtype=torch.uint8)

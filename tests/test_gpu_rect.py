@@ -126,7 +126,7 @@ def _assert_route(c, m, x_shape):
     L = _L()
     want = c["route"]
     assert route_names(L, make_desc(L, c)) == want
-    assert route_names(L, F._prepare_descs(m, tuple(x_shape))[0]) == want
+    assert route_names(L, F.module_descs(m, tuple(x_shape))[0]) == want
 
 
 @pytest.mark.parametrize("idx", range(len(MODULE_CASES)), ids=[case_id(c) for c in MODULE_CASES])

@@ -356,7 +356,7 @@ def _two_stacks(dev, overlap):
         _step(layers, bucket, xs, gs, False)  # the initialising step (torch path)
         _step(layers, bucket, xs, gs, False)  # the first library step records the input shapes
     for m, x in zip(la, xs):
-        assert route_names(_L(), F._prepare_descs(m, tuple(x.shape))[0]) == V7
+        assert route_names(_L(), F.module_descs(m, tuple(x.shape))[0]) == V7
     return la, ba, lb, bb
 
 
@@ -417,7 +417,7 @@ def test_harness_trains_a_4bit_prototxt(cuda_device, tmp_path, capsys):
     for n, m in convs:
         if m.kernel_size == (3, 3) and m.stride == (1, 1):
             h = sizes[m.in_channels]
-            assert route_names(_L(), F._prepare_descs(m, (64, m.in_channels, h, h))[0]) == V7, n
+            assert route_names(_L(), F.module_descs(m, (64, m.in_channels, h, h))[0]) == V7, n
     best = train.main(["--hp", str(hp), "--max-steps", "2", "--max-val-steps", "1"])
     out = capsys.readouterr().out
     losses = [float(l.split("loss ")[1].split()[0]) for l in out.splitlines() if l.startswith("Epoch [")]

@@ -90,7 +90,7 @@ def measure(args):
         ho = bench.out_hw(h, s)
         g = torch.randn(args.batch, o, ho, ho, device=dev) / math.sqrt(args.batch * o * ho * ho)
         m(x).backward(g)  # the first step: the step sizes and alpha_cim from the data (torch path)
-        route = tuple(L.ROUTE_NAMES[v] for v in L.module_route(F._prepare_descs(m, tuple(x.shape))[0]))
+        route = tuple(L.ROUTE_NAMES[v] for v in L.module_route(F.module_descs(m, tuple(x.shape))[0]))
 
         def fb():
             m(x).backward(g)
