@@ -61,6 +61,8 @@ EXPORTED_SYMBOLS = (
     "cimq_module_prepare_shift",
     "cimq_module_shift_supported",
     "cimq_module_route",
+    "cimq_w4a4_eval_abi",
+    "cimq_module_forward_form",
     "cimq_module_shift_forward",
     "cimq_module_shift_backward",
     "cimq_module_forward_epilogue",
@@ -260,6 +262,13 @@ def _bind(lib):
     lib.cimq_module_shift_supported.argtypes = [ctypes.POINTER(ConvDesc)]
     lib.cimq_module_route.restype = ctypes.c_int
     lib.cimq_module_route.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_int)]
+    # (availability symbols of this library; an older one given by CIMQ_LIB_PATH -- the tools that time this tree
+    # against its parent load one -- has neither, and stays loadable without them)
+    if hasattr(lib, "cimq_w4a4_eval_abi"):
+        lib.cimq_w4a4_eval_abi.restype = ctypes.c_int
+        lib.cimq_w4a4_eval_abi.argtypes = []
+        lib.cimq_module_forward_form.restype = ctypes.c_int
+        lib.cimq_module_forward_form.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_int)]
     lib.cimq_module_shift_forward.restype = ctypes.c_int
     lib.cimq_module_shift_forward.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(LsqDesc)] + [_VP] * 12
     lib.cimq_module_shift_backward.restype = ctypes.c_int
@@ -428,6 +437,14 @@ def module_route(desc: ConvDesc):
     r = (ctypes.c_int * 3)()
     check(load().cimq_module_route(ctypes.byref(desc), r), "cimq_module_route")
     return tuple(r)
+
+
+def module_forward_form(desc: ConvDesc):
+    """(state format of the forward family: 0 / 2 / 3 / 4 / 8, 1 where the module forward quantises the activation in
+    its own row staging) for ``desc`` -- cimq_module_forward_form (cimq_w4a4_eval_abi() == 1)."""
+    f = (ctypes.c_int * 2)()
+    check(load().cimq_module_forward_form(ctypes.byref(desc), f), "cimq_module_forward_form")
+    return tuple(f)
 
 
 def query_sizes(desc: ConvDesc) -> Sizes:

@@ -744,6 +744,19 @@ int cimq_module_route(const cimq_conv_desc* d, int* route) {
   return CIMQ_OK;
 }
 
+int cimq_w4a4_eval_abi(void) { return 1; }
+
+int cimq_module_forward_form(const cimq_conv_desc* d, int form[2]) {
+  Geo g;
+  CIMQ_TRY(make_geo(d, &g));
+  if (!form) return fail(CIMQ_EINVAL, "null form");
+  if (g.input_kind != CIMQ_INPUT_RAW_LSQ) return fail(CIMQ_EINVAL, "module entry points take the raw activation");
+  const Route r = route_of(module_form(g));
+  form[0] = r.cst;
+  form[1] = r.actq ? 1 : 0;
+  return CIMQ_OK;
+}
+
 int cimq_module_shift_supported(const cimq_conv_desc* d) {
   Geo g;
   if (make_geo(d, &g) != CIMQ_OK) return 0;

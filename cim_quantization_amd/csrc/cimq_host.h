@@ -350,9 +350,10 @@ inline void gw_pitches(const Geo& g, V7& v) {
 }
 
 // w4a4 in 1-bit slices trains on the v7 pair from 8-byte state words (ST_V7X2): the library ADC's training calls
-// only.  A forward-only call keeps the per-k family -- its route, its kernel instances and its sizes are what they
-// were before the format existed -- and so does every other ADC variant (their backward is the general one, which
-// reads no state words) and every four-slice layer of wider slices ("8/8 in 2/2")
+// only.  A forward-only call fails the v7 plan -- its route names and its sizes are what they were before the format
+// existed; v7_w44_eval below gives it the format's stateless forward -- and every other ADC variant keeps the per-k
+// family (their backward is the general one, which reads no state words), as does every four-slice layer of wider
+// slices ("8/8 in 2/2")
 inline bool v7_w44(const Geo& g) {
   return g.NBP == 4 && g.nbw == 4 && g.nba == 4 && g.bsw == 1 && g.bsa == 1 && g.variant == VAR_LIBRARY &&
          !g.inference;
@@ -443,6 +444,19 @@ inline Plan7 v7_plan_compute(const Geo& g) {
   return p;
 }
 inline Plan7 v7_plan(const Geo& g) { return memo_geo<Plan7, v7_plan_compute>(g); }
+
+// v7_w44's forward-only twin: a CIMQ_OPT_INFERENCE descriptor of such a layer whose training form the v7 plan
+// takes -- the plan's shape gates asked of the same geometry without the inference bit, so a shape runs the
+// format's forward here exactly where its training call does -- with the raw activation (the module entry points:
+// the stateless form quantises in its row staging; a Function call hands over x_q and keeps the per-k family).
+// It moves the forward's kernel instance only (Route::cst / fst / actq): v7_plan itself still fails for the
+// descriptor, and with it every layout and route name stays the per-k family's
+inline bool v7_w44_eval(const Geo& g) {
+  if (!g.inference || g.input_kind != CIMQ_INPUT_RAW_LSQ) return false;
+  Geo t = g;
+  t.inference = 0;
+  return v7_w44(t) && v7_plan(t).ok;
+}
 
 // ---- the fused backward (cimq_fused.hip): one kernel per stride-1 3x3 w2a2 / w3a3 layer ----
 struct Plan9 {
@@ -630,12 +644,14 @@ inline bool v7_bwd(const Geo& g) {
 // no later kernel reads the forward slice words), 4-byte slice words, the prologue's word table applicable, and
 // not the first conv (whose backward re-reads the forward words) or a shift layer in training (its statistics
 // kernel does; a forward-only shift layer of the fused shift path has no such reader).  A w4a4 training forward
-// (v7_w44) keeps the prologue's pass: its no-grad twin runs the per-k family, which has no staged quantiser
+// (v7_w44) keeps the prologue's pass: the staged quantiser is its forward-only twin's (v7_w44_eval), which has no
+// backward and so stands where v7_bwd does for the others
 inline bool fwd_actq_ok(const Geo& g) {
   if (tune("ACTQ", 1) == 0 || v7_w44(g)) return false;
   const bool adc_ok = g.variant == VAR_LIBRARY || (g.inference && g.variant == VAR_SHIFT_ROUND && shift_stats_ok(g));
   return g.input_kind == CIMQ_INPUT_RAW_LSQ && g.NBP == 4 && adc_ok && g.W % 4 == 0 &&
-         g.P % 64 == 0 && g.lsq_qp >= 0.f && g.lsq_qp < 255.f && v3_plan(g).ok && v7_bwd(g) && !c1_plan(g).ok;
+         g.P % 64 == 0 && g.lsq_qp >= 0.f && g.lsq_qp < 255.f && v3_plan(g).ok && (v7_bwd(g) || v7_w44_eval(g)) &&
+         !c1_plan(g).ok;
 }
 
 // ---- the w3a3 forward on the slice-planar patch (cimq_fwd5.hip) ----
@@ -966,6 +982,7 @@ inline Route route_compute(const Geo& g) {
     r.gx = r.gw = CIMQ_ROUTE_NONE;
     r.state = ST_NONE;
     r.st_bytes = 0;
+    if (v7_w44_eval(g)) r.cst = 4;  // (the v7 plan fails for the descriptor: the format's stateless forward alone)
     if (r.cst != 0 && r.fst == FwdState::WRITE) r.fst = FwdState::NONE;  // (CST 0 writes no state as it is)
     r.codes = r.lsq_fused = r.gw_own = r.gxw5 = r.wgx = r.wcy = r.wg5 = r.wx6 = false;
   }
@@ -1023,8 +1040,9 @@ inline CtxLayout ctx_layout_compute(const Geo& g) {
   L.lsq_scal = o; o = align256(o + 16 * 4);
   L.wbytes = o;
   // forward slice bytes (none in a forward-only call whose forward quantises the activation itself; a shift layer
-  // keeps the region, unwritten there: its ctx_bytes are what they were before its forward staged the quantiser)
-  L.xcode = o; o = align256(o + ((g.inference && r.actq && g.variant == VAR_LIBRARY) ? (size_t)0 : (size_t)g.Nin * g.NBP));
+  // keeps the region, unwritten there: its ctx_bytes are what they were before its forward staged the quantiser,
+  // and so does a w4a4 layer on the stateless word-pair forward, v7_w44_eval)
+  L.xcode = o; o = align256(o + ((g.inference && r.actq && g.variant == VAR_LIBRARY && !v7_w44_eval(g)) ? (size_t)0 : (size_t)g.Nin * g.NBP));
   if (g.inference) {
     // forward only (CIMQ_OPT_INFERENCE): the ctx ends here -- no backward slice words, no code table, no state;
     // their offsets point at the end and nothing is written through them

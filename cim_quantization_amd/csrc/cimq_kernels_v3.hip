@@ -28,10 +28,11 @@ namespace cimq {
 // st32[(i*M + m)*O + o], bits 3*(k*nba + j) + {0: STE pass, 1: code != 0, 2: code < 0}; 0: the per-k words.
 // CST > 0 also fixes nbw = nba = CST at compile time: the ternary-threshold path then runs
 // fully unrolled (every slice pair's MFMAs issued before its ADC work, state bits shifted in).
-// CST 4 (w4a4 in 1-bit slices, training only): 16 pairs in a uint2 per (i, m, o) at st64[(i*M + m)*O + o] -- .x the
-// pairs of weight slices 0-1 as above (kj 0..7), .y those of slices 2-3 at 3*(kj - 8).  Its unrolled path adds the
-// pairs to the output in CST 0's order (k, then j, ascending): the forward-only calls of such a layer run CST 0,
-// and the two forwards agree bit for bit.
+// CST 4 (w4a4 in 1-bit slices): 16 pairs in a uint2 per (i, m, o) at st64[(i*M + m)*O + o] -- .x the pairs of
+// weight slices 0-1 as above (kj 0..7), .y those of slices 2-3 at 3*(kj - 8).  Its unrolled path adds the pairs to
+// the output in CST 0's order (k, then j, ascending), so it agrees with CST 0 bit for bit.  Its stateless form
+// (ST NONE: the forward-only module calls, v7_w44_eval) is that path without the words, their bits and the ballots
+// that feed only them, with the activation quantiser in the row staging as in the CST 2 / 3 stateless instances.
 // ST: what becomes of those words (FwdState).  M: what the store does (FwdMode) -- the epilogue ep on the float4
 // about to be stored (NCHW only); with codes, the row staging reads the input's codes (ep.xq: bytes straight into
 // the word table, stage_rows_qc) or quantises fp32 x as before, and the store writes the float4, the consumer's
@@ -51,7 +52,8 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
   constexpr bool INF = ST == FwdState::NONE;
   static_assert(CST == 0 || CST == 2 || CST == 3 || CST == 4 || CST == 8,
                 "state formats: per-k words, w2a2, w3a3, w4a4 word pairs, w8a8 planes");
-  static_assert(CST != 4 || (NBP == 4 && WST && M == FwdMode::TRAIN), "w4a4 word pairs: the training forward only");
+  static_assert(CST != 4 || (NBP == 4 && ((WST && M == FwdMode::TRAIN) || INF)),
+                "w4a4 word pairs: the training forward writes them, every forward-only mode is stateless");
   static_assert(CST != 0 || WST, "CST 0 writes no state words as it is: one form, spelled WRITE, for every call");
   static_assert(ST != FwdState::RECOMPUTE || CST == 8, "the recomputing backward is the w8a8 first conv's");
   static_assert(M != FwdMode::TRAIN || !INF, "a training instance leaves the backward its words, or recomputes them");
@@ -198,9 +200,11 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
   const bool sgn_q = actq && *sgn_p != 0.f;
   // (a compile-time slice count also fixes 1-bit activation slices: CST counts slices, whatever their width, so
   // wider ones take the runtime digit loop; g.bsa is uniform, and either call syncs the block)
+  // (CST 4 stages the quantiser in its stateless form only: the training instance keeps the runtime table)
+  constexpr int LQ = (CST == 2 || CST == 3 || (CST == 4 && INF)) ? CST : 0;
   if (actq) {
-    if ((CST == 2 || CST == 3) && g.bsa == 1)
-      act_lut_build_q<(CST == 2 || CST == 3) ? CST : 0>(g, sa_q, sgn_q, alut);
+    if (LQ > 0 && g.bsa == 1)
+      act_lut_build_q<LQ>(g, sa_q, sgn_q, alut);
     else
       act_lut_build_q<0>(g, sa_q, sgn_q, alut);
   }
@@ -313,6 +317,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
                     const uint64_t mhi = __builtin_amdgcn_ballot_w64(ps[j][r] >= pv.x);
                     const uint64_t mlo = __builtin_amdgcn_ballot_w64(ps[j][r] <= pv.y);
                     acc[ob][r] += adc3(cf, mhi, mlo);
+                    if constexpr (!WST) continue;  // (no state words -- and none of their bits)
                     const uint64_t mps = __builtin_amdgcn_ballot_w64((unsigned)(ps[j][r] - pv.z) <= (unsigned)pv.w);
                     const uint64_t mnz = mhi | mlo;
                     sh[ob][r][k >> 1] = shin(shin(shin(sh[ob][r][k >> 1], mps), mnz), mlo);
@@ -325,6 +330,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
           for (int a = 0; a < OBM; ++a)
 #pragma unroll
             for (int c = 0; c < 4; ++c) {
+              if constexpr (!WST) continue;
               stc[a][c] = __builtin_bitreverse32(sh[a][c][0]) >> 8;
               stc2[CST == 4 ? a : 0][c] = __builtin_bitreverse32(sh[a][c][1]) >> 8;
             }

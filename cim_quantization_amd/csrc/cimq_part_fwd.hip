@@ -32,9 +32,11 @@ Fwd3Kern fwd3_kernel(int cst, FwdState st, int obm) {
                                      : fwd3_obm<8, KS, 8, S, M, 1>(obm);
   else if (cst != 4)
     return cst == 2 ? fwd3_obm<NBP, KS, 2, S, M, has_epi(M) ? 2 : 4>(obm) : fwd3_obm<NBP, KS, 3, S, M, 4>(obm);
-  // w4a4 word pairs: training only (v7_w44), two blocks at the most (named last: the older instances keep their
-  // places in the code object)
+  // w4a4 word pairs: the training forward writes them (v7_w44), every forward-only mode runs their stateless form
+  // (v7_w44_eval); two blocks at the most (named last, the stateless ones after the training one: the older
+  // instances keep their places in the code object)
   if constexpr (NBP == 4 && M == FwdMode::TRAIN) return fwd3_obm<4, KS, 4, FwdState::WRITE, FwdMode::TRAIN, 2>(obm);
+  else if constexpr (NBP == 4) return st == FwdState::NONE ? fwd3_obm<4, KS, 4, FwdState::NONE, M, 2>(obm) : nullptr;
   return nullptr;
 }
 
@@ -58,9 +60,11 @@ int launch_fwd_v3(const Geo& g, const Plan3& p, uint8_t* ctx, const float* sw, c
   // cost them a wave per SIMD: with an epilogue those layers run the two-block instances, twice the blocks in y;
   // the plan's LDS figures, made for four blocks, cover two)
   if (has_epi(m) && cst == 2 && st == FwdState::NONE && obm == 4) obm = 2;
-  // (w4a4 word pairs: 16 pairs of state bits per output block -- instances of one and two blocks)
+  // (w4a4 word pairs: 16 slice pairs per output block -- instances of one and two blocks; the words are the
+  // training forward's, a forward-only mode runs the stateless form)
   if (cst == 4) {
-    if (m != FwdMode::TRAIN) return fail(CIMQ_EINVAL, "internal: the w4a4 state words outside a training forward");
+    if ((m == FwdMode::TRAIN) != (st == FwdState::WRITE) || (m != FwdMode::TRAIN && st != FwdState::NONE))
+      return fail(CIMQ_EINVAL, "internal: the w4a4 state words outside a training forward");
     if (obm == 4) obm = 2;
   }
   // (the modes in the order the code object has always had its instances: a kernel's place decides its addresses)

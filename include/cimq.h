@@ -250,6 +250,21 @@ enum {
   CIMQ_ROUTE_NONE = 10     /* route[1] / route[2] under CIMQ_OPT_INFERENCE: there is no backward.  Since ABI 15 */
 };
 int cimq_module_route(const cimq_conv_desc* d, int* route);
+
+/* 1 where forward-only w4a4 layers in 1-bit slices (four slices a side, the library ADC) run the stateless word-pair
+ * forward -- one launch per prepared layer, the activation quantised in the kernel's row staging -- and
+ * cimq_module_forward_form exists (a library from before them has neither symbol).  CIMQ_ABI_VERSION / _MINOR and
+ * cimq_net_abi() are unchanged: no struct, call, size or route name moved. */
+int cimq_w4a4_eval_abi(void);
+
+/* Which form of the forward kernel family the module entry points run for `d`.  Pure host query, no device work.
+ *   form[0]  the family's state format: 0 the per-k words, 2 / 3 the compact words of w2a2 / w3a3, 4 the word pairs
+ *            of w4a4 in 1-bit slices, 8 the w8a8 planes.  Under CIMQ_OPT_INFERENCE no words are written; the number
+ *            still names the kernel form (4: on every shape whose training call runs that format).
+ *   form[1]  1 where the module forward quantises the activation in its own row staging, so that a call whose
+ *            weight side is prepared (q->wprep) is one launch with no pass over x before it; else 0.
+ * Returns 0, CIMQ_EINVAL for a NULL argument, or the status of a descriptor the module entry points refuse. */
+int cimq_module_forward_form(const cimq_conv_desc* d, int form[2]);
 int cimq_module_shift_forward(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* x, const float* weight,
                               const float* alpha_act, const float* alpha_weight, const float* alpha_cim,
                               const float* beta_cim, const int8_t* binary_mask, const float* signed_act, float* out,

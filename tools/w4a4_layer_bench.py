@@ -11,7 +11,9 @@ alternate them in child processes of one GPU session, each under its own time li
     python tools/w4a4_layer_bench.py --summarise runs --out profiles/w4a4/summary.json
 
 The summary gives, per shape and tag, the median over the runs and their spread (max - min), and the ratio of the
-two medians.
+two medians.  The forward-only column has a summary of its own beside it (``eval``, tags ``new`` and ``parent``): both
+medians, the larger of the two spreads, and whether the new median is lower than the parent's by more than that --
+the gate a forward-only kernel form has to pass to keep a shape.  ``--forward-only`` measures that column alone.
 """
 from __future__ import annotations
 
@@ -99,12 +101,12 @@ def measure(args):
             with torch.no_grad():
                 m(x)
 
-        ms_fb = _graph_ms(fb, args.steps, args.warmup)
+        ms_fb = None if args.forward_only else _graph_ms(fb, args.steps, args.warmup)
         ms_f = _graph_ms(fwd, args.steps, args.warmup)
         rows.append({"layer": name, "C": c, "O": o, "H": h, "stride": s, "route": list(route),
                      "ms_fwd_bwd": ms_fb, "ms_fwd": ms_f})
         print(f"{args.tag} {name:16s} {c:3d}->{o:3d} {h:2d}x{h:<2d} s{s} {'/'.join(route):24s} "
-              f"fwd+bwd {ms_fb:8.4f} ms  fwd {ms_f:8.4f} ms", flush=True)
+              f"fwd+bwd {float('nan') if ms_fb is None else ms_fb:8.4f} ms  fwd {ms_f:8.4f} ms", flush=True)
     res = {"tag": args.tag, "lib": os.path.relpath(L.LIB_PATH), "batch": args.batch, "bits": 4, "xbar": bench.XBAR,
            "adc": bench.ADC, "steps": args.steps, "warmup": args.warmup, "launch": "hip_graph",
            "device": torch.cuda.get_device_name(dev), "rows": rows}
@@ -133,13 +135,23 @@ def summarise(args):
         for t, v in runs.items():
             e[t] = {"route": v[0]["rows"][i]["route"]}
             for key in ("ms_fwd_bwd", "ms_fwd"):
-                xs = [r["rows"][i][key] for r in v]
-                e[t][key] = {"median": statistics.median(xs), "spread": max(xs) - min(xs), "runs": xs}
+                xs = [r["rows"][i][key] for r in v if r["rows"][i][key] is not None]
+                if xs:
+                    e[t][key] = {"median": statistics.median(xs), "spread": max(xs) - min(xs), "runs": xs}
         tags = list(runs)
         if len(tags) == 2:
             a, b = tags
             for key in ("ms_fwd_bwd", "ms_fwd"):
-                e[f"{key}_{a}_over_{b}"] = e[a][key]["median"] / e[b][key]["median"]
+                if key in e[a] and key in e[b]:
+                    e[f"{key}_{a}_over_{b}"] = e[a][key]["median"] / e[b][key]["median"]
+        if "new" in runs and "parent" in runs:
+            # the forward-only column's own summary: the new form keeps a shape whose median is lower than the
+            # parent's by more than the larger of the two spreads
+            n, q = e["new"]["ms_fwd"], e["parent"]["ms_fwd"]
+            bar = max(n["spread"], q["spread"])
+            e["eval"] = {"new_median_ms": n["median"], "parent_median_ms": q["median"], "new_spread_ms": n["spread"],
+                         "parent_spread_ms": q["spread"], "gain_ms": q["median"] - n["median"], "bar_ms": bar,
+                         "speedup": q["median"] / n["median"], "keeps_new_form": q["median"] - n["median"] > bar}
         out["layers"].append(e)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
@@ -156,6 +168,7 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--forward-only", action="store_true", help="time the no-grad forward alone")
     ap.add_argument("--summarise", default=None, metavar="DIR", help="merge the runs under DIR instead of measuring")
     args = ap.parse_args()
     if args.summarise:
