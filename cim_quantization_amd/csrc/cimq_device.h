@@ -324,8 +324,6 @@ __device__ inline void split3(float a, uint16_t& hi, uint16_t& mid, uint16_t& lo
   lo = bf16_bits(r2);
 }
 
-__device__ inline size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 __device__ inline v8bf as_v8bf(v4i x) { return __builtin_bit_cast(v8bf, x); }
 __device__ inline v4i as_v4i(v8bf x) { return __builtin_bit_cast(v4i, x); }
 

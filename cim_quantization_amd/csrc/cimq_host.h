@@ -210,10 +210,18 @@ struct Plan3 {
   size_t lds_fwd;
 };
 
-inline size_t a16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 // activation-prep blocks (grid-stride over 4-element items)
 inline int act_blocks() { return tune("ACT_BLOCKS", 8192); }
+
+// cim_fwd_v3_kernel's dynamic LDS without the quantiser's word table: NOB output blocks per block, TT tiles resident
+inline size_t fwd3_lds_bytes(const Geo& g, const V3& v, int NOB, int TT) {
+  const int NBP = g.NBP, KS = g.KS, nkj = g.nbw * g.nba;
+  size_t n = 0;
+#define X(name, bytes) n += bytes;
+  CIMQ_FWD3_LDS(X)
+#undef X
+  return n;
+}
 
 inline Plan3 v3_plan(const Geo& g) {
   Plan3 p;
@@ -249,18 +257,12 @@ inline Plan3 v3_plan(const Geo& g) {
   v.NT = (v.RI * g.W + 15) / 16 * v.CB;
   if (v.NT > 8 * 4 || g.KH > 3 || g.KW > 3) return p;
   v.nmt = g.M / 64;
-  const int nkj = g.nbw * g.nba;
-  const size_t ckl = a16((size_t)3 * nkj * 4);
-  const size_t patch = a16((size_t)g.C * v.RH * v.WP * g.NBP);
   v.obm = tune("FWD_OBM", 2);  // two o-blocks per block (measured best for O = 32 / 64)
   if (v.obm != 1 && v.obm != 2 && v.obm != 4) v.obm = 4;
   const int nof = std::min(v.obm, g.OB16);
-  const size_t fwd_common = patch + (size_t)g.T * g.KS * 64 * 4 + ckl;
-  const size_t fwd_w1 = (size_t)g.nbw * nof * g.KS * 1024 + (size_t)nkj * nof * 16 * (16 + 4);
-  const size_t fwd_res = fwd_common + (size_t)g.T * fwd_w1;
-  v.fwd_res = fwd_res <= (size_t)tune("FWD_RES_KB", 52) * 1024 ? 1 : 0;
+  v.fwd_res = fwd3_lds_bytes(g, v, nof, g.T) <= (size_t)tune("FWD_RES_KB", 52) * 1024 ? 1 : 0;
   v.pf = tune("FWD_PF", 1);
-  p.lds_fwd = v.fwd_res ? fwd_res : fwd_common + fwd_w1;
+  p.lds_fwd = fwd3_lds_bytes(g, v, nof, v.fwd_res ? g.T : 1);
   const size_t lim = kLdsMax - 512;
   p.ok = p.lds_fwd <= lim;
   return p;

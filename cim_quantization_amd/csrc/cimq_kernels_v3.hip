@@ -24,15 +24,75 @@ namespace cimq {
 // block = 64-pixel m-tiles (grid-stride) x one 64-wide o-group; wave w = pixels 16w..16w+15.
 // ---------------------------------------------------------------------------------------
 
+// The kernel's repeated pieces, one definition each: free functions with scalars by value, the form that keeps every
+// instance's instruction stream.  The weight side's items, global -> LDS, first: the stagings
+// (stage_tile, stage_prm, stage_all, load_tile) differ only in the tile index they pass.  Item idx of tile i's
+// weight fragments [k][ob][ks][64] (zero past the o-group's last output block):
+template <int KS, int OBM>
+__device__ inline v4i frag_item(const Geo& g, const v4i* __restrict__ wf, int og, int nob, int lnob, int i, int idx) {
+  const int l = idx & 63, fr = idx >> 6;
+  const int ks = KS == 1 ? 0 : (fr & 1), kob = KS == 1 ? fr : (fr >> 1);
+  const int k = kob >> lnob, ob = kob - (k << lnob);
+  v4i w = {0, 0, 0, 0};
+  if (ob < nob) w = wf[((size_t)(i * KS + ks) * g.NBLK + k * g.OB16 + og * OBM + ob) * WAVE + l];
+  return w;
+}
+// item idx of tile i's ADC thresholds / STE intervals [j][k][NOB*16] (NOB = 1 << lnob), and of its coefficients
+template <int OBM>
+__device__ inline int4 thr_item(const Geo& g, const Params& pp, int og, int lnob, float inv_nbw, int i, int idx) {
+  const int col = idx & ((16 << lnob) - 1), jk = idx >> (4 + lnob);
+  const int j = fdiv(jk, g.nbw, inv_nbw), k = jk - j * g.nbw;
+  const int o = og * OBM * 16 + col;
+  int4 p = make_int4(0, 0, 0, 0);
+  if (o < g.Opad) {
+    const int pi = pidx(g, i, j, k, o);
+    p = make_int4(pp.thi[pi], pp.tlo[pi], pp.mlo[pi], pp.mhi[pi]);
+  }
+  return p;
+}
+template <int OBM>
+__device__ inline float coef_item(const Geo& g, const Params& pp, int og, int lnob, float inv_nbw, int i, int idx) {
+  const int col = idx & ((16 << lnob) - 1), jk = idx >> (4 + lnob);
+  const int j = fdiv(jk, g.nbw, inv_nbw), k = jk - j * g.nbw;
+  const int o = og * OBM * 16 + col;
+  return (o < g.Opad) ? pp.coef[pidx(g, i, j, k, o)] : 0.f;
+}
+// index of this lane's weight fragment (slice k, output block ob, K-step ks) in a tile's wt[k][ob][ks][64]
+template <int KS>
+__device__ inline int wk_idx(int k, int NOB, int ob, int ks, int l) { return ((k * NOB + ob) * KS + ks) * 64 + l; }
+// The ADC of one partial sum on the unrolled (ballot) paths: the output term, and with state words (WST) the three
+// state masks -- STE pass, code != 0, code < 0 -- which the caller shifts in in the order its format needs.
+struct AdcMasks { uint64_t mps, mnz, mlo; };
+template <bool WST>
+__device__ inline AdcMasks ballot_adc(int ps, int4 pv, float cf, float& acc) {
+  const uint64_t mhi = __builtin_amdgcn_ballot_w64(ps >= pv.x);
+  const uint64_t mlo = __builtin_amdgcn_ballot_w64(ps <= pv.y);
+  acc += adc3(cf, mhi, mlo);
+  if constexpr (!WST) return AdcMasks{0ull, 0ull, 0ull};  // (no state words -- and none of their bits)
+  const uint64_t mps = __builtin_amdgcn_ballot_w64((unsigned)(ps - pv.z) <= (unsigned)pv.w);
+  return AdcMasks{mps, mhi | mlo, mlo};
+}
+// The per-pair loop's state bits of one row: pair (k, j)'s three bits sb (st_bits' order) into weight slice k's
+// word stw (interleaved words, the w4a4 word pair) or its three plane words tq (PLF: w8a8)
+template <bool PLF>
+__device__ inline void add_bits(uint32_t& stw, uint32_t (&tq)[3], int j, uint32_t sb) {
+  if (PLF) {
+    tq[0] |= (sb & 1u) << j;
+    tq[1] |= ((sb >> 1) & 1u) << j;
+    tq[2] |= ((sb >> 2) & 1u) << j;
+  } else {
+    stw |= sb << (3 * j);
+  }
+}
+
 // CST: compact state words (cimq_v7.hip) -- one uint32 per (tile i, pixel m, channel o) at
 // st32[(i*M + m)*O + o], bits 3*(k*nba + j) + {0: STE pass, 1: code != 0, 2: code < 0}; 0: the per-k words.
 // CST > 0 also fixes nbw = nba = CST at compile time: the ternary-threshold path then runs
 // fully unrolled (every slice pair's MFMAs issued before its ADC work, state bits shifted in).
 // CST 4 (w4a4 in 1-bit slices): 16 pairs in a uint2 per (i, m, o) at st64[(i*M + m)*O + o] -- .x the pairs of
-// weight slices 0-1 as above (kj 0..7), .y those of slices 2-3 at 3*(kj - 8).  Its unrolled path adds the pairs to
-// the output in CST 0's order (k, then j, ascending), so it agrees with CST 0 bit for bit.  Its stateless form
-// (ST NONE: the forward-only module calls, v7_w44_eval) is that path without the words, their bits and the ballots
-// that feed only them, with the activation quantiser in the row staging as in the CST 2 / 3 stateless instances.
+// weight slices 0-1 as above (kj 0..7), .y those of slices 2-3 at 3*(kj - 8); its unrolled path agrees with CST 0
+// bit for bit.  Its stateless form (ST NONE: the forward-only module calls, v7_w44_eval) is that path without the
+// words, their bits and the ballots that feed only them, with the quantiser in the row staging as in CST 2 / 3.
 // ST: what becomes of those words (FwdState).  M: what the store does (FwdMode) -- the epilogue ep on the float4
 // about to be stored (NCHW only); with codes, the row staging reads the input's codes (ep.xq: bytes straight into
 // the word table, stage_rows_qc) or quantises fp32 x as before, and the store writes the float4, the consumer's
@@ -48,8 +108,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
                                                          const float* __restrict__ sgn_p, uint8_t* __restrict__ xcb,
                                                          Epi ep) {
   constexpr bool VIEW = has_view(M), COD = has_codes(M), EPI = has_epi(M);
-  constexpr bool WST = ST == FwdState::WRITE;
-  constexpr bool INF = ST == FwdState::NONE;
+  constexpr bool WST = ST == FwdState::WRITE, INF = ST == FwdState::NONE;
   static_assert(CST == 0 || CST == 2 || CST == 3 || CST == 4 || CST == 8,
                 "state formats: per-k words, w2a2, w3a3, w4a4 word pairs, w8a8 planes");
   static_assert(CST != 4 || (NBP == 4 && ((WST && M == FwdMode::TRAIN) || INF)),
@@ -66,14 +125,16 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
   const int TT = v.fwd_res ? g.T : 1;
   const int nkj = g.nbw * g.nba;
   uint8_t* cur = smem;
-  uint8_t* patch = cur; cur += al16((size_t)g.C * v.RH * v.WP * NBP);
-  int* ptab = reinterpret_cast<int*>(cur); cur += (size_t)g.T * KS * 64 * 4;
-  v4i* wfl = reinterpret_cast<v4i*>(cur); cur += (size_t)TT * g.nbw * NOB * KS * 1024;   // [tt][k][ob][ks][64]
-  int4* prm = reinterpret_cast<int4*>(cur); cur += (size_t)TT * nkj * NOB * 16 * 16;    // [tt][j][k][NOB*16]
-  float* cfl = reinterpret_cast<float*>(cur); cur += (size_t)TT * nkj * NOB * 16 * 4;   // coef, same order
-  float* ckl = reinterpret_cast<float*>(cur);
-  // the quantiser's word table [Qp + 1][fwd, bwd] after ckl (launch_fwd_v3 sizes it in)
-  uint32_t* alut = reinterpret_cast<uint32_t*>(cur + al16((size_t)3 * g.nbw * g.nba * 4));
+#define X(name, bytes) uint8_t* const l_##name = cur; cur += bytes;
+  CIMQ_FWD3_LDS(X)
+#undef X
+  uint8_t* patch = l_patch;
+  int* ptab = reinterpret_cast<int*>(l_ptab);
+  v4i* wfl = reinterpret_cast<v4i*>(l_wfl);
+  int4* prm = reinterpret_cast<int4*>(l_prm);
+  float* cfl = reinterpret_cast<float*>(l_cfl);
+  float* ckl = reinterpret_cast<float*>(l_ckl);
+  uint32_t* alut = reinterpret_cast<uint32_t*>(cur);  // the quantiser's word table, after the list
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r16 = lane & 15, g4 = lane >> 4;
@@ -82,7 +143,6 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
   const bool literal = flag_lit || g.mode != ADC_TERNARY;
   const bool has_code = (g.mode == ADC_SIGN || g.mode == ADC_TERNARY);
   const int Wo = 1 << v.lw;
-
   // index math by shifts (NOB in {1, 2, 4}, KS in {1, 2}) and a float-reciprocal division
   // by nbw: integer division is ~30 VALU each, and this prologue runs once per block
   const int lnob = NOB == 4 ? 2 : NOB - 1;
@@ -90,37 +150,17 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
   // the ADC thresholds and coefficients of tile i (the weight side's small part)
   auto stage_prm = [&](int i, int tt) {
     if (!flag_lit) {
-      batched_copy<2>(nkj * NOB * 16, prm + (size_t)tt * nkj * NOB * 16, [&](int idx) -> int4 {
-        const int col = idx & ((16 << lnob) - 1), jk = idx >> (4 + lnob);
-        const int j = fdiv(jk, g.nbw, inv_nbw), k = jk - j * g.nbw;
-        const int o = og * OBM * 16 + col;
-        int4 p = make_int4(0, 0, 0, 0);
-        if (o < g.Opad) {
-          const int pi = pidx(g, i, j, k, o);
-          p = make_int4(pp.thi[pi], pp.tlo[pi], pp.mlo[pi], pp.mhi[pi]);
-        }
-        return p;
-      });
-      batched_copy<4>(nkj * NOB * 16, cfl + (size_t)tt * nkj * NOB * 16, [&](int idx) -> float {
-        const int col = idx & ((16 << lnob) - 1), jk = idx >> (4 + lnob);
-        const int j = fdiv(jk, g.nbw, inv_nbw), k = jk - j * g.nbw;
-        const int o = og * OBM * 16 + col;
-        return (o < g.Opad) ? pp.coef[pidx(g, i, j, k, o)] : 0.f;
-      });
+      batched_copy<2>(nkj * NOB * 16, prm + (size_t)tt * nkj * NOB * 16,
+                      [&](int idx) -> int4 { return thr_item<OBM>(g, pp, og, lnob, inv_nbw, i, idx); });
+      batched_copy<4>(nkj * NOB * 16, cfl + (size_t)tt * nkj * NOB * 16,
+                      [&](int idx) -> float { return coef_item<OBM>(g, pp, og, lnob, inv_nbw, i, idx); });
     }
   };
   auto stage_tile = [&](int i, int tt) {
-    batched_copy<4>(g.nbw * NOB * KS * 64, wfl + (size_t)tt * g.nbw * NOB * KS * 64, [&](int idx) -> v4i {
-      const int l = idx & 63, fr = idx >> 6;
-      const int ks = KS == 1 ? 0 : (fr & 1), kob = KS == 1 ? fr : (fr >> 1);
-      const int k = kob >> lnob, ob = kob - (k << lnob);
-      v4i w = {0, 0, 0, 0};
-      if (ob < nob) w = wfrag[((size_t)(i * KS + ks) * g.NBLK + k * g.OB16 + og * OBM + ob) * WAVE + l];
-      return w;
-    });
+    batched_copy<4>(g.nbw * NOB * KS * 64, wfl + (size_t)tt * g.nbw * NOB * KS * 64,
+                    [&](int idx) -> v4i { return frag_item<KS, OBM>(g, wfrag, og, nob, lnob, i, idx); });
     stage_prm(i, tt);
   };
-
   // every tile's weight side at once (fwd_res): one batched pass per array over all tiles, so its
   // loads are in flight together (tile by tile it took T x 3 dependent round trips: 8-9 us of a
   // 40-45 us launch on the 16x16 / 8x8 layers)
@@ -129,32 +169,16 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
     const float inv_nw = 1.f / (float)nw, inv_np = 1.f / (float)np;
     batched_copy<8>(g.T * nw, wfl, [&](int t) -> v4i {
       const int i = fdiv(t, nw, inv_nw), idx = t - i * nw;
-      const int l = idx & 63, fr = idx >> 6;
-      const int ks = KS == 1 ? 0 : (fr & 1), kob = KS == 1 ? fr : (fr >> 1);
-      const int k = kob >> lnob, ob = kob - (k << lnob);
-      v4i w = {0, 0, 0, 0};
-      if (ob < nob) w = wfrag[((size_t)(i * KS + ks) * g.NBLK + k * g.OB16 + og * OBM + ob) * WAVE + l];
-      return w;
+      return frag_item<KS, OBM>(g, wfrag, og, nob, lnob, i, idx);
     });
     if (!flag_lit) {
       batched_copy<8>(g.T * np, prm, [&](int t) -> int4 {
         const int i = fdiv(t, np, inv_np), idx = t - i * np;
-        const int col = idx & ((16 << lnob) - 1), jk = idx >> (4 + lnob);
-        const int j = fdiv(jk, g.nbw, inv_nbw), k = jk - j * g.nbw;
-        const int o = og * OBM * 16 + col;
-        int4 p = make_int4(0, 0, 0, 0);
-        if (o < g.Opad) {
-          const int pi = pidx(g, i, j, k, o);
-          p = make_int4(pp.thi[pi], pp.tlo[pi], pp.mlo[pi], pp.mhi[pi]);
-        }
-        return p;
+        return thr_item<OBM>(g, pp, og, lnob, inv_nbw, i, idx);
       });
       batched_copy<8>(g.T * np, cfl, [&](int t) -> float {
         const int i = fdiv(t, np, inv_np), idx = t - i * np;
-        const int col = idx & ((16 << lnob) - 1), jk = idx >> (4 + lnob);
-        const int j = fdiv(jk, g.nbw, inv_nbw), k = jk - j * g.nbw;
-        const int o = og * OBM * 16 + col;
-        return (o < g.Opad) ? pp.coef[pidx(g, i, j, k, o)] : 0.f;
+        return coef_item<OBM>(g, pp, og, lnob, inv_nbw, i, idx);
       });
     }
   };
@@ -173,12 +197,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
     for (int u = 0; u < PFW; ++u) {
       const int idx = threadIdx.x + u * 256;
       pw[u] = v4i{0, 0, 0, 0};
-      if (idx < nw) {
-        const int l = idx & 63, fr = idx >> 6;
-        const int ks = KS == 1 ? 0 : (fr & 1), kob = KS == 1 ? fr : (fr >> 1);
-        const int k = kob >> lnob, ob = kob - (k << lnob);
-        if (ob < nob) pw[u] = wfrag[((size_t)(i * KS + ks) * g.NBLK + k * g.OB16 + og * OBM + ob) * WAVE + l];
-      }
+      if (idx < nw) pw[u] = frag_item<KS, OBM>(g, wfrag, og, nob, lnob, i, idx);
     }
   };
   auto store_tile = [&]() {
@@ -187,7 +206,6 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
     for (int u = 0; u < PFW; ++u)
       if ((int)threadIdx.x + u * 256 < nw) wfl[threadIdx.x + u * 256] = pw[u];
   };
-
   for (int i = 0; i < g.T; ++i) build_ptab(g, i, KS, v.RH, v.WP, ptab + i * KS * 64);
   for (int t = threadIdx.x; t < 3 * nkj; t += blockDim.x) ckl[t] = pp.ckj[t];
   if (pfx) load_tile(0);  // in flight through the prologue and the first row staging
@@ -216,7 +234,6 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
   const int pl = wave * 16 + r16;  // this lane's gather pixel within the m-tile
   const int rb = ((pl >> v.lw) * g.SH) * v.WP + (pl & (Wo - 1)) * g.SW;
   const int tiles_per_img = g.P >> 6;
-
   const float inv_tpi = 1.f / (float)tiles_per_img, inv_p = 1.f / (float)g.P;
   for (int mt = blockIdx.x; mt < v.nmt; mt += gridDim.x) {
     const int b = fdiv(mt, tiles_per_img, inv_tpi), p0 = (mt - b * tiles_per_img) * 64;
@@ -240,7 +257,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
     for (int a = 0; a < OBM; ++a)
 #pragma unroll
       for (int c = 0; c < 4; ++c) acc[a][c] = 0.f;
-    for (int i = 0; i < g.T; ++i) {
+    for (int i = 0; i < g.T; ++i) {  // per tile: weight side (non-resident tiles), gather, pairs, store state
       if (!v.fwd_res) {
         __syncthreads();
         if (pfx) {
@@ -282,10 +299,10 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
 #pragma unroll
         for (int c = 0; c < 4; ++c) pl[a][c][0] = pl[a][c][1] = pl[a][c][2] = 0ull;
       if constexpr (CST == 4) {
-        // fast path of the 16 pairs, in CST 0's order of additions: k ascending, per output block the four
-        // pairs' MFMAs, then j ascending.  Each word takes its 8 pairs' bits from the bottom -- pass, code != 0,
-        // code < 0 -- which leaves pair kj's at 23 - 3*(kj & 7) - {0, 1, 2}: a bit reversal and a shift by 8 put
-        // them at 3*(kj & 7) + {0, 1, 2}, where cimq_v7.hip reads them.
+        // pairs, path 1 of 3 -- w4a4 unrolled: the 16 pairs in CST 0's order of additions, k ascending, per output
+        // block the four pairs' MFMAs, then j ascending.  Each word takes its 8 pairs' bits from the bottom -- pass,
+        // code != 0, code < 0 -- which leaves pair kj's at 23 - 3*(kj & 7) - {0, 1, 2}: a bit reversal and a shift by
+        // 8 put them at 3*(kj & 7) + {0, 1, 2}, where cimq_v7.hip reads them.
         if (!literal) {
           uint32_t sh[OBM][4][2];
 #pragma unroll
@@ -299,7 +316,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
               if (ob < nob) {
                 v4i wk[KS];
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks) wk[ks] = wt[((k * NOB + ob) * KS + ks) * 64 + lane];
+                for (int ks = 0; ks < KS; ++ks) wk[ks] = wt[wk_idx<KS>(k, NOB, ob, ks, lane)];
                 v4i ps[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -314,13 +331,9 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
                   const float cf = ct[pcol];
 #pragma unroll
                   for (int r = 0; r < 4; ++r) {
-                    const uint64_t mhi = __builtin_amdgcn_ballot_w64(ps[j][r] >= pv.x);
-                    const uint64_t mlo = __builtin_amdgcn_ballot_w64(ps[j][r] <= pv.y);
-                    acc[ob][r] += adc3(cf, mhi, mlo);
-                    if constexpr (!WST) continue;  // (no state words -- and none of their bits)
-                    const uint64_t mps = __builtin_amdgcn_ballot_w64((unsigned)(ps[j][r] - pv.z) <= (unsigned)pv.w);
-                    const uint64_t mnz = mhi | mlo;
-                    sh[ob][r][k >> 1] = shin(shin(shin(sh[ob][r][k >> 1], mps), mnz), mlo);
+                    const AdcMasks m = ballot_adc<WST>(ps[j][r], pv, cf, acc[ob][r]);
+                    if constexpr (!WST) continue;
+                    sh[ob][r][k >> 1] = shin(shin(shin(sh[ob][r][k >> 1], m.mps), m.mnz), m.mlo);
                   }
                 }
               }
@@ -336,15 +349,14 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
             }
         }
       } else if (CST > 0 && !literal && std8) {
-        // fast path: slice pairs kj = k*CST + j in descending order, so that shifting each
-        // state bit in from the bottom leaves bit 3*kj + {0,1,2} (interleaved words) or bit
+        // pairs, path 2 of 3 -- compact unrolled: slice pairs kj = k*CST + j in descending order, so that
+        // shifting each state bit in from the bottom leaves bit 3*kj + {0,1,2} (interleaved words) or bit
         // kj of each 64-bit plane (PLF) where cimq_v7.hip reads it.  w8a8 (CST 8) runs it only
         // with the standard int8-wrapped binary_mask (_quan_base.py:207-214), whose pairs with
         // j + k >= 8 are 0: they add adc * 0 = 0 to the output and G * 0 = 0 to every gradient,
         // so neither their MFMAs nor their ADC run and their state bits stay 0 (exact: this path
         // has finite ADC outputs).  Any other mask takes the per-pair loop below.
         constexpr int NS = CST > 0 ? CST : 1;
-
         uint32_t sw3[OBM][4][PLF ? 6 : 1];
 #pragma unroll
         for (int a = 0; a < OBM; ++a)
@@ -359,7 +371,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
             if (ob < nob) {
               v4i wk[KS];
 #pragma unroll
-              for (int ks = 0; ks < KS; ++ks) wk[ks] = wt[((k * NOB + ob) * KS + ks) * 64 + lane];
+              for (int ks = 0; ks < KS; ++ks) wk[ks] = wt[wk_idx<KS>(k, NOB, ob, ks, lane)];
               v4i ps[NS];
 #pragma unroll
               for (int j = 0; j < NS; ++j) {
@@ -395,19 +407,15 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
                 const float cf = ct[pcol];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                  const uint64_t mhi = __builtin_amdgcn_ballot_w64(ps[j][r] >= pv.x);
-                  const uint64_t mlo = __builtin_amdgcn_ballot_w64(ps[j][r] <= pv.y);
-                  acc[ob][r] += adc3(cf, mhi, mlo);
-                  if constexpr (!WST) continue;  // (no state words -- and none of their bits)
-                  const uint64_t mps = __builtin_amdgcn_ballot_w64((unsigned)(ps[j][r] - pv.z) <= (unsigned)pv.w);
-                  const uint64_t mnz = mhi | mlo;
+                  const AdcMasks m = ballot_adc<WST>(ps[j][r], pv, cf, acc[ob][r]);
+                  if constexpr (!WST) continue;
                   if constexpr (PLF) {
                     const int wd = kj >= 32 ? 1 : 0;
-                    sw3[ob][r][wd] = shin(sw3[ob][r][wd], mps);
-                    sw3[ob][r][2 + wd] = shin(sw3[ob][r][2 + wd], mnz);
-                    sw3[ob][r][4 + wd] = shin(sw3[ob][r][4 + wd], mlo);
+                    sw3[ob][r][wd] = shin(sw3[ob][r][wd], m.mps);
+                    sw3[ob][r][2 + wd] = shin(sw3[ob][r][2 + wd], m.mnz);
+                    sw3[ob][r][4 + wd] = shin(sw3[ob][r][4 + wd], m.mlo);
                   } else {
-                    sw3[ob][r][0] = shin(shin(shin(sw3[ob][r][0], mlo), mnz), mps);
+                    sw3[ob][r][0] = shin(shin(shin(sw3[ob][r][0], m.mlo), m.mnz), m.mps);
                   }
                 }
               }
@@ -427,6 +435,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
             }
           }
       }
+      // pairs, path 3 of 3 -- the per-k loop: every format and ADC flavour, run-time slice counts
       for (int k = 0; k < ((CST > 0 && !literal && std8) ? 0 : g.nbw); ++k) {
 #pragma unroll
         for (int ob = 0; ob < OBM; ++ob) {
@@ -434,7 +443,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
             const int o = (og * OBM + ob) * 16 + r16;
             v4i wk[KS];
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) wk[ks] = wt[((k * NOB + ob) * KS + ks) * 64 + lane];
+            for (int ks = 0; ks < KS; ++ks) wk[ks] = wt[wk_idx<KS>(k, NOB, ob, ks, lane)];
             uint32_t stw[4] = {0u, 0u, 0u, 0u};
             uint32_t tq[4][3] = {{0u, 0u, 0u}, {0u, 0u, 0u}, {0u, 0u, 0u}, {0u, 0u, 0u}};
 #pragma unroll
@@ -455,13 +464,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
                     acc[ob][r] += a;
                     if constexpr (INF) continue;  // (forward only: no state bits)
                     const bool pass = (unsigned)(ps[r] - pv.z) <= (unsigned)pv.w;
-                    if (PLF) {
-                      tq[r][0] |= (pass ? 1u : 0u) << j;
-                      tq[r][1] |= ((hi || lo) ? 1u : 0u) << j;
-                      tq[r][2] |= (lo ? 1u : 0u) << j;
-                    } else {
-                      stw[r] |= ((pass ? 1u : 0u) | ((hi || lo) ? 2u : 0u) | (lo ? 4u : 0u)) << (3 * j);
-                    }
+                    add_bits<PLF>(stw[r], tq[r], j, (pass ? 1u : 0u) | ((hi || lo) ? 2u : 0u) | (lo ? 4u : 0u));
                   }
                 } else if (is_shift(g)) {
                   const float al = pp.alpha[pidx(g, i, j, k, o)], be = pp.beta[pidx(g, i, j, k, o)];
@@ -470,14 +473,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
                   for (int r = 0; r < 4; ++r) {
                     acc[ob][r] += shift_adc_literal(ps[r], sw, sa, al, be, mk);
                     if constexpr (INF) continue;
-                    const uint32_t sb = shift_state_literal(ps[r], sw, sa, al, be, g.thr_hi, g.thr_lo);
-                    if (PLF) {
-                      tq[r][0] |= (sb & 1u) << j;
-                      tq[r][1] |= ((sb >> 1) & 1u) << j;
-                      tq[r][2] |= ((sb >> 2) & 1u) << j;
-                    } else {
-                      stw[r] |= sb << (3 * j);
-                    }
+                    add_bits<PLF>(stw[r], tq[r], j, shift_state_literal(ps[r], sw, sa, al, be, g.thr_hi, g.thr_lo));
                   }
                 } else {
                   const float al = pp.alpha[pidx(g, i, j, k, o)];
@@ -491,14 +487,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
                                                : ((unsigned)(ps[r] - pv.z) <= (unsigned)pv.w);
                     const float code =
                         has_code ? code_literal(ps[r], g.mode, sw, sa, al, g.qn, g.qp, g.thr_hi, g.thr_lo) : 0.f;
-                    const uint32_t sb = st_bits(pass, code);
-                    if (PLF) {
-                      tq[r][0] |= (sb & 1u) << j;
-                      tq[r][1] |= ((sb >> 1) & 1u) << j;
-                      tq[r][2] |= ((sb >> 2) & 1u) << j;
-                    } else {
-                      stw[r] |= sb << (3 * j);
-                    }
+                    add_bits<PLF>(stw[r], tq[r], j, st_bits(pass, code));
                   }
                 }
               }
@@ -521,7 +510,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
           }
         }
       }
-      if (CST && WST) {
+      if (CST && WST) {  // store state: the words in their format's layout
 #pragma unroll
         for (int ob = 0; ob < OBM; ++ob) {
           const int o = (og * OBM + ob) * 16 + r16;
@@ -547,7 +536,7 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
         }
       }
     }
-    // acc[ob][r]: pixel wave*16 + 4*g4 + r, channel (og*4 + ob)*16 + r16
+    // store out, its mode branches in one place.  acc[ob][r]: pixel wave*16 + 4*g4 + r, channel (og*OBM + ob)*16 + r16
 #pragma unroll
     for (int ob = 0; ob < OBM; ++ob) {
       const int o = (og * OBM + ob) * 16 + r16;
@@ -565,24 +554,20 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
           const int m4 = mt * 64 + wave * 16 + 4 * g4;  // M < 2^24 (v3_plan)
           const int bb = fdiv(m4, g.P, inv_p), pq = m4 - bb * g.P;
           const size_t oi = ((size_t)bb * g.O + o) * g.P + pq;
-          if constexpr (COD) {
-            int oe = o;  // (opaque, as below)
-            asm volatile("" : "+v"(oe));
-            if constexpr (VIEW)
-              store_codes4(ep, out, oi,
-                           epi_val4v(ep, ep.scale[oe], ep.shift[oe], oi, bb, oe, pq, g.Wo, acc[ob][0], acc[ob][1],
-                                     acc[ob][2], acc[ob][3]));
-            else
-              store_codes4(ep, out, oi,
-                           epi_val4(ep, ep.scale[oe], ep.shift[oe], oi, acc[ob][0], acc[ob][1], acc[ob][2], acc[ob][3]));
-          } else if constexpr (EPI) {
+          if constexpr (EPI) {
             // (the table index through an opaque copy: the two 64-bit entry addresses, invariant over the m-tiles,
             // would otherwise be kept in 4 VGPRs per output block across the whole loop -- a wave per SIMD in the
             // OBM 4 instances)
             int oe = o;
             asm volatile("" : "+v"(oe));
-            *reinterpret_cast<float4*>(out + oi) =
-                epi_val4(ep, ep.scale[oe], ep.shift[oe], oi, acc[ob][0], acc[ob][1], acc[ob][2], acc[ob][3]);
+            float4 v4;
+            if constexpr (VIEW)
+              v4 = epi_val4v(ep, ep.scale[oe], ep.shift[oe], oi, bb, oe, pq, g.Wo, acc[ob][0], acc[ob][1], acc[ob][2],
+                             acc[ob][3]);
+            else
+              v4 = epi_val4(ep, ep.scale[oe], ep.shift[oe], oi, acc[ob][0], acc[ob][1], acc[ob][2], acc[ob][3]);
+            if constexpr (COD) store_codes4(ep, out, oi, v4);
+            else *reinterpret_cast<float4*>(out + oi) = v4;
           } else
             *reinterpret_cast<float4*>(out + oi) = make_float4(acc[ob][0], acc[ob][1], acc[ob][2], acc[ob][3]);
         }

@@ -71,8 +71,8 @@ __global__ __launch_bounds__(256) void shift_stats_kernel(Geo g, V3 v, const uin
   const int ncx = c_hi - c_lo + 1;
   const int NE = 2 * R + 1;
   uint8_t* cur = smem;
-  float* tab = reinterpret_cast<float*>(cur); cur += LUT ? al16((size_t)NKJ * 16 * NE * 4) : 0;
-  uint8_t* patch = cur; cur += al16((size_t)ncx * v.RH * v.WP * NBP);
+  float* tab = reinterpret_cast<float*>(cur); cur += LUT ? a16((size_t)NKJ * 16 * NE * 4) : 0;
+  uint8_t* patch = cur; cur += a16((size_t)ncx * v.RH * v.WP * NBP);
   int* ptab = reinterpret_cast<int*>(cur); cur += (size_t)KS * 64 * 4;
   float* red = reinterpret_cast<float*>(cur);  // [4 waves][2 * NKJ][16 channels]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

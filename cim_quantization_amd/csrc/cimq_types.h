@@ -308,4 +308,19 @@ constexpr uint32_t kCodesMagic = 0xC0DE5EEDu;
 // the RAW_LSQ activation word table a block builds in LDS (act_lut_build) holds codes below this
 constexpr int kActLutMax = 256;
 
+__host__ __device__ inline size_t a16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// cim_fwd_v3_kernel's dynamic LDS, region by region in order: X(name, bytes) in terms of g (Geo), v (V3), NBP, KS,
+// NOB (16-channel output blocks per block), TT (tiles with a resident weight side: T with V3::fwd_res, else 1), nkj.
+// The kernel carves its pointers from this list, fwd3_lds_bytes (cimq_host.h: v3_plan) sums it, and the fused
+// quantiser's word table follows the last region (launch_fwd_v3).  A list and not a function: the kernel's address
+// arithmetic stays in its body token for token.
+#define CIMQ_FWD3_LDS(X)                                                                                 \
+  X(patch, a16((size_t)g.C * v.RH * v.WP * NBP)) /* [C][RH][WP] words of NBP bytes */                   \
+  X(ptab, (size_t)g.T * KS * 64 * 4)              /* [T][KS*64] patch word offsets */                    \
+  X(wfl, (size_t)TT * g.nbw * NOB * KS * 1024)    /* [tt][k][ob][ks][64] weight fragments */             \
+  X(prm, (size_t)TT * nkj * NOB * 16 * 16)        /* [tt][j][k][NOB*16] int4 thresholds / STE spans */   \
+  X(cfl, (size_t)TT * nkj * NOB * 16 * 4)         /* coef, same order */                                 \
+  X(ckl, a16((size_t)3 * g.nbw * g.nba * 4))      /* [3][nkj] (Params::ckj) */
+
 }  // namespace cimq

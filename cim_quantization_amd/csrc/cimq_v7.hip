@@ -404,7 +404,7 @@ __global__ __launch_bounds__(256, 2) void cim_bwd_gw_v7_kernel(Geo g, V7 v, cons
 
   const size_t plane = (size_t)v.KWP;  // one (j, kw) plane, bf16 elements (padded: gw_pitches)
   uint8_t* cur = smem;
-  __bf16* pl = reinterpret_cast<__bf16*>(cur); { const size_t pb = (size_t)NBA * 3 * plane * 2; cur += al16(pb > 36864 ? pb : (size_t)36864); }
+  __bf16* pl = reinterpret_cast<__bf16*>(cur); { const size_t pb = (size_t)NBA * 3 * plane * 2; cur += a16(pb > 36864 ? pb : (size_t)36864); }
   float* cdl = reinterpret_cast<float*>(cur); cur += 64 * 4;
   float* red = reinterpret_cast<float*>(cur);  // [4 waves][NTL][NKJ][16] grad_alpha partials
   for (int t = threadIdx.x; t < NKJ; t += blockDim.x) cdl[t] = pp.ckj[2 * NKJ + t];
