@@ -23,9 +23,10 @@ CIMQ_INPUT_XQ = 0
 CIMQ_INPUT_RAW_LSQ = 1
 # cimq_module_route codes (include/cimq.h CIMQ_ROUTE_*)
 ROUTE_NAMES = {0: "general", 1: "v3", 2: "fwd5", 3: "v7", 4: "fused", 5: "c1", 6: "gx5", 7: "gw5", 8: "dense", 9: "r6",
-               10: "none"}
+               10: "none", 11: "wide"}
 CIMQ_ROUTE_R6 = 9
 CIMQ_ROUTE_NONE = 10  # route[1] / route[2] under CIMQ_OPT_INFERENCE (ABI 15)
+CIMQ_ROUTE_WIDE = 11  # route[0]: cim_fwd_wide_kernel (cimq_wide_abi() == 1)
 CIMQ_LSQ_ACCUMULATE_GRADS = 1
 CIMQ_LSQ_SKIP_TAIL = 2
 CIMQ_LSQ_DEFER_GW = 4
@@ -63,6 +64,8 @@ EXPORTED_SYMBOLS = (
     "cimq_module_route",
     "cimq_w4a4_eval_abi",
     "cimq_module_forward_form",
+    "cimq_wide_abi",
+    "cimq_module_wide_plan",
     "cimq_module_shift_forward",
     "cimq_module_shift_backward",
     "cimq_module_forward_epilogue",
@@ -269,6 +272,11 @@ def _bind(lib):
         lib.cimq_w4a4_eval_abi.argtypes = []
         lib.cimq_module_forward_form.restype = ctypes.c_int
         lib.cimq_module_forward_form.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_int)]
+    if hasattr(lib, "cimq_wide_abi"):
+        lib.cimq_wide_abi.restype = ctypes.c_int
+        lib.cimq_wide_abi.argtypes = []
+        lib.cimq_module_wide_plan.restype = ctypes.c_int
+        lib.cimq_module_wide_plan.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_int)]
     lib.cimq_module_shift_forward.restype = ctypes.c_int
     lib.cimq_module_shift_forward.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(LsqDesc)] + [_VP] * 12
     lib.cimq_module_shift_backward.restype = ctypes.c_int
@@ -444,6 +452,14 @@ def module_forward_form(desc: ConvDesc):
     its own row staging) for ``desc`` -- cimq_module_forward_form (cimq_w4a4_eval_abi() == 1)."""
     f = (ctypes.c_int * 2)()
     check(load().cimq_module_forward_form(ctypes.byref(desc), f), "cimq_module_forward_form")
+    return tuple(f)
+
+
+def module_wide_plan(desc: ConvDesc):
+    """(ok, channel chunks, output groups, tiles) of the channel-chunked forward for ``desc`` --
+    cimq_module_wide_plan (cimq_wide_abi() == 1)."""
+    f = (ctypes.c_int * 4)()
+    check(load().cimq_module_wide_plan(ctypes.byref(desc), f), "cimq_module_wide_plan")
     return tuple(f)
 
 

@@ -623,6 +623,8 @@ static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
     }
     if (ep->rvw1) {  // the view lives in the code instances of the fwd5, v3 and general routes
       const int fwd = route_of(g).fwd;
+      if (fwd == CIMQ_ROUTE_WIDE)
+        return fail(CIMQ_EUNSUPPORTED, "cimq_net_forward: the wide route reads no residual view");
       if (fwd == CIMQ_ROUTE_DENSE)
         return fail(CIMQ_EUNSUPPORTED, "cimq_net_forward: the dense route reads no residual view (res_stride 2 or "
                                        "fewer source channels than out_channels)");
@@ -635,6 +637,9 @@ static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
   uint8_t* oq = ep ? ep->oq : nullptr;        // ... the output's codes; with nofloat, out is not written
   if (xq || oq) {
     const Route rc = route_of(g);
+    if (rc.fwd == CIMQ_ROUTE_WIDE)
+      return fail(CIMQ_EUNSUPPORTED, "cimq_module_forward_codes: the wide route takes no x_codes and writes no "
+                                     "out_codes (cimq_module_codes_supported)");
     if (xq && !codes_qp_ok(g.lsq_qp))
       return fail(CIMQ_EUNSUPPORTED, "cimq_module_forward_codes: x_codes needs an integer lsq_qp in [1, 254] (it is %g)",
                   (double)g.lsq_qp);
@@ -746,6 +751,23 @@ int cimq_module_route(const cimq_conv_desc* d, int* route) {
 
 int cimq_w4a4_eval_abi(void) { return 1; }
 
+int cimq_wide_abi(void) { return 1; }
+
+int cimq_module_wide_plan(const cimq_conv_desc* d, int out[4]) {
+  Geo g;
+  CIMQ_TRY(make_geo(d, &g));
+  if (!out) return fail(CIMQ_EINVAL, "null out");
+  if (g.input_kind != CIMQ_INPUT_RAW_LSQ) return fail(CIMQ_EINVAL, "module entry points take the raw activation");
+  g = module_form(g);
+  const PlanW p = wide_plan(g);
+  const bool ok = route_of(g).fwd == CIMQ_ROUTE_WIDE;
+  out[0] = ok ? 1 : 0;
+  out[1] = ok ? p.w.nch : 0;
+  out[2] = ok ? p.groups : 0;
+  out[3] = ok ? g.T : 0;
+  return CIMQ_OK;
+}
+
 int cimq_module_forward_form(const cimq_conv_desc* d, int form[2]) {
   Geo g;
   CIMQ_TRY(make_geo(d, &g));
@@ -794,7 +816,7 @@ int cimq_module_codes_supported(const cimq_conv_desc* d, int* in_ok, int* out_ok
   if (g.input_kind != CIMQ_INPUT_RAW_LSQ) return fail(CIMQ_EINVAL, "module entry points take the raw activation");
   g = module_form(g);
   const int fwd = route_of(g).fwd;
-  if (in_ok) *in_ok = codes_qp_ok(g.lsq_qp) ? 1 : 0;
+  if (in_ok) *in_ok = (codes_qp_ok(g.lsq_qp) && fwd != CIMQ_ROUTE_WIDE) ? 1 : 0;
   if (out_ok) *out_ok = (fwd == CIMQ_ROUTE_FWD5 || fwd == CIMQ_ROUTE_V3 || fwd == CIMQ_ROUTE_GENERAL) ? 1 : 0;
   return CIMQ_OK;
 }
@@ -938,6 +960,9 @@ static int net_walk(const cimq_net_desc* n, bool bufs, bool run, const float* x,
                                  "input", who, i, s.B, s.C, s.H, s.W);
       if (L.in_codes && !codes_qp_ok(g.lsq_qp))
         return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: x_codes needs an integer lsq_qp in [1, 254]", who, i);
+      if (L.in_codes && fwd == CIMQ_ROUTE_WIDE)
+        return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: the wide route takes no x_codes (cimq_module_codes_supported)",
+                    who, i);
     }
     // the output
     if (L.out_mode < 1 || L.out_mode > 3) return fail(CIMQ_EINVAL, "%s: layer %d: out_mode must be 1, 2 or 3", who, i);
@@ -952,6 +977,9 @@ static int net_walk(const cimq_net_desc* n, bool bufs, bool run, const float* x,
       if (!K.desc || !K.lsq) return fail(CIMQ_EINVAL, "%s: layer %d: null descriptor", who, L.consumer);
       if (fwd == CIMQ_ROUTE_DENSE)
         return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: the dense route writes no out_codes (cimq_module_codes_supported)",
+                    who, i);
+      if (fwd == CIMQ_ROUTE_WIDE)
+        return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: the wide route writes no out_codes (cimq_module_codes_supported)",
                     who, i);
       if (!codes_qp_ok(K.desc->lsq_qp))
         return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: its consumer %d reads no codes (an integer lsq_qp in [1, 254]; "
@@ -977,6 +1005,9 @@ static int net_walk(const cimq_net_desc* n, bool bufs, bool run, const float* x,
       if (is_view) {
         if (fwd == CIMQ_ROUTE_DENSE)
           return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: the dense route reads no residual view (res_stride 2 or fewer "
+                                         "source channels than out_channels)", who, i);
+        if (fwd == CIMQ_ROUTE_WIDE)
+          return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: the wide route reads no residual view (res_stride 2 or fewer "
                                          "source channels than out_channels)", who, i);
         if (fwd != CIMQ_ROUTE_GENERAL && g.Wo % 4 != 0)
           return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: a residual view on the fwd5 / v3 routes needs an output width that "

@@ -613,6 +613,77 @@ inline int dense_rows_per_chunk(const Geo& g) {
   return ((g.M + n - 1) / n + 31) / 32 * 32;
 }
 
+// ---- the channel-chunked forward (cimq_wide.hip): module-path layers whose C does not fit v3's whole-C patch ----
+struct PlanW {
+  bool ok;
+  V3 v;      // the pixel geometry alone: lw, RH, WP, nmt
+  WideP w;
+  size_t lds;  // with the quantiser's word table (every mode reserves it)
+  int groups;  // output groups of kWideOBM blocks: grid y
+};
+
+inline size_t wide_lds_bytes(const Geo& g, const V3& v, const WideP& wp) {
+  const int KS = g.KS, nkj = g.nbw * g.nba;
+  size_t n = 0;
+#define X(name, bytes) n += bytes;
+  CIMQ_WIDE_LDS(X)
+#undef X
+  return n + (size_t)kActLutMax * 2 * 4;
+}
+// channels the patch must hold when the tiles are walked in runs of tr: the widest run's span
+inline int wide_span(const Geo& g, int tr) {
+  int ncx = 0;
+  for (int i0 = 0; i0 < g.T; i0 += tr) {
+    const int i1 = std::min(g.T, i0 + tr);
+    ncx = std::max(ncx, (std::min(i1 * g.xbar, g.K) - 1) / g.KHW - (i0 * g.xbar) / g.KHW + 1);
+  }
+  return ncx;
+}
+
+inline PlanW wide_plan_compute(const Geo& g) {
+  PlanW p;
+  memset(&p, 0, sizeof(p));
+  if (tune("WIDE", 1) == 0) return p;
+  if (!g.onchw || g.variant != VAR_LIBRARY || g.NBP != 4 || g.nbw > 4) return p;
+  // the module entry points' raw activation, with a clamp maximum the staged quantiser's table holds
+  if (g.input_kind != CIMQ_INPUT_RAW_LSQ || !(g.lsq_qp >= 0.f && g.lsq_qp < 255.f)) return p;
+  if (v3_plan(g).ok || dense_plan(g)) return p;
+  // (C >= 128: below it every 3x3 layer the tables of earlier work hold keeps its route)
+  if (g.C < 128 || g.C % 16 != 0 || g.O % 16 != 0) return p;
+  if (g.P % 64 != 0 || g.Wo > 64 || 64 % g.Wo != 0 || g.Wo < 4) return p;
+  if ((g.W * 4) % 16 != 0 || g.KH > 3 || g.KW > 3 || g.KS > 2 || g.M >= (1 << 24)) return p;
+  V3& v = p.v;
+  v.lw = 0;
+  while ((1 << v.lw) < g.Wo) ++v.lw;
+  v.RH = (64 / g.Wo - 1) * g.SH + g.KH;
+  v.WP = g.W + 2 * g.PW;
+  v.nmt = g.M / 64;
+  WideP& w = p.w;
+  // the longest tile run whose chunk leaves two workgroups a CU (80 KB); a layer whose single tile does not
+  // (e.g. a 64-wide image) takes one tile per chunk in whatever the CU has
+  const size_t aim = (size_t)tune("WIDE_LDS_KB", 80) * 1024;
+  for (w.tr = g.T; w.tr >= 1; --w.tr) {
+    w.ncx = wide_span(g, w.tr);
+    if (wide_lds_bytes(g, v, w) <= aim) break;
+  }
+  if (w.tr < 1) {
+    w.tr = 1;
+    w.ncx = wide_span(g, 1);
+  }
+  w.nch = (g.T + w.tr - 1) / w.tr;
+  w.pf = tune("WIDE_PF", 1);
+  p.lds = wide_lds_bytes(g, v, w);
+  p.groups = cdiv(g.OB16, kWideOBM);
+  p.ok = p.lds <= kLdsMax - 512;
+  return p;
+}
+inline PlanW wide_plan(const Geo& g) { return memo_geo<PlanW, wide_plan_compute>(g); }
+// the slice count cim_fwd_wide_kernel fixes at compile time: equal counts of 1-bit slices (a compile-time count
+// also fixes 1-bit digits in the quantiser's table), else 0 -- the runtime-count instance
+inline int wide_cst(const Geo& g) {
+  return (g.nbw == g.nba && g.bsw == 1 && g.bsa == 1 && g.nbw >= 2 && g.nbw <= 4) ? g.nbw : 0;
+}
+
 // the shift ADC's statistics kernel (cimq_part_shift.hip) applies: interleaved 3-bit state words of
 // w2a2 / w3a3 on a v7 shape (other shift layers take the general backward)
 inline bool shift_stats_ok(const Geo& g) {
@@ -913,9 +984,13 @@ inline Route route_compute(const Geo& g) {
   const bool raw = g.input_kind == CIMQ_INPUT_RAW_LSQ, v7b = v7_bwd(g), dense = dense_plan(g);
   // forward.  cim_fwd5_kernel writes NCHW only; the Function path fuses the quantiser only where no backward
   // needs the slice words
-  r.actq = fwd_actq_ok(g) && (g.onchw || g.inference);
+  // (a wide layer's forward-only call quantises in its row staging too; its training call keeps the prologue's
+  // pass, whose backward words the general backward reads)
+  const bool wide = wide_plan(g).ok;
+  r.actq = (fwd_actq_ok(g) && (g.onchw || g.inference)) || (wide && g.inference);
   r.fwd = v3_plan(g).ok ? ((g.onchw && r.actq && f5_plan(g).ok) ? CIMQ_ROUTE_FWD5 : CIMQ_ROUTE_V3)
         : dense         ? CIMQ_ROUTE_DENSE
+        : wide          ? CIMQ_ROUTE_WIDE
                         : CIMQ_ROUTE_GENERAL;
   // backward: the recompute (the module path's forward is cim_fwd5_kernel, whose operand it needs), the first
   // conv, the fused kernel, then the v7 pair with gx5 / gw5 in either role; else dense, else general
@@ -1003,7 +1078,9 @@ inline FwdMode fwd_mode_of(const Geo& g, const Epi* ep) {
 // the module entry points' form of a geometry: NCHW output where the fast forward runs, fixed before anything
 // is asked of it ([B, P, O] through the workspace for the dense and general forwards)
 inline Geo module_form(Geo g) {
-  g.onchw = v3_plan(g).ok ? 1 : 0;
+  Geo t = g;
+  t.onchw = 1;  // (wide_plan asks for the module's layout itself)
+  g.onchw = (v3_plan(g).ok || wide_plan(t).ok) ? 1 : 0;
   return g;
 }
 
@@ -1043,8 +1120,8 @@ inline CtxLayout ctx_layout_compute(const Geo& g) {
   L.wbytes = o;
   // forward slice bytes (none in a forward-only call whose forward quantises the activation itself; a shift layer
   // keeps the region, unwritten there: its ctx_bytes are what they were before its forward staged the quantiser,
-  // and so does a w4a4 layer on the stateless word-pair forward, v7_w44_eval)
-  L.xcode = o; o = align256(o + ((g.inference && r.actq && g.variant == VAR_LIBRARY && !v7_w44_eval(g)) ? (size_t)0 : (size_t)g.Nin * g.NBP));
+  // and so does a w4a4 layer on the stateless word-pair forward, v7_w44_eval, and a layer on the wide forward)
+  L.xcode = o; o = align256(o + ((g.inference && r.actq && g.variant == VAR_LIBRARY && !v7_w44_eval(g) && r.fwd != CIMQ_ROUTE_WIDE) ? (size_t)0 : (size_t)g.Nin * g.NBP));
   if (g.inference) {
     // forward only (CIMQ_OPT_INFERENCE): the ctx ends here -- no backward slice words, no code table, no state;
     // their offsets point at the end and nothing is written through them
@@ -1109,7 +1186,8 @@ inline WsLayout ws_layout_compute(const Geo& g) {
     W.gw_slab = W.ga_slab = W.gb_slab = W.ss_slab = W.qtab = 0;
     W.lsq_part = o; o = align256(o + sizeof(float) * std::max(kLsqParts, g.B * g.H));
     W.gaq = W.gapart = W.wpart = o;
-    W.bpo = o; o = align256(o + (r.fwd != CIMQ_ROUTE_GENERAL ? (size_t)0 : sizeof(float) * (size_t)g.M * g.O));
+    // (the wide forward writes NCHW itself; the region stays, unwritten, so that the sizes are what they were)
+    W.bpo = o; o = align256(o + ((r.fwd != CIMQ_ROUTE_GENERAL && r.fwd != CIMQ_ROUTE_WIDE) ? (size_t)0 : sizeof(float) * (size_t)g.M * g.O));
     W.gxu = W.total = o;
     return W;
   }
@@ -1272,6 +1350,9 @@ inline void prof_end(int slot, hipStream_t s) {
 int launch_fwd_any(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, int* ps_dbg,
                    float* adc_dbg, hipStream_t s,
                    const ActQ* aq = nullptr, const Epi* ep = nullptr);
+// cimq_part_wide.hip: the channel-chunked module forward (wide_plan); aq: fp32 x for the forward-only modes
+int launch_wide(const Geo& g, const PlanW& p, uint8_t* ctx, const float* sw, const float* sa, float* out,
+                hipStream_t s, const ActQ* aq, const Epi* ep = nullptr);
 // cimq_part_fwd5.hip: the w3a3 module forward on the slice-planar patch (f5_plan)
 int launch_fwd5(const Geo& g, const Plan5& p, uint8_t* ctx, const float* sw, const float* sa, float* out,
                 hipStream_t s, const ActQ* aq, const Epi* ep = nullptr);

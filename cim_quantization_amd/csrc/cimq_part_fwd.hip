@@ -128,6 +128,10 @@ int launch_fwd_any(const Geo& g, uint8_t* ctx, const float* sw, const float* sa,
   const Route r = route_of(g);
   if (aq && (!r.actq || ps_dbg)) return fail(CIMQ_EINVAL, "internal: fused activation quantiser off its plan");
   if (ep && (ps_dbg || !g.inference)) return fail(CIMQ_EINVAL, "internal: output epilogue off the forward-only path");
+  if (r.fwd == CIMQ_ROUTE_WIDE) {
+    if (ps_dbg) return fail(CIMQ_EINVAL, "internal: the debug hook on the wide forward");
+    return launch_wide(g, wide_plan(g), ctx, sw, sa, out, s, aq, ep);
+  }
   if (r.fwd == CIMQ_ROUTE_DENSE) {
     // the dense GEMM path (its state words feed the dense backward); the debug hook then reruns
     // the general kernel for the partial sums (same out values)

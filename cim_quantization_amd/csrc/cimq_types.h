@@ -323,4 +323,23 @@ __host__ __device__ inline size_t a16(size_t v) { return (v + 15) & ~(size_t)15;
   X(cfl, (size_t)TT * nkj * NOB * 16 * 4)         /* coef, same order */                                 \
   X(ckl, a16((size_t)3 * g.nbw * g.nba * 4))      /* [3][nkj] (Params::ckj) */
 
+// ... of the channel-chunked forward (cimq_wide.hip; wide_plan): the pixel geometry is a V3's (lw, RH, WP, nmt)
+struct WideP {
+  int tr;   // crossbar tiles per channel chunk (the last chunk may hold fewer)
+  int ncx;  // channels the LDS patch holds: the widest chunk's span
+  int nch;  // channel chunks: ceil(T / tr)
+  int pf;   // compile-time slice counts: the next tile's weight fragments prefetched in registers
+};
+constexpr int kWideOBM = 4;  // 16-channel output blocks per workgroup (tables sized for four, zero past the last)
+
+// cim_fwd_wide_kernel's dynamic LDS, as CIMQ_FWD3_LDS: in terms of g (Geo), v (V3), wp (WideP), KS, nkj; the fused
+// quantiser's word table follows the last region
+#define CIMQ_WIDE_LDS(X)                                                                                  \
+  X(patch, a16((size_t)wp.ncx * v.RH * v.WP * 4)) /* [ncx][RH][WP] slice words of one channel chunk */    \
+  X(ptab, (size_t)wp.tr * KS * 64 * 4)             /* [tr][KS*64] patch word offsets of the chunk's tiles */ \
+  X(wfl, (size_t)g.nbw * kWideOBM * KS * 1024)     /* [k][ob][ks][64] weight fragments of one tile */      \
+  X(prm, (size_t)nkj * kWideOBM * 16 * 16)         /* [j][k][64] int4 thresholds */                        \
+  X(cfl, (size_t)nkj * kWideOBM * 16 * 4)          /* coef, same order */                                  \
+  X(ckl, a16((size_t)3 * g.nbw * g.nba * 4))       /* [3][nkj] (Params::ckj) */
+
 }  // namespace cimq

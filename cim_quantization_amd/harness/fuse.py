@@ -1,5 +1,5 @@
-"""Evaluation of a harness ResNet with each BatchNorm folded into a per-channel affine and, together with
-the residual add and the ReLU, applied inside the CiM conv's forward kernel
+"""Evaluation of a harness ResNet (or VGG: ``FusedEval._forward_vgg``) with each BatchNorm folded into a per-channel
+affine and, together with the residual add and the ReLU, applied inside the CiM conv's forward kernel
 (``Conv2dLSQCiM.forward_fused`` -> cimq_module_forward_epilogue): one library launch per conv where
 ``ResNet.forward`` runs the conv and five or six elementwise torch kernels.
 
@@ -22,7 +22,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .models import ResNet
+from .models import VGG, ResNet
 
 __all__ = ["fold_bn", "FusedEval"]
 
@@ -263,8 +263,8 @@ class FusedEval(nn.Module):
 
     def __init__(self, model, codes=False, net=False):
         super().__init__()
-        if not isinstance(model, ResNet):
-            raise TypeError("FusedEval wraps a harness.models.ResNet")
+        if not isinstance(model, (ResNet, VGG)):
+            raise TypeError("FusedEval wraps a harness.models.ResNet or a harness.models.VGG")
         self.model = model
         self.codes = bool(codes)
         self.net = bool(net)
@@ -400,9 +400,50 @@ class FusedEval(nn.Module):
         y = F.avg_pool2d(y, y.shape[3]).flatten(1)
         return m.linear(y)
 
+    def _forward_vgg(self, x):
+        """A ``harness.models.VGG``: every conv of ``features`` runs ``forward_fused`` with the BatchNorm behind it
+        folded and the ReLU in the epilogue; the max-pools, the flatten and the classifier stay torch operations.
+        ``codes=True``: a conv whose only reader is the next conv hands it codes alone where ``codes_ready`` says the
+        producer writes and the consumer reads them -- the rule of ``_forward_codes``; an edge into a max-pool stays
+        fp32.  In VGG7 every such consumer has 128 channels or more (the wide route, which reads no codes), so all
+        its edges stay fp32; a narrower ``VGG(plan=...)`` gets code edges."""
+        mods = list(self.model.features)
+        names = {id(mod): "features.%d" % k for k, mod in enumerate(mods)}
+        is_conv = lambda mod: isinstance(mod, nn.Conv2d) or hasattr(mod, "forward_fused")  # noqa: E731
+        self.code_edges = []
+        y, i = x, 0  # y: the current activation, fp32 or (handed by the conv before) the consumer's codes
+        while i < len(mods):
+            mod = mods[i]
+            if not is_conv(mod):
+                y = mod(y)
+                i += 1
+                continue
+            if not (i + 2 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm2d) and isinstance(mods[i + 2], nn.ReLU)):
+                raise RuntimeError("FusedEval: a VGG conv without its BatchNorm and ReLU behind it")
+            bn = mods[i + 1]
+            nxt = mods[i + 3] if i + 3 < len(mods) and is_conv(mods[i + 3]) else None
+            hand = False
+            if self.codes and nxt is not None and hasattr(mod, "codes_ready") and hasattr(nxt, "codes_ready"):
+                probe = torch.empty(1, dtype=torch.uint8, device=y.device).expand(_out_shape(mod, y.shape))
+                hand = mod.codes_ready(y)[1] and nxt.codes_ready(probe)[0]
+            if hand:
+                scale, shift = self.tables(bn)
+                y = mod.forward_fused(y, scale, shift, relu=True, out_quant=nxt, keep_float=False)
+                self.code_edges.append((names[id(mod)], names[id(nxt)], "codes"))
+            else:
+                if y.dtype == torch.uint8 and not (hasattr(mod, "fused_epilogue_ready") and mod.fused_epilogue_ready(y)):
+                    raise RuntimeError("FusedEval: a conv stopped taking the library path during a forward")
+                y = self._conv(mod, bn, y)
+            i += 3
+        return self.model.classifier(y.flatten(1))
+
     def forward(self, x):
         if torch.is_grad_enabled():
             raise RuntimeError("FusedEval is evaluation only: call it under torch.no_grad()")
+        if isinstance(self.model, VGG):
+            if self.net:  # (a plan of wide layers and max-pools: a follow-up)
+                self.net_used, self.net_reason = False, "a VGG runs in the loop: its max-pools are torch operations"
+            return self._forward_vgg(x)
         if self.net:
             y = self._forward_net(x)
             self.net_used = y is not None

@@ -10,7 +10,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-__all__ = ["resnet20", "resnet32", "resnet44", "resnet56", "resnet110", "resnet1202", "ResNet"]
+__all__ = ["resnet20", "resnet32", "resnet44", "resnet56", "resnet110", "resnet1202", "ResNet", "VGG",
+           "cifar10_vggsmall"]
 
 
 class PadShortcut(nn.Module):
@@ -67,8 +68,40 @@ class ResNet(nn.Module):
         return self.linear(y)
 
 
-def _make(n, pretrained=False, pretrained_location=None):
-    model = ResNet(n)
+VGG7 = (128, 128, "M", 256, 256, "M", 512, 512, "M")
+
+
+class VGG(nn.Module):
+    """VGG-small (VGG7) for 32 x 32 inputs with the module names of the reference's models/cifar10/vgg.py, so its
+    state_dict keys load: ``features`` is one Sequential of conv (3 x 3, pad 1, no bias), BatchNorm, ReLU triples
+    with a 2 x 2 max-pool after every second triple (features.0 / .1, features.3 / .4, pool at .6, ...), and
+    ``classifier`` the Linear over the flattened 512 x 4 x 4 map.  Convs start from He's fan-out normal, the
+    classifier from N(0, 0.01) with zero bias."""
+
+    def __init__(self, plan=VGG7, num_classes=10):
+        super().__init__()
+        mods, cin, side = [], 3, 32
+        for width in plan:
+            if width == "M":
+                mods.append(nn.MaxPool2d(kernel_size=2, stride=2))
+                side //= 2
+                continue
+            mods += [nn.Conv2d(cin, width, 3, padding=1, bias=False), nn.BatchNorm2d(width), nn.ReLU(inplace=True)]
+            cin = width
+        self.features = nn.Sequential(*mods)
+        self.classifier = nn.Linear(cin * side * side, num_classes)
+        for m in self.modules():
+            if isinstance(m, nn.Conv2d):
+                nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
+            elif isinstance(m, nn.Linear):
+                nn.init.normal_(m.weight, 0.0, 0.01)
+                nn.init.zeros_(m.bias)
+
+    def forward(self, x):
+        return self.classifier(self.features(x).flatten(1))
+
+
+def _load_pretrained(model, pretrained, pretrained_location):
     if pretrained:
         if not pretrained_location:
             raise RuntimeError("pretrained weights need a local file (pretrained_location); there is no download")
@@ -76,6 +109,14 @@ def _make(n, pretrained=False, pretrained_location=None):
         sd = sd.get("state_dict", sd)
         model.load_state_dict({k[7:] if k.startswith("module.") else k: v for k, v in sd.items()})
     return model
+
+
+def cifar10_vggsmall(pretrained=False, pretrained_location=None):
+    return _load_pretrained(VGG(), pretrained, pretrained_location)
+
+
+def _make(n, pretrained=False, pretrained_location=None):
+    return _load_pretrained(ResNet(n), pretrained, pretrained_location)
 
 
 def resnet20(pretrained=False, **kw):

@@ -247,7 +247,9 @@ enum {
   CIMQ_ROUTE_DENSE = 8,    /* the dense 1x1 path */
   CIMQ_ROUTE_R6 = 9,       /* grad_x and grad_w in cim_bwd_r6_kernel from RECOMPUTED partial sums (the forward
                               writes no state words; round 6, ABI 13; only under CIMQ_OPT_RECOMPUTE since ABI 14) */
-  CIMQ_ROUTE_NONE = 10     /* route[1] / route[2] under CIMQ_OPT_INFERENCE: there is no backward.  Since ABI 15 */
+  CIMQ_ROUTE_NONE = 10,    /* route[1] / route[2] under CIMQ_OPT_INFERENCE: there is no backward.  Since ABI 15 */
+  CIMQ_ROUTE_WIDE = 11     /* forward: cim_fwd_wide_kernel, the channel-chunked forward of 3x3 module layers from 128
+                              input channels up (cimq_wide_abi() == 1); their backward stays CIMQ_ROUTE_GENERAL */
 };
 int cimq_module_route(const cimq_conv_desc* d, int* route);
 
@@ -265,6 +267,22 @@ int cimq_w4a4_eval_abi(void);
  *            weight side is prepared (q->wprep) is one launch with no pass over x before it; else 0.
  * Returns 0, CIMQ_EINVAL for a NULL argument, or the status of a descriptor the module entry points refuse. */
 int cimq_module_forward_form(const cimq_conv_desc* d, int form[2]);
+
+/* 1 where module layers whose input channels do not fit the fast forward's whole-C LDS patch (C >= 128, C and O
+ * multiples of 16, the fast path's pixel geometry, the library ADC, at most four slices a side) run
+ * cim_fwd_wide_kernel: route[0] is CIMQ_ROUTE_WIDE, the training forward writes NCHW in one launch after the
+ * prologue, and a prepared forward-only layer -- plain or with an epilogue -- is one launch.  The route takes no
+ * activation codes and no residual view: cimq_module_codes_supported answers 0 / 0, and cimq_module_forward_codes /
+ * cimq_net_forward return CIMQ_EUNSUPPORTED before any launch.  Every size (cimq_query_sizes, cimq_sizes) is what it
+ * was: the [B, P, O] workspace region and a forward-only call's slice-word region simply go unwritten.
+ * CIMQ_ABI_VERSION / _MINOR and the other availability numbers are unchanged. */
+int cimq_wide_abi(void);
+
+/* The plan of that forward for `d`, without device work: out[0] 1 where the route applies (else 0, and the rest 0),
+ * out[1] the channel chunks the LDS patch is staged in per 64-pixel m-tile, out[2] the output groups of up to four
+ * 16-channel blocks (the grid's y), out[3] the crossbar tiles.  Returns 0, CIMQ_EINVAL for a NULL argument, or the
+ * status of a descriptor the module entry points refuse. */
+int cimq_module_wide_plan(const cimq_conv_desc* d, int out[4]);
 int cimq_module_shift_forward(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* x, const float* weight,
                               const float* alpha_act, const float* alpha_weight, const float* alpha_cim,
                               const float* beta_cim, const int8_t* binary_mask, const float* signed_act, float* out,
