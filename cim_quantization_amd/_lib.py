@@ -41,6 +41,8 @@ CIMQ_OPT_RECOMPUTE = 1  # cimq_conv_desc.options (ABI 14)
 CIMQ_OPT_INFERENCE = 4  # forward only: nothing written that a backward would read (ABI 15; bit 2 is refused)
 CIMQ_EPI_RELU = 1  # cimq_epilogue.flags (ABI 16)
 CIMQ_CODES_NO_FLOAT = 1  # cimq_act_codes.flags (ABI 16, minor 1)
+CIMQ_POOL_MAX2 = 2  # cimq_module_forward_pool's pool / cimq_net_ext.pool entries (cimq_pool_abi() == 1)
+NET_HEAD_FLATTEN = 1  # cimq_net_ext.head_flags: CIMQ_NET_HEAD_FLATTEN
 
 # every symbol include/cimq.h declares
 EXPORTED_SYMBOLS = (
@@ -69,11 +71,16 @@ EXPORTED_SYMBOLS = (
     "cimq_module_shift_forward",
     "cimq_module_shift_backward",
     "cimq_module_forward_epilogue",
+    "cimq_pool_abi",
+    "cimq_module_pool_supported",
+    "cimq_module_forward_pool",
     "cimq_module_codes_supported",
     "cimq_module_forward_codes",
     "cimq_net_abi",
     "cimq_net_sizes",
     "cimq_net_forward",
+    "cimq_net_sizes_ex",
+    "cimq_net_forward_ex",
     "cimq_alpha_init",
     "cimq_shift_forward",
     "cimq_shift_backward",
@@ -170,6 +177,13 @@ class NetDesc(ctypes.Structure):
     _fields_ = [("n_layers", ctypes.c_int32), ("n_slots", ctypes.c_int32), ("layers", ctypes.POINTER(NetLayer)),
                 ("head", ctypes.POINTER(NetHead)), ("B", ctypes.c_int32), ("C", ctypes.c_int32),
                 ("H", ctypes.c_int32), ("W", ctypes.c_int32)]
+
+
+class NetExt(ctypes.Structure):
+    """Mirror of ``cimq_net_ext`` (cimq_pool_abi() == 1)."""
+
+    _fields_ = [("pool", ctypes.POINTER(ctypes.c_int32)), ("head_flags", ctypes.c_int32),
+                ("reserved", ctypes.c_int32 * 3)]
 
 
 NET_HEAD_MAX_C = 8192  # CIMQ_NET_HEAD_MAX_C
@@ -298,6 +312,20 @@ def _bind(lib):
     lib.cimq_net_forward.restype = ctypes.c_int
     lib.cimq_net_forward.argtypes = [ctypes.POINTER(NetDesc), _VP, ctypes.POINTER(_VP), ctypes.POINTER(_VP), _VP, _VP,
                                      _VP]
+    if hasattr(lib, "cimq_pool_abi"):
+        lib.cimq_pool_abi.restype = ctypes.c_int
+        lib.cimq_pool_abi.argtypes = []
+        lib.cimq_module_pool_supported.restype = ctypes.c_int
+        lib.cimq_module_pool_supported.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_int)]
+        lib.cimq_module_forward_pool.restype = ctypes.c_int
+        lib.cimq_module_forward_pool.argtypes = ([ctypes.POINTER(ConvDesc), ctypes.POINTER(LsqDesc)] + [_VP] * 8 +
+                                                 [ctypes.POINTER(Epilogue), ctypes.c_int] + [_VP] * 4)
+        lib.cimq_net_sizes_ex.restype = ctypes.c_int
+        lib.cimq_net_sizes_ex.argtypes = ([ctypes.POINTER(NetDesc)] + [ctypes.POINTER(ctypes.c_size_t)] * 3 +
+                                          [ctypes.POINTER(NetExt)])
+        lib.cimq_net_forward_ex.restype = ctypes.c_int
+        lib.cimq_net_forward_ex.argtypes = [ctypes.POINTER(NetDesc), _VP, ctypes.POINTER(_VP), ctypes.POINTER(_VP), _VP,
+                                            _VP, _VP, ctypes.POINTER(NetExt)]
     lib.cimq_alpha_init.restype = ctypes.c_int
     lib.cimq_alpha_init.argtypes = [ctypes.POINTER(ConvDesc)] + [_VP] * 10
     lib.cimq_shift_forward.restype = ctypes.c_int
@@ -461,6 +489,28 @@ def module_wide_plan(desc: ConvDesc):
     f = (ctypes.c_int * 4)()
     check(load().cimq_module_wide_plan(ctypes.byref(desc), f), "cimq_module_wide_plan")
     return tuple(f)
+
+
+def pool_abi() -> int:
+    """cimq_pool_abi(): 1 where the pooled store and the cimq_net_*_ex calls exist."""
+    return int(load().cimq_pool_abi())
+
+
+def module_pool_supported(desc: ConvDesc) -> bool:
+    """Whether cimq_module_forward_pool takes ``desc`` with CIMQ_POOL_MAX2 -- cimq_module_pool_supported."""
+    ok = ctypes.c_int(0)
+    check(load().cimq_module_pool_supported(ctypes.byref(desc), ctypes.byref(ok)), "cimq_module_pool_supported")
+    return bool(ok.value)
+
+
+def make_net_ext(pool=None, head_flags=0) -> NetExt:
+    """``pool``: None, or one entry (0 / CIMQ_POOL_MAX2) per layer of the plan.  The entries' array is kept alive on
+    the returned struct."""
+    e = NetExt()
+    e._pool = (ctypes.c_int32 * len(pool))(*[int(v) for v in pool]) if pool is not None else None
+    e.pool = ctypes.cast(e._pool, ctypes.POINTER(ctypes.c_int32)) if e._pool is not None else None
+    e.head_flags = int(head_flags)
+    return e
 
 
 def query_sizes(desc: ConvDesc) -> Sizes:

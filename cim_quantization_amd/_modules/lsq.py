@@ -18,7 +18,8 @@ import torch
 import torch.nn.functional as F
 
 from ..functional import (alpha_cim_init, cim_conv2d_lsq, cim_conv2d_lsq_shift, cim_module_conv,  # noqa: F401
-                          act_codes_of, cim_module_conv_codes, cim_module_conv_epilogue, cim_module_shift_conv, get_adcless_cim_output, get_analog_partial_sums_autograd_ver2,
+                          act_codes_of, cim_module_conv_codes, cim_module_conv_epilogue, cim_module_conv_pool,
+                          cim_module_shift_conv, get_adcless_cim_output, get_analog_partial_sums_autograd_ver2,
                           conv_out_hw, get_cim_output_signed, inference_call, inference_weights, lsq_quantize,
                           module_descs, module_shift_supported, qconv2d)
 from ._quan_base import (_ActQ, _Conv2dQ, _Conv2dQCiM, _LinearQ, Qmodes, grad_scale,  # noqa: F401
@@ -248,7 +249,21 @@ class Conv2dLSQCiM(_Conv2dQCiM):
             return False, False
         return self._codes_desc(x.shape)
 
-    def forward_fused(self, x, scale, shift, residual=None, relu=False, *, out_quant=None, keep_float=True):
+    def pool_ready(self, x):
+        """Whether ``forward_fused(..., pool=2)`` takes this layer for input ``x``: ``fused_epilogue_ready``, a
+        library-ADC layer, and what cimq_module_pool_supported answers for x's shape (cached per shape): the wide
+        forward route with an output at most 32 wide.  Only x's shape and device matter."""
+        if not self.fused_epilogue_ready(x) or self.adc_shift or self.stochastic_quant:
+            return False
+        key = tuple(x.shape)
+        hit = getattr(self, "_pool_ok", None)
+        if hit is None or hit[0] != key:
+            from .. import _lib
+            desc, _ = module_descs(self, key, inference=True)
+            hit = self._pool_ok = (key, _lib.module_pool_supported(desc))
+        return hit[1]
+
+    def forward_fused(self, x, scale, shift, residual=None, relu=False, *, out_quant=None, keep_float=True, pool=None):
         """Evaluation only: ``forward(x)`` with a per-channel affine (a folded BatchNorm: ``scale``, ``shift``,
         [out_channels] fp32), an optional ``residual`` (the output's shape; made contiguous fp32 if it is not) and an
         optional ReLU applied in the forward kernel's registers before the store -- bit for bit
@@ -259,7 +274,17 @@ class Conv2dLSQCiM(_Conv2dQCiM):
         ``torch.uint8`` ``x`` is this layer's input as codes (``act_codes``), and the output is bit for bit that of
         any fp32 input with those codes; ``out_quant=next_conv`` also returns the output's codes for that layer,
         written by the kernel that stores the output -- ``(output, codes)``, or with ``keep_float=False`` the codes
-        alone.  ``codes_ready`` says which of the two this layer supports."""
+        alone.  ``codes_ready`` says which of the two this layer supports.
+        ``pool=2``: the storing kernel writes the 2x2 / stride-2 max pool of those values instead
+        (cim_module_conv_pool): [B, O, Ho/2, Wo/2], bit for bit ``F.max_pool2d(forward_fused(...), 2, 2)``; the
+        residual keeps the unpooled shape.  Raises where ``pool_ready`` does not hold, and with codes on either side."""
+        if pool is not None and pool != 2:
+            raise ValueError("Conv2dLSQCiM.forward_fused: pool must be None or 2")
+        if pool and (out_quant is not None or torch.is_tensor(x) and x.dtype == torch.uint8):
+            raise ValueError("Conv2dLSQCiM.forward_fused: pool takes fp32 in and writes fp32 out (no out_quant, no codes)")
+        if pool and not self.pool_ready(x):
+            raise RuntimeError("Conv2dLSQCiM.forward_fused(pool=2) needs the steady-state library path, the library "
+                               "ADC and a layer on the wide forward route at most 32 output columns wide (pool_ready)")
         if not self.fused_epilogue_ready(x):
             raise RuntimeError("Conv2dLSQCiM.forward_fused needs the steady-state library path (both first-step "
                                "initialisations done, adcbits != 0, ROCm tensors) and bias=None")
@@ -273,6 +298,11 @@ class Conv2dLSQCiM(_Conv2dQCiM):
         if x.dtype != torch.uint8 and out_quant is None:
             if not keep_float:
                 raise ValueError("Conv2dLSQCiM.forward_fused: keep_float=False needs out_quant")
+            if pool:
+                return cim_module_conv_pool(
+                    x, self.weight, self.alpha_act, self.alpha_weight, self.alpha_cim, self.binary_mask,
+                    self.signed_act, *self.layer_config(), scale, shift, residual=residual, relu=relu, pool=pool,
+                    wprep=wprep, recompute=self.recompute_psum)
             return cim_module_conv_epilogue(
                 x, self.weight, self.alpha_act, self.alpha_weight, self.alpha_cim, self.binary_mask, self.signed_act,
                 *self.layer_config(), scale, shift, residual=residual, relu=relu,

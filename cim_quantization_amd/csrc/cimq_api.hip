@@ -605,11 +605,17 @@ static bool codes_qp_ok(float qp) { return qp >= 1.f && qp <= 254.f && qp == (fl
 static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* x, const float* weight,
                                const float* alpha_act, const float* alpha_weight, const float* alpha_cim,
                                const float* beta_cim, const int8_t* binary_mask, const float* signed_act, float* out,
-                               void* ctx, void* ws, void* stream, const Epi* ep = nullptr, bool dry = false) {
+                               void* ctx, void* ws, void* stream, const Epi* ep = nullptr, bool dry = false,
+                               int pool = 0, bool stage8 = false) {
   // dry (cimq_net_forward's validation pass): every refusal below, no launch
+  // stage8 (a layer of a cimq_net_forward_ex plan): a w8a8 layer that can (fwd8_stage_ok) quantises x in its kernel's
+  // row staging -- the prologue's words, one launch fewer; a hint, ignored where it does not apply
+  // pool (cimq_module_forward_pool, a pooled layer of cimq_net_forward_ex; CIMQ_POOL_MAX2 or 0, with ep): out is the
+  // 2x2 / stride-2 max pool of the epilogue's values, [B, O, Ho/2, Wo/2]
   Geo g;
   LsqArgs la;
   CIMQ_TRY(module_geo(d, q, &g, &la, beta_cim != nullptr));
+  if (pool && (pool != CIMQ_POOL_MAX2 || !ep)) return fail(CIMQ_EINVAL, "internal: a pooled forward off its entry point");
   // the residual's extent: out's geometry, or the view's own (Epi::rview, cimq_net_forward alone)
   const ResView rv = ep ? res_view(ep->rvw0, ep->rvw1) : ResView{};
   const uintptr_t res_bytes = !ep ? 0 : ep->rvw1 ? (uintptr_t)g.B * rv.cr * rv.h * rv.w * 4 : (uintptr_t)g.M * g.O * 4;
@@ -617,7 +623,7 @@ static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
     if (!g.inference) return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: a CIMQ_OPT_INFERENCE descriptor only");
     if (ep->res && out) {
       const uintptr_t r0 = reinterpret_cast<uintptr_t>(ep->res), o0 = reinterpret_cast<uintptr_t>(out);
-      const uintptr_t nb = (uintptr_t)g.M * g.O * 4;
+      const uintptr_t nb = (uintptr_t)g.M * g.O * (pool ? 1 : 4);  // (pooled: a quarter of the residual's extent)
       if (r0 < o0 + nb && o0 < r0 + res_bytes)
         return fail(CIMQ_EINVAL, "cimq_module_forward_epilogue: residual overlaps out");
     }
@@ -662,9 +668,16 @@ static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
       (!out && !(ep && ep->nofloat)) || !ctx || !ws)
     return fail(CIMQ_EINVAL, "null pointer argument");
   CIMQ_TRY(check_alpha(g, &la, alpha_cim, nullptr, false));
+  if (pool) {  // what cimq_module_pool_supported answers, with its reason
+    const char* why = nullptr;
+    if (route_of(g).fwd != CIMQ_ROUTE_WIDE) why = "the layer is off the wide route (cimq_module_route)";
+    else (void)wide_pool_ok(g, wide_plan(g), &why);
+    if (why) return fail(CIMQ_EUNSUPPORTED, "cimq_module_forward_pool: %s (cimq_module_pool_supported)", why);
+  }
   if (dry) return CIMQ_OK;
   const bool has_alpha = la.nbits_alpha > 0;
   const Route r = route_of(g);
+  const bool q8 = stage8 && ep && x && !xq && !oq && !ep->nofloat && !ep->rvw1 && !pool && fwd8_stage_ok(g);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   uint8_t* c = reinterpret_cast<uint8_t*>(ctx);
   CtxLayout L = ctx_layout(g);
@@ -679,7 +692,7 @@ static int module_forward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, 
       nwblk = prep_wblocks(a);
     }
     if (g.wbase) nwblk = 0;  // weight side prepared (cimq_module_prepare): the activation quantiser only
-    if (r.actq) a.nact_blocks = 0;  // the forward's row staging quantises (stage_rows_q)
+    if (r.actq || q8) a.nact_blocks = 0;  // the forward's row staging quantises (stage_rows_q, stage_rows_q8)
     if (a.nact_blocks + nwblk == 0) goto prepared;
     {
     const int slot = prof_begin(KID_PREP_ACT, g, s);
@@ -711,6 +724,8 @@ prepared:
     ep = &epk;
   }
   // (the fast forward writes NCHW, g.onchw; the dense one's P = 1: NCHW is [B, P, O])
+  if (pool) return launch_wide(g, wide_plan(g), c, scal + 1, scal, out, s, &aq, ep, true);
+  if (q8) return launch_fwd8_staged(g, c, scal + 1, scal, out, s, &aq, ep);
   if (r.fwd != CIMQ_ROUTE_GENERAL)
     return launch_fwd_any(g, c, scal + 1, scal, out, nullptr, nullptr, s, r.actq ? &aq : nullptr, ep);
   // general kernels write [B, P, O]; the module returns NCHW
@@ -807,6 +822,32 @@ int cimq_module_forward_epilogue(const cimq_conv_desc* d, const cimq_lsq_desc* q
                              out, ctx, ws, stream, &ep);
 }
 
+int cimq_pool_abi(void) { return 1; }
+
+int cimq_module_pool_supported(const cimq_conv_desc* d, int* ok) {
+  Geo g;
+  CIMQ_TRY(make_geo(d, &g));
+  if (!ok) return fail(CIMQ_EINVAL, "null ok");
+  if (g.input_kind != CIMQ_INPUT_RAW_LSQ) return fail(CIMQ_EINVAL, "module entry points take the raw activation");
+  g = module_form(g);
+  *ok = (g.inference && route_of(g).fwd == CIMQ_ROUTE_WIDE && wide_pool_ok(g, wide_plan(g))) ? 1 : 0;
+  return CIMQ_OK;
+}
+
+int cimq_module_forward_pool(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* x, const float* weight,
+                             const float* alpha_act, const float* alpha_weight, const float* alpha_cim,
+                             const float* beta_cim, const int8_t* binary_mask, const float* signed_act,
+                             const cimq_epilogue* epi, int pool, float* out, void* ctx, void* ws, void* stream) {
+  static const char who[] = "cimq_module_forward_pool";
+  CIMQ_TRY(check_forward_only(who, d));
+  CIMQ_TRY(check_epilogue(who, epi, alpha_cim, beta_cim));
+  if (pool != 0 && pool != CIMQ_POOL_MAX2) return fail(CIMQ_EINVAL, "%s: pool must be 0 or CIMQ_POOL_MAX2 (it is %d)", who, pool);
+  if (pool && beta_cim) return fail(CIMQ_EUNSUPPORTED, "%s: the shift ADC's layers run off the wide route: no pooled store", who);
+  const Epi ep = epi_of(epi);
+  return module_forward_impl(d, q, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act,
+                             out, ctx, ws, stream, &ep, false, pool);
+}
+
 int cimq_module_codes_supported(const cimq_conv_desc* d, int* in_ok, int* out_ok) {
   if (!d) return fail(CIMQ_EINVAL, "null descriptor");
   cimq_conv_desc di = *d;  // (the call takes forward-only descriptors alone: answer for that form)
@@ -823,14 +864,15 @@ int cimq_module_codes_supported(const cimq_conv_desc* d, int* in_ok, int* out_ok
 
 }  // extern "C"
 
-// cimq_module_forward_codes, and one layer of cimq_net_forward: view (the net alone) makes epi->residual a view of
+// cimq_module_forward_codes, and one layer of cimq_net_forward: pool and stage8 (the net alone) as
+// module_forward_impl's; view (the net alone) makes epi->residual a view of
 // a larger tensor (Epi::rvw0 / rvw1); dry (the net's validation pass) stops before the first launch
 static int forward_codes_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, const cimq_act_codes* io,
                               const float* x, const float* weight, const float* alpha_act,
                               const float* alpha_weight, const float* alpha_cim, const float* beta_cim,
                               const int8_t* binary_mask, const float* signed_act, const cimq_epilogue* epi,
                               float* out, void* ctx, void* ws, void* stream, const ResView* view = nullptr,
-                              bool dry = false) {
+                              bool dry = false, int pool = 0, bool stage8 = false) {
   // (the descriptor-independent refusals first; the epilogue's are cimq_module_forward_epilogue's own)
   static const char who[] = "cimq_module_forward_codes";
   CIMQ_TRY(check_forward_only(who, d));
@@ -842,7 +884,7 @@ static int forward_codes_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, c
     Epi ep = epi_of(epi);
     if (view) set_res_view(&ep, view->c0, view->cr, view->s, view->h, view->w);
     return module_forward_impl(d, q, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act,
-                               out, ctx, ws, stream, &ep, dry);
+                               out, ctx, ws, stream, &ep, dry, pool, stage8);
   }
   if ((io->flags & CIMQ_CODES_NO_FLOAT) && !io->out_codes)
     return fail(CIMQ_EINVAL, "cimq_module_forward_codes: CIMQ_CODES_NO_FLOAT needs out_codes");
@@ -863,7 +905,7 @@ static int forward_codes_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q, c
   ep.oqp = io->out_qp;
   if (view) set_res_view(&ep, view->c0, view->cr, view->s, view->h, view->w);
   return module_forward_impl(d, q, x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act,
-                             out, ctx, ws, stream, &ep, dry);
+                             out, ctx, ws, stream, &ep, dry, pool, stage8);
 }
 
 // ---- cimq_net_*: a plan of fused conv layers, their slots and the head, run in one call ----
@@ -877,7 +919,7 @@ struct NetSlot {
 
 // One layer's call (forward_codes_impl's arguments from the plan); view: the residual as a view, or null
 static int net_layer_call(const cimq_net_desc* n, int i, const float* x, void* const* sf, void* const* sc,
-                          const ResView* view, void* ws, void* stream, bool dry) {
+                          const ResView* view, void* ws, void* stream, bool dry, int pool, bool stage8) {
   const cimq_net_layer& L = n->layers[i];
   cimq_epilogue e;
   e.scale = L.scale;
@@ -902,16 +944,25 @@ static int net_layer_call(const cimq_net_desc* n, int i, const float* x, void* c
   }
   float* out = (L.out_mode & 1) ? reinterpret_cast<float*>(sf[L.out_slot]) : nullptr;
   return forward_codes_impl(L.desc, L.lsq, &io, xin, L.weight, L.alpha_act, L.alpha_weight, L.alpha_cim, L.beta_cim,
-                            L.binary_mask, L.signed_act, &e, out, L.ctx, ws, stream, view, dry);
+                            L.binary_mask, L.signed_act, &e, out, L.ctx, ws, stream, view, dry, pool, stage8);
 }
 
 // The whole validation of a plan, in layer order, and with ``run`` its launches.  bufs: the caller's buffers are
 // there to be checked (cimq_net_forward) -- each layer's own call is then made dry, so that every refusal it has
 // comes before the first launch.  fb / cb / wsb: cimq_net_sizes' outputs (may be null).
 static int net_walk(const cimq_net_desc* n, bool bufs, bool run, const float* x, void* const* sf, void* const* sc,
-                    float* logits, void* ws, void* stream, size_t* fb, size_t* cb, size_t* wsb) {
+                    float* logits, void* ws, void* stream, size_t* fb, size_t* cb, size_t* wsb,
+                    const cimq_net_ext* ext) {
   static const char who[] = "cimq_net_forward";
   if (!n) return fail(CIMQ_EINVAL, "%s: null plan", who);
+  if (ext) {  // (cimq_net_*_ex: pooled layers and the flatten head; null is the plan alone)
+    if (ext->head_flags & ~CIMQ_NET_HEAD_FLATTEN) return fail(CIMQ_EINVAL, "%s: ext: unknown head_flags 0x%x", who, ext->head_flags);
+    if (ext->reserved[0] != 0 || ext->reserved[1] != 0 || ext->reserved[2] != 0)
+      return fail(CIMQ_EINVAL, "%s: ext: reserved must be 0", who);
+    for (int i = 0; ext->pool && i < n->n_layers; ++i)
+      if (ext->pool[i] != 0 && ext->pool[i] != CIMQ_POOL_MAX2)
+        return fail(CIMQ_EINVAL, "%s: ext: pool[%d] must be 0 or CIMQ_POOL_MAX2 (it is %d)", who, i, ext->pool[i]);
+  }
   if (n->n_layers < 0 || n->n_slots < 0) return fail(CIMQ_EINVAL, "%s: negative n_layers or n_slots", who);
   if (n->n_layers == 0 && !n->head) return fail(CIMQ_EINVAL, "%s: n_layers == 0 without a head", who);
   if (n->n_layers > 0 && !n->layers) return fail(CIMQ_EINVAL, "%s: null layers", who);
@@ -1017,7 +1068,15 @@ static int net_walk(const cimq_net_desc* n, bool bufs, bool run, const float* x,
         view = ResView{L.res_c0, s.C, rs, s.H, s.W};
       }
     }
-    if (fb && (L.out_mode & 1)) fb[L.out_slot] = std::max(fb[L.out_slot], (size_t)g.M * g.O * 4);
+    // a pooled layer (ext->pool): its slot holds [B, O, Ho/2, Wo/2]; its residual, checked above, has the unpooled shape
+    const int pool = (ext && ext->pool) ? ext->pool[i] : 0;
+    if (pool) {
+      const char* why = nullptr;
+      if (fwd != CIMQ_ROUTE_WIDE) why = "the layer is off the wide route (cimq_module_route)";
+      else (void)wide_pool_ok(g, wide_plan(g), &why);
+      if (why) return fail(CIMQ_EUNSUPPORTED, "%s: layer %d: no pooled store: %s (cimq_module_pool_supported)", who, i, why);
+    }
+    if (fb && (L.out_mode & 1)) fb[L.out_slot] = std::max(fb[L.out_slot], (size_t)g.M * g.O * (pool ? 1 : 4));
     if (cb && (L.out_mode & 2)) cb[L.out_slot] = std::max(cb[L.out_slot], (size_t)g.M * g.O);
     wsmax = std::max(wsmax, ws_layout(g).total);
     if (bufs) {
@@ -1026,13 +1085,14 @@ static int net_walk(const cimq_net_desc* n, bool bufs, bool run, const float* x,
           ((L.out_mode & 2) && bad(sc[L.out_slot])) || (L.res_slot >= 0 && bad(sf[L.res_slot])))
         return fail(CIMQ_EINVAL, "%s: layer %d: a slot buffer it uses is null or not 16-byte aligned", who, i);
       // every refusal of the per-layer call, and with run its launches
-      CIMQ_TRY(net_layer_call(n, i, x, sf, sc, is_view ? &view : nullptr, ws, stream, !run));
+      // (a plan given with an ext is a cimq_net_forward_ex plan: its w8a8 layers quantise in their row staging)
+      CIMQ_TRY(net_layer_call(n, i, x, sf, sc, is_view ? &view : nullptr, ws, stream, !run, pool, ext != nullptr));
     }
     NetSlot& o = slot[L.out_slot];
     o.has_float = (L.out_mode & 1) != 0;
     o.has_codes = (L.out_mode & 2) != 0;
     o.consumer = o.has_codes ? L.consumer : -1;
-    o.B = g.B; o.C = g.O; o.H = g.Ho; o.W = g.Wo;
+    o.B = g.B; o.C = g.O; o.H = pool ? g.Ho / 2 : g.Ho; o.W = pool ? g.Wo / 2 : g.Wo;
   }
   if (wsb) *wsb = wsmax;
   if (const cimq_net_head* h = n->head) {
@@ -1047,6 +1107,14 @@ static int net_walk(const cimq_net_desc* n, bool bufs, bool run, const float* x,
       if (!s.has_float) return fail(CIMQ_EINVAL, "%s: head: reads a plane of slot %d that no earlier layer wrote", who, h->in_slot);
       B = s.B; C = s.C; H = s.H; W = s.W;
       if (bufs) src = reinterpret_cast<const float*>(sf[h->in_slot]);
+    }
+    if (ext && (ext->head_flags & CIMQ_NET_HEAD_FLATTEN)) {  // the plane as [B, C * H * W, 1, 1]: a classifier over the flattened map
+      const long long cf = (long long)C * H * W;
+      if (cf > kHeadMaxC)
+        return fail(CIMQ_EUNSUPPORTED, "%s: head: %lld flattened features, at most CIMQ_NET_HEAD_MAX_C (%d) fit its LDS plan",
+                    who, cf, kHeadMaxC);
+      C = (int)cf;
+      H = W = 1;
     }
     if (C > kHeadMaxC)
       return fail(CIMQ_EUNSUPPORTED, "%s: head: %d channels, at most CIMQ_NET_HEAD_MAX_C (%d) fit its LDS plan", who, C, kHeadMaxC);
@@ -1077,16 +1145,26 @@ int cimq_module_forward_codes(const cimq_conv_desc* d, const cimq_lsq_desc* q, c
 
 int cimq_net_abi(void) { return 1; }
 
-int cimq_net_sizes(const cimq_net_desc* net, size_t* slot_float_bytes, size_t* slot_code_bytes, size_t* ws_bytes) {
+int cimq_net_sizes_ex(const cimq_net_desc* net, size_t* slot_float_bytes, size_t* slot_code_bytes, size_t* ws_bytes,
+                      const cimq_net_ext* ext) {
   return net_walk(net, false, false, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, slot_float_bytes,
-                  slot_code_bytes, ws_bytes);
+                  slot_code_bytes, ws_bytes, ext);
+}
+
+int cimq_net_forward_ex(const cimq_net_desc* net, const float* x, void* const* slot_float, void* const* slot_codes,
+                        float* logits, void* ws, void* stream, const cimq_net_ext* ext) {
+  // the whole plan is validated first (every layer's own call made dry): a refused plan launches nothing
+  CIMQ_TRY(net_walk(net, true, false, x, slot_float, slot_codes, logits, ws, stream, nullptr, nullptr, nullptr, ext));
+  return net_walk(net, true, true, x, slot_float, slot_codes, logits, ws, stream, nullptr, nullptr, nullptr, ext);
+}
+
+int cimq_net_sizes(const cimq_net_desc* net, size_t* slot_float_bytes, size_t* slot_code_bytes, size_t* ws_bytes) {
+  return cimq_net_sizes_ex(net, slot_float_bytes, slot_code_bytes, ws_bytes, nullptr);
 }
 
 int cimq_net_forward(const cimq_net_desc* net, const float* x, void* const* slot_float, void* const* slot_codes,
                      float* logits, void* ws, void* stream) {
-  // the whole plan is validated first (every layer's own call made dry): a refused plan launches nothing
-  CIMQ_TRY(net_walk(net, true, false, x, slot_float, slot_codes, logits, ws, stream, nullptr, nullptr, nullptr));
-  return net_walk(net, true, true, x, slot_float, slot_codes, logits, ws, stream, nullptr, nullptr, nullptr);
+  return cimq_net_forward_ex(net, x, slot_float, slot_codes, logits, ws, stream, nullptr);
 }
 
 // one layer of cimq_module_prepare (beta null) or cimq_module_prepare_shift

@@ -162,6 +162,39 @@ __device__ inline void stage_rows_q(const Geo& g, int WP, int RHx, const float* 
   }
 }
 
+// stage_rows_q<false> for eight slices a side (NBP 8: the w8a8 first conv, 8-byte patch words): no table -- a signed
+// activation's codes are not table indices -- but act_words itself on every element, the chain prep_module_fwd_kernel
+// runs (its table holds act_words_xq of r * sa, which is what act_words makes of an element whose code is r), so the
+// patch holds that prologue's forward words bit for bit.  Eight 1-bit slices and W % 4 == 0 (fwd8_stage_ok).
+__device__ inline void stage_rows_q8(const Geo& g, int WP, int RHx, const float* __restrict__ x, float sa, bool sgn,
+                                     int b, int ih_first, uint8_t* patch) {
+  const int QW = g.W >> 2;  // 4-element items per row
+  const int n = g.C * RHx * QW;
+  const float invQ = 1.f / (float)QW, invR = 1.f / (float)RHx;
+  const size_t img = (size_t)b * g.C * g.H;
+  for (int idx = threadIdx.x; idx < n; idx += (int)blockDim.x) {
+    const int row = fdiv(idx, QW, invQ), q = idx - row * QW;
+    const int c = fdiv(row, RHx, invR);
+    const int ih = ih_first + (row - c * RHx);
+    // (8-byte stores: the padding columns leave a row's data 8-byte aligned only)
+    uint2* p = reinterpret_cast<uint2*>(patch + ((size_t)row * WP + g.PW) * 8 + q * 32);
+    if ((unsigned)ih >= (unsigned)g.H) {
+      p[0] = p[1] = p[2] = p[3] = make_uint2(0u, 0u);
+      continue;
+    }
+    const float4 v = reinterpret_cast<const float4*>(x)[((img + (size_t)c * g.H + ih) * g.W >> 2) + q];
+    uint32_t f0[2], f1[2], f2[2], f3[2], bw[2];
+    act_words<8, 8>(g, v.x, sa, sgn, f0, bw);
+    act_words<8, 8>(g, v.y, sa, sgn, f1, bw);
+    act_words<8, 8>(g, v.z, sa, sgn, f2, bw);
+    act_words<8, 8>(g, v.w, sa, sgn, f3, bw);
+    p[0] = make_uint2(f0[0], f0[1]);
+    p[1] = make_uint2(f1[0], f1[1]);
+    p[2] = make_uint2(f2[0], f2[1]);
+    p[3] = make_uint2(f3[0], f3[1]);
+  }
+}
+
 // stage_rows_q for an input that arrives as activation codes (cimq_module_forward_codes; forward only, so no
 // backward words): one byte per element, [B, C, H, W], four columns per 32-bit load, each byte straight into the
 // word table -- no division, clamp or rint.  A byte above Qp + 1 reads the NaN entry: none indexes past the table.

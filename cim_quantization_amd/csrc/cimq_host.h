@@ -684,6 +684,21 @@ inline int wide_cst(const Geo& g) {
   return (g.nbw == g.nba && g.bsw == 1 && g.bsa == 1 && g.nbw >= 2 && g.nbw <= 4) ? g.nbw : 0;
 }
 
+// The pooled store of cim_fwd_wide_kernel (cimq_module_forward_pool): the lower row of every 2x2 window crosses to
+// the upper row's lane through the weight-fragment region of the kernel's LDS, one float2 per thread and output block
+constexpr size_t kWidePoolBytes = (size_t)256 * kWideOBM * 8;
+// ... applies on a wide plan whose m-tile holds whole row pairs (Wo <= 32: 64 / Wo rows, an even count from an even
+// row, since P % 64 == 0) and whose fragment region holds the exchange; why: the refusal's reason (may be null)
+inline bool wide_pool_ok(const Geo& g, const PlanW& p, const char** why = nullptr) {
+  const char* r = nullptr;
+  if (!p.ok) r = "the layer is off the wide route";
+  else if (g.Wo > 32) r = "an output wider than 32 keeps the rows of a 2x2 window in different m-tiles";
+  else if ((size_t)g.nbw * kWideOBM * g.KS * 1024 < kWidePoolBytes)
+    r = "one weight slice in one K-step leaves the LDS fragment region too small for the row exchange";
+  if (why) *why = r;
+  return r == nullptr;
+}
+
 // the shift ADC's statistics kernel (cimq_part_shift.hip) applies: interleaved 3-bit state words of
 // w2a2 / w3a3 on a v7 shape (other shift layers take the general backward)
 inline bool shift_stats_ok(const Geo& g) {
@@ -1067,6 +1082,16 @@ inline Route route_compute(const Geo& g) {
 }
 inline Route route_of(const Geo& g) { return memo_geo<Route, route_compute>(g); }
 
+// A forward-only w8a8 layer of eight 1-bit slices on the v3 route (the first conv of the CIFAR networks) can quantise
+// its input in the kernel's row staging (cim_fwd_v3_kernel<8, ., 8, ., EPI, 1, Q8>, stage_rows_q8): the layers of a
+// cimq_net_forward_ex plan alone do -- every existing call keeps its prologue launch and Route::actq its answer
+inline bool fwd8_stage_ok(const Geo& g) {
+  const Route r = route_of(g);
+  return g.inference && g.onchw && g.NBP == 8 && g.nba == 8 && g.bsa == 1 && g.W % 4 == 0 &&
+         g.input_kind == CIMQ_INPUT_RAW_LSQ && g.variant == VAR_LIBRARY && r.fwd == CIMQ_ROUTE_V3 && (r.cst == 8 || r.cst == 0) &&
+         v3_plan(g).ok && !r.actq;
+}
+
 // which mode a forward call is: the one place that reads the call's Epi to decide a kernel instance (the launchers
 // of the three forward families, and the transposer after the general kernel).  It only classifies: what a route
 // cannot run is refused where the call is checked (module_forward_impl)
@@ -1350,9 +1375,13 @@ inline void prof_end(int slot, hipStream_t s) {
 int launch_fwd_any(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, int* ps_dbg,
                    float* adc_dbg, hipStream_t s,
                    const ActQ* aq = nullptr, const Epi* ep = nullptr);
+// ... a forward-only w8a8 layer with an epilogue, its activation quantised in the row staging (fwd8_stage_ok)
+int launch_fwd8_staged(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, hipStream_t s,
+                       const ActQ* aq, const Epi* ep);
 // cimq_part_wide.hip: the channel-chunked module forward (wide_plan); aq: fp32 x for the forward-only modes
+// pool: the 2x2 max-pooled store of an epilogue call (wide_pool_ok), out [B, O, Ho/2, Wo/2]
 int launch_wide(const Geo& g, const PlanW& p, uint8_t* ctx, const float* sw, const float* sa, float* out,
-                hipStream_t s, const ActQ* aq, const Epi* ep = nullptr);
+                hipStream_t s, const ActQ* aq, const Epi* ep = nullptr, bool pool = false);
 // cimq_part_fwd5.hip: the w3a3 module forward on the slice-planar patch (f5_plan)
 int launch_fwd5(const Geo& g, const Plan5& p, uint8_t* ctx, const float* sw, const float* sa, float* out,
                 hipStream_t s, const ActQ* aq, const Epi* ep = nullptr);

@@ -99,7 +99,10 @@ __device__ inline void add_bits(uint32_t& stw, uint32_t (&tq)[3], int j, uint32_
 // codes (ep.oq) or both; the view costs four scalar loads per float4 and, inside the code instances, a wave per
 // SIMD of <4, 1, 0, WRITE, CODES, 2> (96 -> 97 VGPRs): hence instances of its own.
 // xin (module path, NBP 4): the activation quantiser fused into the row staging (stage_rows_q)
-template <int NBP, int KS, int CST, FwdState ST, FwdMode M, int OBM>
+// Q8 (NBP 8, forward only with an epilogue; a layer of a cimq_net_forward_ex plan alone): the w8a8 layer's row staging
+// quantises fp32 xin itself (stage_rows_q8: the prologue's act_words, element by element), so a prepared call is one
+// launch; every other instance is what it was
+template <int NBP, int KS, int CST, FwdState ST, FwdMode M, int OBM, bool Q8 = false>
 __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint8_t* __restrict__ xcf,
                                                          const v4i* __restrict__ wfrag, Params pp,
                                                          const float* __restrict__ sw_p,
@@ -118,6 +121,8 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
   static_assert(M != FwdMode::TRAIN || !INF, "a training instance leaves the backward its words, or recomputes them");
   static_assert(M != FwdMode::INFER || INF, "forward only is the stateless form of a compact format");
   static_assert(!EPI || CST == 0 || !WST, "the epilogue instances are forward only");
+  static_assert(!Q8 || (NBP == 8 && (CST == 8 || CST == 0) && M == FwdMode::EPI),
+                "the staged w8a8 quantiser is an epilogue instance's: the one-block format (CST 8) or per-k (CST 0)");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int og = blockIdx.y;
   const int NOB = min(OBM, g.OB16);
@@ -239,7 +244,9 @@ __global__ __launch_bounds__(256) void cim_fwd_v3_kernel(Geo g, V3 v, const uint
     const int b = fdiv(mt, tiles_per_img, inv_tpi), p0 = (mt - b * tiles_per_img) * 64;
     const int oh0 = p0 >> v.lw;
     __syncthreads();
-    if (actq) {
+    if constexpr (Q8) {
+      stage_rows_q8(g, v.WP, v.RH, xin, *sa_p, *sgn_p != 0.f, b, oh0 * g.SH - g.PH, patch);
+    } else if (actq) {
       // input rows this m-tile owns (written once to xcb): its output rows' stride-spans, to the
       // image's end for its last m-tile; one o-group's blocks write them
       const int own_lo = blockIdx.y == 0 ? oh0 * g.SH : 0;

@@ -445,7 +445,7 @@ __global__ void bpo_to_nchw_view_kernel(Geo g, const float* __restrict__ src, fl
 // divided by (float)hw with an IEEE division: the C pooled values stay in LDS (C <= kHeadMaxC).  Classifier: wave
 // w takes classes w, w + 4, ...; lane l sums w[k, c] * p[c] over c = l, l + 64, ... (a product, then an add: no
 // fused multiply-add), the same butterfly, lane 0 adds the bias.  No atomics, one fixed order: two runs are equal
-// bit for bit.  A NaN feature makes its image's pooled value and so all of that image's logits NaN, nobody else's.
+// bit for bit.  hw == 1 (a flattened plane) skips the per-channel butterfly.  A NaN feature makes its image's pooled value and so all of that image's logits NaN, nobody else's.
 constexpr int kHeadMaxC = 8192;  // 32 KB of LDS (include/cimq.h states it: CIMQ_NET_HEAD_MAX_C)
 __device__ inline float wave_sum_fixed(float v) {
 #pragma unroll
@@ -460,7 +460,14 @@ __global__ __launch_bounds__(256) void net_head_kernel(const float* __restrict__
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.x;
   const float* xb = x + (size_t)b * C * hw;
   const float n = (float)hw;
-  for (int c = wave; c < C; c += 4) {
+  // one element per channel (the flatten head of cimq_net_forward_ex): the whole block copies the plane.  0 + v is
+  // what the sum, the butterfly's adds of 0 and the division by 1 below give, bit for bit (a -0.0 becomes +0.0)
+  for (int c = threadIdx.x; hw == 1 && c < C; c += blockDim.x) {
+    const float p = __fadd_rn(0.f, xb[c]);
+    pl[c] = p;
+    if (pooled) pooled[(size_t)b * C + c] = p;
+  }
+  for (int c = wave; hw != 1 && c < C; c += 4) {
     const float* src = xb + (size_t)c * hw;
     float s = 0.f;
     if ((hw & 3) == 0) {

@@ -42,7 +42,7 @@ Fwd3Kern fwd3_kernel(int cst, FwdState st, int obm) {
 
 template <int NBP, int KS>
 int launch_fwd_v3(const Geo& g, const Plan3& p, uint8_t* ctx, const float* sw, const float* sa, float* out,
-                  hipStream_t s, const ActQ* aq, const Epi* ep = nullptr) {
+                  hipStream_t s, const ActQ* aq, const Epi* ep = nullptr, bool q8 = false) {
   CtxLayout L = ctx_layout(g);
   // CST, fixed at compile time: 0 per-k state words (the general backward's), else the compact ones the v7-plan
   // backwards read -- nbw = nba = CST (2, 3, 4), 8 the w8a8 planes.  The first conv's backward recomputes them; a
@@ -75,6 +75,20 @@ int launch_fwd_v3(const Geo& g, const Plan3& p, uint8_t* ctx, const float* sw, c
     case FwdMode::INFER: kern = fwd3_kernel<NBP, KS, FwdMode::INFER>(cst, st, obm); break;
     case FwdMode::TRAIN: kern = fwd3_kernel<NBP, KS, FwdMode::TRAIN>(cst, st, obm); break;
     case FwdMode::VIEW: kern = fwd3_kernel<NBP, KS, FwdMode::VIEW>(cst, st, obm); break;
+  }
+  // q8 (launch_fwd8_staged): the w8a8 epilogue instance whose row staging quantises aq->x itself
+  if (q8) {
+    kern = nullptr;
+    if constexpr (NBP == 8) {
+      if (m == FwdMode::EPI && cst == 8 && aq)  // one 16-channel block (the ResNets' first conv)
+        kern = st == FwdState::RECOMPUTE ? cim_fwd_v3_kernel<8, KS, 8, FwdState::RECOMPUTE, FwdMode::EPI, 1, true>
+                                         : cim_fwd_v3_kernel<8, KS, 8, FwdState::NONE, FwdMode::EPI, 1, true>;
+      if (m == FwdMode::EPI && cst == 0 && aq)  // wider (VGG's 3 -> 128): the per-k form, as fwd3_kernel names it
+        kern = obm == 1   ? cim_fwd_v3_kernel<8, KS, 0, FwdState::WRITE, FwdMode::EPI, 1, true>
+               : obm == 2 ? cim_fwd_v3_kernel<8, KS, 0, FwdState::WRITE, FwdMode::EPI, 2, true>
+                          : cim_fwd_v3_kernel<8, KS, 0, FwdState::WRITE, FwdMode::EPI, 4, true>;
+    }
+    if (!kern) return fail(CIMQ_EINVAL, "internal: the staged w8a8 quantiser off its plan");
   }
   // the fused activation quantiser's word table (after the kernel's other LDS)
   const size_t lds = p.lds_fwd + (aq ? (size_t)kActLutMax * 2 * 4 : 0);
@@ -122,6 +136,14 @@ int launch_fwd(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, flo
   return check_hip("cim_fwd");
 }
 
+
+int launch_fwd8_staged(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, hipStream_t s,
+                       const ActQ* aq, const Epi* ep) {
+  if (!fwd8_stage_ok(g) || !aq || !ep) return fail(CIMQ_EINVAL, "internal: the staged w8a8 quantiser off its plan");
+  const Plan3 p = v3_plan(g);
+  if (g.KS == 1) return launch_fwd_v3<8, 1>(g, p, ctx, sw, sa, out, s, aq, ep, true);
+  return launch_fwd_v3<8, 2>(g, p, ctx, sw, sa, out, s, aq, ep, true);
+}
 
 int launch_fwd_any(const Geo& g, uint8_t* ctx, const float* sw, const float* sa, float* out, int* ps_dbg,
                    float* adc_dbg, hipStream_t s, const ActQ* aq, const Epi* ep) {

@@ -28,14 +28,29 @@ WideKern wide_kernel(FwdMode m, int cst) {
   }
 }
 
+// the pooled-store instances (POOL): the epilogue mode alone, the same eight (K-steps, slice count) forms
+template <int KS>
+WideKern wide_pool_kernel(int cst) {
+  switch (cst) {
+    case 2: return cim_fwd_wide_kernel<KS, 2, FwdMode::EPI, true>;
+    case 3: return cim_fwd_wide_kernel<KS, 3, FwdMode::EPI, true>;
+    case 4: return cim_fwd_wide_kernel<KS, 4, FwdMode::EPI, true>;
+    default: return cim_fwd_wide_kernel<KS, 0, FwdMode::EPI, true>;
+  }
+}
+
 int launch_wide(const Geo& g, const PlanW& p, uint8_t* ctx, const float* sw, const float* sa, float* out,
-                hipStream_t s, const ActQ* aq, const Epi* ep) {
+                hipStream_t s, const ActQ* aq, const Epi* ep, bool pool) {
   if (!p.ok || !g.onchw) return fail(CIMQ_EINVAL, "internal: cim_fwd_wide off its plan");
   const FwdMode m = fwd_mode_of(g, ep);
   // a forward-only call reads fp32 x (Route::actq), a training call the prologue's slice words
   if ((m != FwdMode::TRAIN) != (aq != nullptr) || (m != FwdMode::TRAIN && !g.inference))
     return fail(CIMQ_EINVAL, "internal: cim_fwd_wide's input form off its mode");
-  WideKern kern = g.KS == 1 ? wide_kernel<1>(m, wide_cst(g)) : wide_kernel<2>(m, wide_cst(g));
+  // (out is [B, O, Ho/2, Wo/2] then: module_forward_impl has checked wide_pool_ok)
+  if (pool && (m != FwdMode::EPI || !wide_pool_ok(g, p)))
+    return fail(CIMQ_EINVAL, "internal: cim_fwd_wide's pooled store off its plan");
+  WideKern kern = pool ? (g.KS == 1 ? wide_pool_kernel<1>(wide_cst(g)) : wide_pool_kernel<2>(wide_cst(g)))
+                       : (g.KS == 1 ? wide_kernel<1>(m, wide_cst(g)) : wide_kernel<2>(m, wide_cst(g)));
   if (!kern) return fail(CIMQ_EUNSUPPORTED, "the wide route takes no activation codes and no residual view");
   CtxLayout L = ctx_layout(g);
   CIMQ_TRY(set_lds(kern, p.lds));

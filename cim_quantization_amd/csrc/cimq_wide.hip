@@ -67,9 +67,17 @@ __device__ inline void stage_rows_qw(const Geo& g, int WP, int RHx, const float*
   }
 }
 
+// torch's max-pool update (max_pool_forward_nchw: v > m || isnan(v)) on an ordered pair: the earlier element m stays
+// unless the later one is greater or a NaN -- so any NaN gives NaN and of +0 / -0 the earlier wins.  Compare and
+// select: v_max_f32 drops NaNs and does not order the zeros.  pool_pick(pool_pick(a, b), pool_pick(c, d)) is the
+// sequential scan a, b, c, d bit for bit.
+__device__ inline float pool_pick(float m, float v) { return (v > m || v != v) ? v : m; }
+
 // CST: 2 / 3 / 4 fix nbw = nba = CST in 1-bit slices at compile time (the ternary-threshold path then runs
 // unrolled); 0 takes the counts -- and slices of any width -- at run time.  M: TRAIN, INFER or EPI (FwdMode).
-template <int KS, int CST, FwdMode M>
+// POOL (EPI alone): the epilogue's values leave through a 2x2 / stride-2 max pool, out is [B, O, Ho/2, Wo/2] -- see
+// pool_pick and the store below (wide_pool_ok on the host: Wo <= 32, so that both rows of a window sit in one m-tile).
+template <int KS, int CST, FwdMode M, bool POOL = false>
 __global__ __launch_bounds__(256) void cim_fwd_wide_kernel(Geo g, V3 v, WideP wp, const uint8_t* __restrict__ xcf,
                                                            const v4i* __restrict__ wfrag, Params pp,
                                                            const float* __restrict__ sw_p,
@@ -80,6 +88,7 @@ __global__ __launch_bounds__(256) void cim_fwd_wide_kernel(Geo g, V3 v, WideP wp
   constexpr bool EPI = has_epi(M), ACTQ = M != FwdMode::TRAIN;
   static_assert(M == FwdMode::TRAIN || M == FwdMode::INFER || M == FwdMode::EPI, "codes and views are not built");
   static_assert(CST == 0 || CST == 2 || CST == 3 || CST == 4, "runtime counts, or w2a2 / w3a3 / w4a4 in 1-bit slices");
+  static_assert(!POOL || M == FwdMode::EPI, "the pooled store is the epilogue instances' alone");
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
   const int og = blockIdx.y;
   const int nob = min(OBM, g.OB16 - og * OBM);
@@ -251,6 +260,55 @@ __global__ __launch_bounds__(256) void cim_fwd_wide_kernel(Geo g, V3 v, WideP wp
       }
     }
     // store out (NCHW).  acc[ob][r]: pixel wave*16 + 4*g4 + r, channel (og*OBM + ob)*16 + r16
+    if constexpr (POOL) {
+      // The 2x2 / stride-2 max pool of the epilogue's values.  A lane's four pixels are one row's columns 4q' .. 4q' + 3
+      // (Wo % 4 == 0): the two horizontal pairs are pooled in registers.  The window's other row is pixel + Wo: the
+      // quad (wave * 4 + g4) ^ (Wo / 4) of this m-tile (64 / Wo rows, an even count from an even row: Wo <= 32 and
+      // P % 64 == 0).  The lower row's halves go through the weight-fragment region of LDS -- dead after the last
+      // tile's MFMAs and rewritten whole by the next m-tile's first store_tile / stage_tile behind the loop's top
+      // barrier (the patch is not free: its padding columns are zeroed once per block) -- as one float2 per lane and
+      // block, [ob][quad][r16]: consecutive lanes write and read consecutive 8-byte words.  The upper row's lane pools
+      // top before bottom, so the result is the first maximal element in the scan order (0,0) (0,1) (1,0) (1,1).
+      float2* ex = reinterpret_cast<float2*>(l_wfl);
+      const int quad = wave * 4 + g4, qpr = Wo >> 2;
+      const bool top = (quad & qpr) == 0;
+      const int m4 = mt * 64 + quad * 4;  // M < 2^24 (wide_plan)
+      const int bb = fdiv(m4, g.P, inv_p), pq = m4 - bb * g.P;
+      float2 hz[OBM];
+#pragma unroll
+      for (int ob = 0; ob < OBM; ++ob) {
+        const int o = (og * OBM + ob) * 16 + r16;
+        hz[ob] = make_float2(0.f, 0.f);
+        if (ob < nob && o < g.O) {
+          const size_t oi = ((size_t)bb * g.O + o) * g.P + pq;  // the unpooled index: the residual's
+          int oe = o;
+          asm volatile("" : "+v"(oe));
+          const float4 y = epi_val4(ep, ep.scale[oe], ep.shift[oe], oi, acc[ob][0], acc[ob][1], acc[ob][2], acc[ob][3]);
+          hz[ob] = make_float2(pool_pick(y.x, y.y), pool_pick(y.z, y.w));
+        }
+      }
+      __syncthreads();  // every wave's reads of the last tile's weight fragments are done
+      if (!top) {
+#pragma unroll
+        for (int ob = 0; ob < OBM; ++ob)
+          if (ob < nob) ex[(ob * 16 + quad) * 16 + r16] = hz[ob];
+      }
+      __syncthreads();
+      if (top) {
+        const int Wh = Wo >> 1, Ph = g.P >> 2;
+        const int pp = ((pq >> v.lw) >> 1) * Wh + ((pq & (Wo - 1)) >> 1);  // the pooled pixel of the lane's first window
+#pragma unroll
+        for (int ob = 0; ob < OBM; ++ob) {
+          const int o = (og * OBM + ob) * 16 + r16;
+          if (ob < nob && o < g.O) {
+            const float2 lo = ex[(ob * 16 + (quad | qpr)) * 16 + r16];
+            *reinterpret_cast<float2*>(out + ((size_t)bb * g.O + o) * Ph + pp) =
+                make_float2(pool_pick(hz[ob].x, lo.x), pool_pick(hz[ob].y, lo.y));
+          }
+        }
+      }
+      continue;  // (the next m-tile's top barrier follows the reads above)
+    }
 #pragma unroll
     for (int ob = 0; ob < OBM; ++ob) {
       const int o = (og * OBM + ob) * 16 + r16;

@@ -925,6 +925,19 @@ def cim_module_conv_epilogue(x, weight, alpha_act, alpha_weight, alpha_cim, bina
                           residual, relu, beta_cim, stochastic, wprep, recompute, "cim_module_conv_epilogue")
 
 
+def cim_module_conv_pool(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding,
+                         dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha, scale, shift,
+                         residual=None, relu=False, pool=_lib.CIMQ_POOL_MAX2, wprep=None, recompute=False):
+    """cim_module_conv_epilogue whose kernel stores the 2x2 / stride-2 max pool of the epilogue's values
+    (cimq_module_forward_pool, ``pool`` CIMQ_POOL_MAX2): [B, O, Ho/2, Wo/2], bit for bit
+    ``F.max_pool2d(cim_module_conv_epilogue(...), 2, 2)``.  ``residual`` keeps the unpooled shape.  ``pool`` 0 is
+    cim_module_conv_epilogue.  Layers off the wide route, or wider than 32 output columns, raise CimqError
+    (``_lib.module_pool_supported``)."""
+    return _conv_epilogue(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding,
+                          dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha, scale, shift,
+                          residual, relu, None, False, wprep, recompute, "cim_module_conv_pool", pool=int(pool))
+
+
 def act_code_step(alpha_act, gscale_a):
     """The step size ``sa`` of a layer's activation quantiser as libcimq computes it: grad_scale's forward value
     ``(alpha_act - alpha_act * s) + alpha_act * s`` with every operation in fp32 (cimq_device.h grad_scale_value)."""
@@ -962,9 +975,10 @@ def cim_module_conv_codes(x, weight, alpha_act, alpha_weight, alpha_cim, binary_
 
 def _conv_epilogue(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding, dilation,
                    nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha, scale, shift, residual, relu,
-                   beta_cim, stochastic, wprep, recompute, who, codes=False, out_quant=None, keep_float=True):
+                   beta_cim, stochastic, wprep, recompute, who, codes=False, out_quant=None, keep_float=True, pool=None):
     """The shared body of cim_module_conv_epilogue (``codes`` False: cimq_module_forward_epilogue, fp32 in and
-    out) and cim_module_conv_codes (cimq_module_forward_codes)."""
+    out), cim_module_conv_pool (``pool`` an int: cimq_module_forward_pool) and cim_module_conv_codes
+    (cimq_module_forward_codes)."""
     if not inference_call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, scale, shift, residual):
         raise RuntimeError(f"{who} is forward only: call it under torch.no_grad(), or with no "
                            "argument that requires a gradient")
@@ -989,9 +1003,16 @@ def _conv_epilogue(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, s
                              f"{c.out_shape}")
         rs = _f32(residual, dev)
     epi = _lib.make_epilogue(*_ptrs(sc, sh, rs), relu)
+    if pool:  # (any non-zero value reaches the library, which refuses all but CIMQ_POOL_MAX2)
+        B, _, Ho, Wo = c.out_shape
+        c.out = torch.empty((B, O, Ho // 2, Wo // 2), device=dev, dtype=torch.float32)
     # the operands every one of the two entry points takes between its leading arguments and the epilogue
     args = _ptrs(o.w, o.sa, o.sw, o.alpha, o.beta, o.mask, o.sgn) + [ctypes.byref(epi)] + _ptrs(c.out, o.ctx, c.ws) + \
         [_stream()]
+    if pool is not None:
+        _lib.check(_lib.load().cimq_module_forward_pool(c.desc, c.lsq, o.x.data_ptr(), *args[:8], pool, *args[8:]),
+                   "cimq_module_forward_pool")
+        return c.out
     if not codes:
         _lib.check(_lib.load().cimq_module_forward_epilogue(c.desc, c.lsq, o.x.data_ptr(), *args),
                    "cimq_module_forward_epilogue")
@@ -1015,21 +1036,32 @@ def _conv_epilogue(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, s
     return (c.out, oq) if keep_float else oq
 
 
-def net_sizes(net):
+def net_sizes(net, ext=None):
     """cimq_net_sizes of a ``_lib.NetDesc``: (float bytes per slot, code bytes per slot, workspace bytes).  Raises
-    CimqError where the library refuses the plan."""
+    CimqError where the library refuses the plan.  ``ext``: a ``_lib.NetExt`` (pooled layers, the flatten head):
+    cimq_net_sizes_ex."""
     n = max(int(net.n_slots), 1)
     fb, cb, ws = (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)(), ctypes.c_size_t()
-    _lib.check(_lib.load().cimq_net_sizes(ctypes.byref(net), fb, cb, ctypes.byref(ws)), "cimq_net_sizes")
+    if ext is None:
+        _lib.check(_lib.load().cimq_net_sizes(ctypes.byref(net), fb, cb, ctypes.byref(ws)), "cimq_net_sizes")
+    else:
+        _lib.check(_lib.load().cimq_net_sizes_ex(ctypes.byref(net), fb, cb, ctypes.byref(ws), ctypes.byref(ext)),
+                   "cimq_net_sizes_ex")
     return list(fb)[:net.n_slots], list(cb)[:net.n_slots], ws.value
 
 
-def net_forward(net, x, slot_float, slot_codes, logits, ws, stream=None):
+def net_forward(net, x, slot_float, slot_codes, logits, ws, stream=None, ext=None):
     """cimq_net_forward: the whole plan ``net`` (a ``_lib.NetDesc``) on ``stream`` (default: torch's current one) in
     one library call.  ``x`` / ``logits`` / ``ws``: device addresses (None where the plan has no use for one);
-    ``slot_float`` / ``slot_codes``: ``(ctypes.c_void_p * n_slots)`` arrays of device addresses."""
-    _lib.check(_lib.load().cimq_net_forward(ctypes.byref(net), x, slot_float, slot_codes, logits, ws,
-                                            _stream() if stream is None else stream), "cimq_net_forward")
+    ``slot_float`` / ``slot_codes``: ``(ctypes.c_void_p * n_slots)`` arrays of device addresses.  ``ext``: a
+    ``_lib.NetExt``: cimq_net_forward_ex."""
+    s = _stream() if stream is None else stream
+    if ext is None:
+        _lib.check(_lib.load().cimq_net_forward(ctypes.byref(net), x, slot_float, slot_codes, logits, ws, s),
+                   "cimq_net_forward")
+    else:
+        _lib.check(_lib.load().cimq_net_forward_ex(ctypes.byref(net), x, slot_float, slot_codes, logits, ws, s,
+                                                   ctypes.byref(ext)), "cimq_net_forward_ex")
 
 
 def alpha_cim_init(x, w_q, sa, sw, binary_mask, signed_act, stride, padding, nbits_a, abitslice,

@@ -98,10 +98,7 @@ class _NetPlan:
     and the arena behind the slots.  ``run(x)`` is one library call."""
 
     def __init__(self, fused, x):
-        import ctypes
-
         from .. import _lib
-        from .. import functional as CF
         from .models import PadShortcut
         m = fused.model
         chain, names = fused._chain_of()
@@ -117,40 +114,10 @@ class _NetPlan:
         shape = tuple(x.shape)
         shapes, block_shape = [], None
         for i, (conv, bn, blk) in enumerate(chain):
-            probe = torch.empty(1, dtype=torch.uint8, device=dev).expand(shape)
-            if not getattr(conv, "fused_epilogue_ready", lambda t: False)(probe):
-                raise _NoPlan("a conv is off the library path")
-            if conv.stochastic_quant:
-                raise _NoPlan("stochastic-ADC layers run in the loop")
-            # (a shift-ADC layer that is ready is one the fused shift path takes: its prepared side carries beta_cim)
-            ps = (conv.weight, conv.alpha_act, conv.alpha_weight, conv.alpha_cim) + \
-                ((conv.beta_cim,) if conv.adc_shift else ())
-            if any(t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev) for t in ps):
-                raise _NoPlan("parameters must be contiguous fp32 on the input's device")
-            if conv.binary_mask.device != dev:
-                conv.binary_mask = conv.binary_mask.to(dev)
-            desc, lsq = CF.module_descs(conv, shape, inference=True)
-            wp = conv._inf_prep = CF.inference_weights(conv, shape, conv._inf_prep)
-            lsq.wprep = wp.buf.data_ptr()
-            sizes = _lib.query_sizes(desc)
-            ctx = torch.empty(max(sizes.module_ctx_bytes, 1), device=dev, dtype=torch.uint8)
-            bm = conv.binary_mask.to(device=dev, dtype=torch.int8).contiguous()
-            sg = conv.signed_act.detach().to(device=dev, dtype=torch.float32).reshape(-1)[:1].contiguous()
-            scale, shift = fused.tables(bn)
-            scale, shift = scale.to(dev), shift.to(dev)
-            self.keep += [desc, lsq, wp, ctx, bm, sg, scale, shift]
             L = layers[i]
-            L.desc, L.lsq = ctypes.pointer(desc), ctypes.pointer(lsq)
-            L.weight, L.alpha_act = conv.weight.data_ptr(), conv.alpha_act.data_ptr()
-            L.alpha_weight = conv.alpha_weight.data_ptr()
-            L.alpha_cim = None if conv.alpha_cim is None else conv.alpha_cim.data_ptr()
-            L.beta_cim = conv.beta_cim.data_ptr() if conv.adc_shift else None
-            L.binary_mask, L.signed_act = bm.data_ptr(), sg.data_ptr()
-            L.scale, L.shift, L.epi_flags = scale.data_ptr(), shift.data_ptr(), _lib.CIMQ_EPI_RELU
+            self._fill_layer(fused, L, conv, bn, shape, dev)
             L.in_slot = -1 if i == 0 else slot_of[i - 1]
-            L.out_slot, L.out_mode, L.consumer, L.in_codes = slot_of[i], 1, 0, 0
-            L.res_slot, L.res_c0, L.res_stride, L.reserved = -1, 0, 1, 0
-            L.ctx = ctx.data_ptr()
+            L.out_slot = slot_of[i]
             if i > 0 and blk is None:
                 block_shape = shape  # a block's first conv: its input feeds the block's shortcut too
             out_shape = _out_shape(conv, shape)
@@ -183,8 +150,58 @@ class _NetPlan:
         if not isinstance(lin, nn.Linear) or lin.weight.device != dev or lin.weight.dtype != torch.float32 or \
                 not lin.weight.is_contiguous() or lin.in_features != shape[1]:
             raise _NoPlan("the classifier is not a contiguous fp32 nn.Linear over the last conv's channels")
+        self._finish(layers, n_slots, slot_of[n - 1], lin, x, shape)
+
+    def _fill_layer(self, fused, L, conv, bn, shape, dev):
+        """one conv of the plan for input ``shape``: its descriptors, prepared weight side, ctx and folded BatchNorm
+        (kept alive on the plan), an fp32 output with ReLU and no residual; the caller sets the slots"""
+        import ctypes
+
+        from .. import _lib
+        from .. import functional as CF
+        probe = torch.empty(1, dtype=torch.uint8, device=dev).expand(shape)
+        if not getattr(conv, "fused_epilogue_ready", lambda t: False)(probe):
+            raise _NoPlan("a conv is off the library path")
+        if conv.stochastic_quant:
+            raise _NoPlan("stochastic-ADC layers run in the loop")
+        # (a shift-ADC layer that is ready is one the fused shift path takes: its prepared side carries beta_cim)
+        ps = (conv.weight, conv.alpha_act, conv.alpha_weight, conv.alpha_cim) + \
+            ((conv.beta_cim,) if conv.adc_shift else ())
+        if any(t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev) for t in ps):
+            raise _NoPlan("parameters must be contiguous fp32 on the input's device")
+        if conv.binary_mask.device != dev:
+            conv.binary_mask = conv.binary_mask.to(dev)
+        desc, lsq = CF.module_descs(conv, shape, inference=True)
+        wp = conv._inf_prep = CF.inference_weights(conv, shape, conv._inf_prep)
+        lsq.wprep = wp.buf.data_ptr()
+        sizes = _lib.query_sizes(desc)
+        ctx = torch.empty(max(sizes.module_ctx_bytes, 1), device=dev, dtype=torch.uint8)
+        bm = conv.binary_mask.to(device=dev, dtype=torch.int8).contiguous()
+        sg = conv.signed_act.detach().to(device=dev, dtype=torch.float32).reshape(-1)[:1].contiguous()
+        scale, shift = fused.tables(bn)
+        scale, shift = scale.to(dev), shift.to(dev)
+        self.keep += [desc, lsq, wp, ctx, bm, sg, scale, shift]
+        L.desc, L.lsq = ctypes.pointer(desc), ctypes.pointer(lsq)
+        L.weight, L.alpha_act = conv.weight.data_ptr(), conv.alpha_act.data_ptr()
+        L.alpha_weight = conv.alpha_weight.data_ptr()
+        L.alpha_cim = None if conv.alpha_cim is None else conv.alpha_cim.data_ptr()
+        L.beta_cim = conv.beta_cim.data_ptr() if conv.adc_shift else None
+        L.binary_mask, L.signed_act = bm.data_ptr(), sg.data_ptr()
+        L.scale, L.shift, L.epi_flags = scale.data_ptr(), shift.data_ptr(), _lib.CIMQ_EPI_RELU
+        L.out_mode, L.consumer, L.in_codes = 1, 0, 0
+        L.res_slot, L.res_c0, L.res_stride, L.reserved = -1, 0, 1, 0
+        L.ctx = ctx.data_ptr()
+        return desc
+
+    def _finish(self, layers, n_slots, last_slot, lin, x, shape, ext=None):
+        """the head over ``lin``, the plan's sizes (``ext``: a ``_lib.NetExt``, kept) and the arena behind its slots"""
+        import ctypes
+
+        from .. import _lib
+        from .. import functional as CF
+        n, dev = len(layers), x.device
         head = _lib.NetHead()
-        head.in_slot, head.classes = slot_of[n - 1], lin.out_features
+        head.in_slot, head.classes = last_slot, lin.out_features
         head.weight = lin.weight.data_ptr()
         head.bias = None if lin.bias is None else lin.bias.data_ptr()
         head.pooled = None
@@ -193,8 +210,9 @@ class _NetPlan:
         net.layers, net.head = layers, ctypes.pointer(head)
         net.B, net.C, net.H, net.W = x.shape
         self.keep += [layers, head]
+        self.ext = ext
         try:
-            fb, cb, wsb = CF.net_sizes(net)
+            fb, cb, wsb = CF.net_sizes(net, ext)
         except _lib.CimqError as e:
             raise _NoPlan(str(e))
         # one arena behind the slots' planes and the shared workspace
@@ -215,13 +233,13 @@ class _NetPlan:
             off += al(cb[s])
         self.ws = base + off
         self.net, self.n_slots, self.classes, self.batch = net, n_slots, lin.out_features, x.shape[0]
-        self.last_shape, self.last_slot = shape, slot_of[n - 1]
+        self.last_shape, self.last_slot = shape, last_slot
         self._run = CF.net_forward
 
     def run(self, x):
         logits = torch.empty(self.batch, self.classes, device=x.device, dtype=torch.float32)
         self._run(self.net, x.data_ptr(), self.slot_float, self.slot_codes, logits.data_ptr(), self.ws,
-                  torch.cuda.current_stream(x.device).cuda_stream)
+                  torch.cuda.current_stream(x.device).cuda_stream, self.ext)
         return logits
 
     def last_plane(self):
@@ -229,6 +247,68 @@ class _NetPlan:
         nb = 4 * self.last_shape[0] * self.last_shape[1] * self.last_shape[2] * self.last_shape[3]
         o = self._float_off[self.last_slot]
         return self.arena[o:o + nb].view(torch.float32).view(self.last_shape)
+
+
+def _is_pool2(mod):
+    """an ``nn.MaxPool2d`` that is exactly the 2 x 2 / stride-2 pool a conv's kernel can apply to its own output"""
+    pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)  # noqa: E731
+    return (isinstance(mod, nn.MaxPool2d) and pair(mod.kernel_size) == (2, 2) and pair(mod.stride) == (2, 2) and
+            pair(mod.padding) == (0, 0) and pair(mod.dilation) == (1, 1) and not mod.ceil_mode and
+            not mod.return_indices)
+
+
+def _vgg_triples(model):
+    """``[(k, conv, bn, pooled)]`` of a harness VGG's ``features``: conv k with the BatchNorm and ReLU behind it, and
+    whether a 2 x 2 max-pool (``_is_pool2``) follows them; None where ``features`` holds anything else"""
+    mods, out, i = list(model.features), [], 0
+    is_conv = lambda mod: isinstance(mod, nn.Conv2d) or hasattr(mod, "forward_fused")  # noqa: E731
+    while i < len(mods):
+        if not (is_conv(mods[i]) and i + 2 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm2d) and
+                isinstance(mods[i + 2], nn.ReLU)):
+            return None
+        pooled = i + 3 < len(mods) and _is_pool2(mods[i + 3])
+        out.append((i, mods[i], mods[i + 1], pooled))
+        i += 4 if pooled else 3
+    return out
+
+
+class _VggPlan(_NetPlan):
+    """The cimq_net_forward_ex plan of a harness VGG under ``FusedEval(pool=True, net=True)``: the convs of
+    ``features`` in order on fp32 edges, a straight chain's slots, each 2 x 2 max-pool applied by the conv in front of
+    it (``cimq_net_ext.pool``) and ``classifier`` as the flatten head.  ``pooled``: those convs' names."""
+
+    def __init__(self, fused, x):
+        from .. import _lib
+        m, dev = fused.model, x.device
+        self.keep, self.code_edges, self.pooled = [], [], []
+        triples = _vgg_triples(m)
+        if not triples:
+            raise _NoPlan("features is not a sequence of conv, BatchNorm, ReLU triples and 2 x 2 max-pools")
+        n = len(triples)
+        slot_of, n_slots = assign_slots([((), 0)] + [((i - 1,), i) for i in range(1, n)] + [((n - 1,), None)])
+        layers = (_lib.NetLayer * n)()
+        pool, shape = [0] * n, tuple(x.shape)
+        for i, (k, conv, bn, pooled) in enumerate(triples):
+            L = layers[i]
+            desc = self._fill_layer(fused, L, conv, bn, shape, dev)
+            L.in_slot = -1 if i == 0 else slot_of[i - 1]
+            L.out_slot = slot_of[i]
+            in_shape, shape = shape, _out_shape(conv, shape)
+            if pooled:
+                if not conv.pool_ready(torch.empty(1, dtype=torch.uint8, device=dev).expand(in_shape)):
+                    route = _lib.ROUTE_NAMES.get(_lib.module_route(desc)[0], "?")
+                    why = "it is off the wide route (its forward route is %s)" % route if route != "wide" else \
+                        "its output is wider than 32 columns"
+                    raise _NoPlan("features.%d: the max-pool behind it cannot run in its kernel: %s" % (k, why))
+                pool[i] = _lib.CIMQ_POOL_MAX2
+                self.pooled.append("features.%d" % k)
+                shape = shape[:2] + (shape[2] // 2, shape[3] // 2)
+        lin = m.classifier
+        if not isinstance(lin, nn.Linear) or lin.weight.device != dev or lin.weight.dtype != torch.float32 or \
+                not lin.weight.is_contiguous() or lin.in_features != shape[1] * shape[2] * shape[3]:
+            raise _NoPlan("the classifier is not a contiguous fp32 nn.Linear over the flattened last map")
+        self._finish(layers, n_slots, slot_of[n - 1], lin, x, shape,
+                     _lib.make_net_ext(pool, _lib.NET_HEAD_FLATTEN))
 
 
 class _NoPlan(Exception):
@@ -259,15 +339,24 @@ class FusedEval(nn.Module):
     Every conv's output is bit for bit the loop's; the logits differ from the loop's by the summation order of the
     pooling and of the classifier alone.  Shift-ADC layers (``adc_shift``) on the fused shift path are plan layers
     like any other; stochastic-ADC layers run in the loop.  Where a conv is off the library path, the library refuses the plan or the
-    final map is not square, the loop runs: ``net_used`` says which of the two the last forward was."""
+    final map is not square, the loop runs: ``net_used`` says which of the two the last forward was.
 
-    def __init__(self, model, codes=False, net=False):
+    ``pool=True`` (a VGG; a ResNet has nothing to pool): a conv whose ReLU is followed by ``nn.MaxPool2d(2, 2)`` and
+    whose ``pool_ready`` holds stores the pooled plane itself (``forward_fused(pool=2)``, bit for bit the torch pool
+    of its output) and the torch pool is skipped; ``pooled`` lists the convs that did.  With ``net=True`` as well the
+    VGG is one cimq_net_forward_ex call: the convs of ``features`` on fp32 edges, each pool in the conv in front of it
+    and ``classifier`` as the head over the flattened map (``_VggPlan``; the plan is kept under the same key).  A pool
+    behind a conv that cannot pool in its kernel means no plan: the loop runs and ``net_reason`` names the layer."""
+
+    def __init__(self, model, codes=False, net=False, pool=False):
         super().__init__()
         if not isinstance(model, (ResNet, VGG)):
             raise TypeError("FusedEval wraps a harness.models.ResNet or a harness.models.VGG")
         self.model = model
         self.codes = bool(codes)
         self.net = bool(net)
+        self.pool = bool(pool)  # a VGG's 2 x 2 max-pools in the kernel of the conv in front of them (see _forward_vgg)
+        self.pooled = []        # the names of the convs that pooled their own output in the last forward
         self.net_used = False   # whether the last forward ran as one cimq_net_forward call
         self.net_reason = None  # ... and if not, why (the loop ran)
         self.code_edges = []
@@ -281,10 +370,13 @@ class FusedEval(nn.Module):
         and the module names; made once, the model's modules are shared, not copied"""
         if self._chain is None:
             m = self.model
-            chain = [(m.conv1, m.bn1, None)]
-            for stage in (m.layer1, m.layer2, m.layer3):
-                for blk in stage:
-                    chain += [(blk.conv1, blk.bn1, None), (blk.conv2, blk.bn2, blk)]
+            if isinstance(m, VGG):  # (a straight chain: no residuals)
+                chain = [(conv, bn, None) for _, conv, bn, _ in _vgg_triples(m) or ()]
+            else:
+                chain = [(m.conv1, m.bn1, None)]
+                for stage in (m.layer1, m.layer2, m.layer3):
+                    for blk in stage:
+                        chain += [(blk.conv1, blk.bn1, None), (blk.conv2, blk.bn2, blk)]
             self._chain = chain
             self._names = {id(mod): name for name, mod in m.named_modules()}
         return self._chain, self._names
@@ -296,7 +388,7 @@ class FusedEval(nn.Module):
         off the library path (the loop then runs, and says so)"""
         from ..functional import _versions
         chain, _ = self._chain_of()
-        key = [tuple(x.shape), x.device, self.codes]
+        key = [tuple(x.shape), x.device, self.codes, self.pool]
         for conv, bn, _ in chain:
             ready = getattr(conv, "fused_epilogue_ready", None)
             if ready is None or not ready(x):
@@ -306,7 +398,7 @@ class FusedEval(nn.Module):
             key.append(_versions(conv.weight, conv.alpha_act, conv.alpha_weight, conv.alpha_cim, conv.binary_mask,
                                  conv.signed_act, getattr(conv, "beta_cim", None)))
             key.append(_bn_versions(bn))
-        lin = self.model.linear
+        lin = self.model.classifier if isinstance(self.model, VGG) else self.model.linear
         key.append(_versions(getattr(lin, "weight", None), getattr(lin, "bias", None)))
         return tuple(key)
 
@@ -322,7 +414,7 @@ class FusedEval(nn.Module):
         if key != self._net_key:
             self._net_key, self._net_plan = key, None
             try:
-                self._net_plan = _NetPlan(self, x)
+                self._net_plan = (_VggPlan if isinstance(self.model, VGG) else _NetPlan)(self, x)
                 self.net_reason = None
             except _NoPlan as e:
                 self.net_reason = str(e)
@@ -333,6 +425,7 @@ class FusedEval(nn.Module):
             x.to(torch.float32).contiguous().clone()
         y = plan.run(xc)
         self.code_edges = list(plan.code_edges)
+        self.pooled = list(getattr(plan, "pooled", ()))
         return y
 
     def tables(self, bn):
@@ -410,7 +503,7 @@ class FusedEval(nn.Module):
         mods = list(self.model.features)
         names = {id(mod): "features.%d" % k for k, mod in enumerate(mods)}
         is_conv = lambda mod: isinstance(mod, nn.Conv2d) or hasattr(mod, "forward_fused")  # noqa: E731
-        self.code_edges = []
+        self.code_edges, self.pooled = [], []
         y, i = x, 0  # y: the current activation, fp32 or (handed by the conv before) the consumer's codes
         while i < len(mods):
             mod = mods[i]
@@ -421,6 +514,14 @@ class FusedEval(nn.Module):
             if not (i + 2 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm2d) and isinstance(mods[i + 2], nn.ReLU)):
                 raise RuntimeError("FusedEval: a VGG conv without its BatchNorm and ReLU behind it")
             bn = mods[i + 1]
+            # pool=True: the 2 x 2 max-pool behind the ReLU runs in this conv's kernel where the layer can (pool_ready)
+            if self.pool and i + 3 < len(mods) and _is_pool2(mods[i + 3]) and y.dtype != torch.uint8 and \
+                    hasattr(mod, "pool_ready") and mod.pool_ready(y):
+                scale, shift = self.tables(bn)
+                y = mod.forward_fused(y, scale, shift, relu=True, pool=2)
+                self.pooled.append(names[id(mod)])
+                i += 4
+                continue
             nxt = mods[i + 3] if i + 3 < len(mods) and is_conv(mods[i + 3]) else None
             hand = False
             if self.codes and nxt is not None and hasattr(mod, "codes_ready") and hasattr(nxt, "codes_ready"):
@@ -441,8 +542,15 @@ class FusedEval(nn.Module):
         if torch.is_grad_enabled():
             raise RuntimeError("FusedEval is evaluation only: call it under torch.no_grad()")
         if isinstance(self.model, VGG):
-            if self.net:  # (a plan of wide layers and max-pools: a follow-up)
-                self.net_used, self.net_reason = False, "a VGG runs in the loop: its max-pools are torch operations"
+            if self.net and self.pool:  # the max-pools in the convs' kernels: the whole network is one plan
+                y = self._forward_net(x)
+                self.net_used = y is not None
+                if y is not None:
+                    return y
+            elif self.net:
+                self.net_used = False
+                self.net_reason = "a VGG runs in the loop: its max-pools are torch operations (pool=True moves them " \
+                                  "into the convs' kernels)"
             return self._forward_vgg(x)
         if self.net:
             y = self._forward_net(x)

@@ -50,6 +50,9 @@ def get_base_parser():
     p.add_argument("--fused-net", action="store_true",
                    help="--fused-eval with each forward as one library call (FusedEval(model, net=True): "
                         "cimq_net_forward; combines with --fused-codes)")
+    p.add_argument("--fused-pool", action="store_true",
+                   help="--fused-eval with a VGG's 2x2 max-pools in the kernels of the convs in front of them "
+                        "(FusedEval(model, pool=True)); with --fused-net the VGG is one library call")
     p.add_argument("--adc-shift", action="store_true",
                    help="Conv2dLSQCiM(adc_shift=True): the per-tile scale + shift ADC with a learnable beta_cim "
                         "(adcbits 1 / 1.5; a launcher flag, not a prototxt field: the schema stays the reference's)")
@@ -205,7 +208,7 @@ def train_epoch(loader, model, criterion, optimizer, epoch, hp, max_steps=0, log
     return loss_sum / max(seen, 1), top1 / max(seen, 1)
 
 
-def validate(loader, model, criterion, hp, max_steps=0, fused=False, codes=False, net=False):
+def validate(loader, model, criterion, hp, max_steps=0, fused=False, codes=False, net=False, pool=False):
     """main_lsq.py's validate(): top-1 / top-5 accuracy and mean loss in eval mode under no_grad.
     Nothing here selects the evaluation path: under no_grad every Conv2dLSQCiM runs libcimq's
     forward-only mode by itself (CIMQ_OPT_INFERENCE: same outputs, no backward state) and keeps its
@@ -214,16 +217,19 @@ def validate(loader, model, criterion, hp, max_steps=0, fused=False, codes=False
     conv kernels' epilogue; not bit-identical to the BatchNorm path, see that module).  ``codes`` (with
     ``fused``): FusedEval(model, codes=True) -- activation codes between the convs, the same logits.  ``net``
     (with ``fused``): FusedEval(model, net=True) -- each forward one cimq_net_forward call; the convs' outputs are
-    the loop's, the logits differ by the head's summation order alone."""
+    the loop's, the logits differ by the head's summation order alone.  ``pool`` (with ``fused``):
+    FusedEval(model, pool=True) -- a VGG's max-pools in the convs' kernels; with ``net`` the VGG is one call."""
     model.eval()
     if codes and not fused:
         raise ValueError("validate: codes=True needs fused=True")
     if net and not fused:
         raise ValueError("validate: net=True needs fused=True")
+    if pool and not fused:
+        raise ValueError("validate: pool=True needs fused=True")
     if fused:
         from .fuse import FusedEval
         bare = model.module if isinstance(model, nn.parallel.DistributedDataParallel) else model
-        model = FusedEval(bare, codes=codes, net=net)
+        model = FusedEval(bare, codes=codes, net=net, pool=pool)
     seen, loss_sum, c1, c5 = 0, 0.0, 0.0, 0.0
     with torch.no_grad():
         for i, (x, y) in enumerate(loader):
@@ -272,8 +278,8 @@ def main(argv=None):
     train_loader = CifarLoader(xtr, ytr, batch, device, train=True, seed=seed, rank=rank, world=world)
     val_loader = CifarLoader(xte, yte, batch, device, train=False)
     log = print if rank == 0 else (lambda *a, **k: None)
-    ev = dict(fused=args.fused_eval or args.fused_codes or args.fused_net, codes=args.fused_codes,
-              net=args.fused_net)  # how validate evaluates
+    ev = dict(fused=args.fused_eval or args.fused_codes or args.fused_net or args.fused_pool, codes=args.fused_codes,
+              net=args.fused_net, pool=args.fused_pool)  # how validate evaluates
     if hp.evaluate:
         acc1, acc5, _ = validate(val_loader, model, criterion, hp, args.max_val_steps, **ev)
         log(f" * Acc@1 {acc1:.3f} Acc@5 {acc5:.3f}")

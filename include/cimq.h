@@ -322,6 +322,35 @@ int cimq_module_forward_epilogue(const cimq_conv_desc* d, const cimq_lsq_desc* q
                                  const float* signed_act, const cimq_epilogue* epi, float* out, void* ctx, void* ws,
                                  void* stream);
 
+/* ---- the epilogue's values through a 2x2 max pool (cimq_pool_abi() == 1; CIMQ_ABI_VERSION / _MINOR and the other
+ * availability numbers are unchanged: new symbols alone) ----
+ *
+ * A CIMQ_ROUTE_WIDE layer can store, instead of its [B, O, Ho, Wo] output, that output's 2x2 / stride-2 max pool
+ * [B, O, Ho/2, Wo/2], computed in the registers of the storing kernel on the values the epilogue produces (scale,
+ * shift, residual, ReLU): bit for bit torch's max_pool2d(., 2, 2) of cimq_module_forward_epilogue's output -- the
+ * first maximal element of a window in the order (0,0), (0,1), (1,0), (1,1), any NaN in a window gives NaN. */
+#define CIMQ_POOL_MAX2 2 /* the `pool` argument / cimq_net_ext.pool entry: 2x2 windows, stride 2, no padding */
+
+/* 1 where the calls of this section exist (a library from before them has no such symbol). */
+int cimq_pool_abi(void);
+
+/* Whether cimq_module_forward_pool takes d with pool == CIMQ_POOL_MAX2: a host query, no device work.  *ok is 1
+ * where d has CIMQ_OPT_INFERENCE, its forward route is CIMQ_ROUTE_WIDE, its output is at most 32 wide (both rows of a
+ * window then sit in one 64-pixel tile) and the kernel's LDS holds the row exchange (every layer of two or more weight
+ * slices or two K-steps); else 0.  Returns CIMQ_OK, CIMQ_EINVAL for a NULL argument, or the descriptor's own error. */
+int cimq_module_pool_supported(const cimq_conv_desc* d, int* ok);
+
+/* cimq_module_forward_epilogue with ``pool`` before ``out``.  pool == 0: that call exactly.  pool == CIMQ_POOL_MAX2:
+ * out is [B, O, Ho/2, Wo/2], the pooled plane alone is written; epi->residual keeps the unpooled shape
+ * [B, O, Ho, Wo]; the same launches (one for a prepared layer), the same q->wprep rules, ctx and workspace as
+ * cimq_query_sizes reports.  CIMQ_EINVAL: every refusal of cimq_module_forward_epilogue (the overlap test takes out's
+ * pooled extent), any other ``pool``.  CIMQ_EUNSUPPORTED, nothing launched or written: a layer for which
+ * cimq_module_pool_supported answers 0, or beta_cim given (cimq_last_error names the reason). */
+int cimq_module_forward_pool(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* x, const float* weight,
+                             const float* alpha_act, const float* alpha_weight, const float* alpha_cim,
+                             const float* beta_cim, const int8_t* binary_mask, const float* signed_act,
+                             const cimq_epilogue* epi, int pool, float* out, void* ctx, void* ws, void* stream);
+
 /* cimq_act_codes.flags */
 #define CIMQ_CODES_NO_FLOAT 1 /* out is not written and may be NULL (needs out_codes) */
 
@@ -449,6 +478,38 @@ int cimq_net_sizes(const cimq_net_desc* net, size_t* slot_float_bytes, size_t* s
  * with an output width that is no multiple of 4; a head over more than CIMQ_NET_HEAD_MAX_C channels. */
 int cimq_net_forward(const cimq_net_desc* net, const float* x, void* const* slot_float, void* const* slot_codes,
                      float* logits, void* ws, void* stream);
+
+/* cimq_net_ext.head_flags */
+#define CIMQ_NET_HEAD_FLATTEN 1 /* the head reads its slot's [B, C, H, W] plane as [B, C*H*W, 1, 1]: y = W flat(x) + b */
+
+/* What a plan may add without moving cimq_net_layer / _head / _desc (cimq_pool_abi() == 1): pooled layers and a
+ * classifier over the flattened map (VGG).  A layer with pool[i] == CIMQ_POOL_MAX2 is the cimq_module_forward_pool
+ * call: its slot holds [B, O, Ho/2, Wo/2] -- the shape its consumers' descriptors, cimq_net_sizes_ex's bytes and the
+ * head see -- while its residual, a whole tensor, has the unpooled shape. */
+typedef struct cimq_net_ext {
+  const int32_t* pool;   /* NULL, or n_layers entries: 0, or CIMQ_POOL_MAX2 for that layer's output */
+  int32_t head_flags;    /* CIMQ_NET_HEAD_FLATTEN (1): the head reads its slot's [B,C,H,W] plane as [B, C*H*W, 1, 1] */
+  int32_t reserved[3];   /* 0 */
+} cimq_net_ext;
+
+/* cimq_net_sizes / cimq_net_forward with ``ext``; ext == NULL is that call exactly.  On top of its refusals, all
+ * before the first launch -- CIMQ_EINVAL: a pool entry other than 0 / CIMQ_POOL_MAX2, unknown head_flags, a non-zero
+ * reserved.  CIMQ_EUNSUPPORTED: a pooled layer for which cimq_module_pool_supported answers 0 (a pooled layer with
+ * out_mode & 2 or a residual view is the wide route's own refusal); a flatten head over more than
+ * CIMQ_NET_HEAD_MAX_C features (C*H*W; with the flag, head->pooled is [B, C*H*W]).
+ *
+ * One more thing a non-NULL ext changes, an all-zero one included: which kernel a w8a8 layer on CIMQ_ROUTE_V3 runs
+ * (eight 1-bit slices a side, the library ADC, a float-only edge, W % 4 == 0: the first conv of the CIFAR networks, in
+ * a ResNet plan as in a VGG one).  Under cimq_net_forward and the per-layer calls such a layer is two launches: the
+ * activation prologue, which writes the slice words of x into its ctx, then the forward.  In a cimq_net_forward_ex
+ * plan the forward kernel quantises x in its own row staging (an instance of its own, the prologue's element chain)
+ * and the prologue is not launched: one launch for a prepared layer, the same plane bit for bit, the same sizes; the
+ * ctx's slice-word region goes unwritten.  cimq_module_forward_form's answer for the layer (form[1] == 0) describes
+ * the per-layer calls and is unchanged.  VGG-small with q->wprep set on every layer is so 7 kernels: 6 convs + head. */
+int cimq_net_sizes_ex(const cimq_net_desc* net, size_t* slot_float_bytes, size_t* slot_code_bytes, size_t* ws_bytes,
+                      const cimq_net_ext* ext);
+int cimq_net_forward_ex(const cimq_net_desc* net, const float* x, void* const* slot_float, void* const* slot_codes,
+                        float* logits, void* ws, void* stream, const cimq_net_ext* ext);
 
 /* One layer of cimq_module_prepare: its descriptors (as the forward will receive them; the
  * lsq descriptor's wprep and flags are ignored here) and raw parameters, and its output buffer

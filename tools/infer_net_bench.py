@@ -33,6 +33,11 @@ second window) comes from the package and the libcimq.so of another checkout of 
 beforehand -- e.g. the parent commit's -- loaded into the same process under another name, on a model of its own
 made from the same seed; the other sides are this tree's.  The defaults, and the files they write, are unchanged.
 
+``--arch vggsmall`` is the harness VGG-small (VGG7, five wide 3 x 3 layers, three 2 x 2 max-pools).  ``--pool`` adds
+side P, FusedEval(model, pool=True): the max-pools in the store of the convs in front of them; with ``--net`` side D
+is FusedEval(model, net=True, pool=True), the whole VGG as one cimq_net_forward_ex call.  The rounds run A, B, P, D, B
+again (-> profiles/vgg_pool/infer_net_bench_vggsmall_B256.json).
+
 Needs the GPU: there is no CPU fallback and no number without a run.
 """
 from __future__ import annotations
@@ -79,7 +84,7 @@ def build_model(batch, dev, arch="resnet20", bits=3, xbar=bench.XBAR, adc_shift=
         conv_cls = importlib.import_module(pkg.__name__ + "._modules.lsq").Conv2dLSQCiM
         tool_cls = importlib.import_module(pkg.__name__ + ".harness.replace").ReplaceModuleTool
     torch.manual_seed(20)
-    model = getattr(mods, arch)()
+    model = getattr(mods, "cifar10_vggsmall" if arch == "vggsmall" else arch)()
     tool_cls(model, {"Conv2d": [conv_cls]}, True, nbits_w=bits, nbits_a=bits, nbits_alpha=8, wbitslice=1,
              abitslice=1, xbar=xbar, adcbits=bench.ADC, signed_xbar=True, stochastic_quant=False,
              **({"adc_shift": True} if adc_shift else {})).replace()
@@ -124,7 +129,10 @@ def main(argv=None):
     ap.add_argument("--codes", action="store_true", help="add side C, FusedEval(model, codes=True): A, B, C, B per round")
     ap.add_argument("--net", action="store_true",
                     help="add side D, FusedEval(model, net=True) (with --codes also E, net=True and codes=True)")
-    ap.add_argument("--arch", default="resnet20", choices=("resnet20", "resnet32", "resnet44", "resnet56"))
+    ap.add_argument("--arch", default="resnet20", choices=("resnet20", "resnet32", "resnet44", "resnet56", "vggsmall"))
+    ap.add_argument("--pool", action="store_true",
+                    help="add side P, FusedEval(model, pool=True) (a VGG's max-pools in the conv kernels); with --net "
+                         "side D is net=True, pool=True")
     ap.add_argument("--bits", type=int, default=3, help="weight and activation bits of every conv but the first")
     ap.add_argument("--xbar", type=int, default=bench.XBAR)
     ap.add_argument("--adc-shift", action="store_true", help="Conv2dLSQCiM(adc_shift=True) layers")
@@ -136,6 +144,8 @@ def main(argv=None):
         raise SystemExit("infer_net_bench: no ROCm device (there is no CPU fallback; nothing is measured)")
     tag = "_shift" if args.adc_shift else "_net" if args.net else "_codes" if args.codes else ""
     out_path = args.out or os.path.join(REPO, "profiles", "inference", f"infer_net_bench{tag}_B{args.batch}.json")
+    if args.arch == "vggsmall" and not args.out:
+        out_path = os.path.join(REPO, "profiles", "vgg_pool", f"infer_net_bench_vggsmall_B{args.batch}.json")
     dev = torch.device("cuda:0")
     net_kw = dict(arch=args.arch, bits=args.bits, xbar=args.xbar, adc_shift=args.adc_shift)
     model, x = build_model(args.batch, dev, **net_kw)
@@ -152,9 +162,13 @@ def main(argv=None):
         coded = FusedEval(model, codes=True)
         sides["C"] = lambda: coded(x)
         order = ("A", "B", "C", "B2")
+    if args.pool:
+        pooled = FusedEval(model, pool=True)
+        sides["P"] = lambda: pooled(x)
+        order = (order[:-1] if order[-1] == "B2" else ("A", "B")) + ("P", "B2")
     nets = {}
     if args.net:
-        nets["D"] = FusedEval(model, net=True)
+        nets["D"] = FusedEval(model, net=True, pool=True) if args.pool else FusedEval(model, net=True)
         if args.codes:
             nets["E"] = FusedEval(model, net=True, codes=True)
         for k, f in nets.items():
@@ -168,6 +182,11 @@ def main(argv=None):
             codes_info = {"logits_equal_B": bool(torch.equal(yb, yc)), "code_edges": len(coded.code_edges),
                           "edges_codes_only": sum(e[2] == "codes" for e in coded.code_edges)}
             del yc
+        pool_info = None
+        if args.pool:
+            yp = sides["P"]()
+            pool_info = {"logits_equal_B": bool(torch.equal(yb, yp)), "pooled": list(pooled.pooled)}
+            del yp
         diff = {"max_abs_logit_difference": float((ya - yb).abs().max()), "max_abs_logit": float(ya.abs().max()),
                 "top1_agree": float((ya.argmax(1) == yb.argmax(1)).float().mean())}
         net_info = {}
@@ -204,7 +223,7 @@ def main(argv=None):
     twin = order[-1]  # the repeated side: the same code, the same call
     spread = max(abs(a - b) for a, b in zip(tot[twin[0]], tot[twin]))
     result = {
-        "workload": f"harness ResNet-{args.arch[6:]} evaluation forward (model(x) vs FusedEval(model)(x)), eval + no_grad, "
+        "workload": f"harness {'VGG-small' if args.arch == 'vggsmall' else 'ResNet-' + args.arch[6:]} evaluation forward (model(x) vs FusedEval(model)(x)), eval + no_grad, "
                     f"B = {args.batch}, w{args.bits}a{args.bits} (first conv w8a8), xbar {args.xbar}, adc {bench.ADC}"
                     f"{', scale + shift ADC (adc_shift)' if args.adc_shift else ''}, synthetic input",
         "device": torch.cuda.get_device_name(0), "abi": _lib.ABI_VERSION,
@@ -227,8 +246,15 @@ def main(argv=None):
         result["C_minus_B_us"] = round(med["C"] - med["B"], 1)
         result["C_not_above_B_by_more_than_spread"] = bool(med["C"] <= med["B"] + spread)
         result["codes"] = codes_info
+    if args.pool:
+        result["workload"] += "; side P = FusedEval(model, pool=True)(x)"
+        result["pool"] = pool_info
+        result["P_minus_B_us"] = round(med["P"] - med["B"], 1)
+        result["P_below_B_by_more_than_spread"] = bool(med["P"] < med["B"] - spread)
+        result["P_above_B_by_more_than_spread"] = bool(med["P"] > med["B"] + spread)
     if args.net:
-        result["workload"] += "; side D = FusedEval(model, net=True)(x)" + (", E = net=True, codes=True" if args.codes else "")
+        result["workload"] += "; side D = FusedEval(model, net=True%s)(x)" % (", pool=True" if args.pool else "") + \
+            (", E = net=True, codes=True" if args.codes else "")
         result["net"] = net_info
         for k in nets:
             result[f"{k}_minus_B_us"] = round(med[k] - med["B"], 1)
@@ -239,6 +265,8 @@ def main(argv=None):
         f.write("\n")
     keys = ("forward_us", "spread_us", "B_minus_A_us", "kernel_launches_per_forward", "peak_memory_bytes",
             "fused_vs_batchnorm_path") + (("C_minus_B_us", "C_not_above_B_by_more_than_spread", "codes") if args.codes else ())
+    if args.pool:
+        keys += ("pool", "P_minus_B_us", "P_below_B_by_more_than_spread", "P_above_B_by_more_than_spread")
     if args.net:
         keys += ("net",) + tuple(f"{k}_minus_B_us" for k in nets) + tuple(f"{k}_below_B_by_more_than_spread" for k in nets)
     print(json.dumps({k: result[k] for k in keys}))

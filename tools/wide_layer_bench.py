@@ -15,6 +15,14 @@ alternate them in child processes of one GPU session, each under its own time li
 The summary gives, per shape, precision, column and tag, the median over the runs and their spread (max - min), and
 per column whether the new median is lower than the parent's by more than the larger of the two spreads -- the gate a
 shape has to pass to stay in wide_plan.
+
+``--pool``: VGG7's three pooled shapes (128 -> 128 @ 32, 256 -> 256 @ 16, 512 -> 512 @ 8) instead:
+``forward_fused(pool=2)`` -- the 2 x 2 max pool in the conv kernel's store -- against the pair it replaces,
+``forward_fused`` followed by ``F.max_pool2d(., 2, 2)``, both with the folded affine and the ReLU, each a HIP graph,
+alternated over ``--runs`` runs (3) in this one session: per layer the medians, the spreads (max - min) and whether the
+pooled call is faster, or slower, than the pair by more than the larger spread.
+
+    python tools/wide_layer_bench.py --pool --out profiles/vgg_pool/layers.json
 """
 from __future__ import annotations
 
@@ -100,6 +108,76 @@ def measure(args):
     return out
 
 
+POOL_SHAPES = [(128, 128, 32), (256, 256, 16), (512, 512, 8)]
+
+
+def measure_pool(args):
+    import torch
+    import torch.nn.functional as TF
+
+    import cim_quantization_amd._lib as L
+    import cim_quantization_amd._modules as my_nn
+    from infer_net_bench import count_launches
+    from w4a4_layer_bench import _graph_ms
+    if not torch.cuda.is_available():
+        raise SystemExit("wide_layer_bench measures on a GPU; none found")
+    dev = torch.device("cuda", 0)
+    rows = []
+    for bits in args.bits:
+        for c, o, h in POOL_SHAPES:
+            torch.manual_seed(11)
+            m = my_nn.Conv2dLSQCiM(c, o, 3, 1, 1, bias=False, nbits_w=bits, nbits_a=bits, nbits_alpha=8, wbitslice=1,
+                                   abitslice=1, xbar=128, adcbits=1.5)
+            torch.nn.init.kaiming_normal_(m.weight)
+            m = m.to(dev).train()
+            x = torch.randn(args.batch, c, h, h, device=dev).relu()
+            g2 = torch.randn(2, o, h, h, device=dev) / math.sqrt(2 * o * h * h)
+            m(x[:2].contiguous()).backward(g2)  # the first step on two images (see measure)
+            scale, shift = torch.randn(o, device=dev), torch.randn(o, device=dev)
+            m.eval()
+            with torch.no_grad():
+                m(x)  # the kept weight side
+                if not m.pool_ready(x):
+                    raise SystemExit(f"wide_layer_bench --pool: {c} -> {o} @ {h} does not pool in its kernel")
+
+                def pair():
+                    TF.max_pool2d(m.forward_fused(x, scale, shift, relu=True), 2, 2)
+
+                def pooled():
+                    m.forward_fused(x, scale, shift, relu=True, pool=2)
+
+                equal = bool(torch.equal(TF.max_pool2d(m.forward_fused(x, scale, shift, relu=True), 2, 2),
+                                         m.forward_fused(x, scale, shift, relu=True, pool=2)))
+                us = {"pair": [], "pooled": []}
+                for _ in range(args.runs):
+                    us["pair"].append(1e3 * _graph_ms(pair, args.steps, args.warmup))
+                    us["pooled"].append(1e3 * _graph_ms(pooled, args.steps, args.warmup))
+                n_pair, n_pool = count_launches(pair), count_launches(pooled)
+            e = {"bits": bits, "C": c, "O": o, "H": h, "equal": equal,
+                 "launches": {"pair": n_pair, "pooled": n_pool}}
+            for k, v in us.items():
+                e["us_" + k] = {"median": statistics.median(v), "spread": max(v) - min(v), "runs": v}
+            bar = max(e["us_pair"]["spread"], e["us_pooled"]["spread"])
+            gain = e["us_pair"]["median"] - e["us_pooled"]["median"]
+            e["gate"] = {"gain_us": gain, "bar_us": bar, "speedup": e["us_pair"]["median"] / e["us_pooled"]["median"],
+                         "faster": gain > bar, "slower": -gain > bar}
+            rows.append(e)
+            print(f"w{bits}a{bits} {c:3d}->{o:3d} {h:2d}x{h:<2d} conv + max_pool2d {e['us_pair']['median']:9.1f}"
+                  f"+-{e['us_pair']['spread']:6.1f} us  pooled store {e['us_pooled']['median']:9.1f}"
+                  f"+-{e['us_pooled']['spread']:6.1f} us  gain {gain:8.1f} us  faster {e['gate']['faster']}  "
+                  f"slower {e['gate']['slower']}  equal {equal}", flush=True)
+            del m, x
+            torch.cuda.empty_cache()
+    out = {"lib": os.path.relpath(L.LIB_PATH), "batch": args.batch, "xbar": 128, "adc": 1.5, "steps": args.steps,
+           "warmup": args.warmup, "runs": args.runs, "launch": "hip_graph",
+           "device": torch.cuda.get_device_name(dev), "layers": rows}
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+    return out
+
+
 def summarise(args):
     runs = {}
     for p in sorted(glob.glob(os.path.join(args.summarise, "*.json"))):
@@ -151,8 +229,13 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--summarise", default=None, metavar="DIR", help="merge the runs under DIR instead of measuring")
+    ap.add_argument("--pool", action="store_true",
+                    help="time forward_fused(pool=2) against forward_fused + F.max_pool2d on VGG7's pooled shapes")
+    ap.add_argument("--runs", type=int, default=3, help="--pool: alternated runs of the two sides")
     args = ap.parse_args()
-    if args.summarise:
+    if args.pool:
+        measure_pool(args)
+    elif args.summarise:
         summarise(args)
     else:
         measure(args)
