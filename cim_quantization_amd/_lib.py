@@ -23,10 +23,11 @@ CIMQ_INPUT_XQ = 0
 CIMQ_INPUT_RAW_LSQ = 1
 # cimq_module_route codes (include/cimq.h CIMQ_ROUTE_*)
 ROUTE_NAMES = {0: "general", 1: "v3", 2: "fwd5", 3: "v7", 4: "fused", 5: "c1", 6: "gx5", 7: "gw5", 8: "dense", 9: "r6",
-               10: "none", 11: "wide"}
+               10: "none", 11: "wide", 12: "wide_bwd"}
 CIMQ_ROUTE_R6 = 9
 CIMQ_ROUTE_NONE = 10  # route[1] / route[2] under CIMQ_OPT_INFERENCE (ABI 15)
 CIMQ_ROUTE_WIDE = 11  # route[0]: cim_fwd_wide_kernel (cimq_wide_abi() == 1)
+CIMQ_ROUTE_WIDE_BWD = 12  # route[1] / route[2] of such a layer under CIMQ_OPT_WIDE_BWD (cimq_wide_bwd_abi() == 1)
 CIMQ_LSQ_ACCUMULATE_GRADS = 1
 CIMQ_LSQ_SKIP_TAIL = 2
 CIMQ_LSQ_DEFER_GW = 4
@@ -38,6 +39,7 @@ CIMQ_ADC_SHIFT_SIGN = 3
 CIMQ_ADC_F_PS_INT8 = 0x100
 CIMQ_ADC_F_SHIFT_RANGE = 0x200
 CIMQ_OPT_RECOMPUTE = 1  # cimq_conv_desc.options (ABI 14)
+CIMQ_OPT_WIDE_BWD = 16  # a wide layer trains on the compact-state backward where its plan applies (bit 8 is refused)
 CIMQ_OPT_INFERENCE = 4  # forward only: nothing written that a backward would read (ABI 15; bit 2 is refused)
 CIMQ_EPI_RELU = 1  # cimq_epilogue.flags (ABI 16)
 CIMQ_CODES_NO_FLOAT = 1  # cimq_act_codes.flags (ABI 16, minor 1)
@@ -68,6 +70,8 @@ EXPORTED_SYMBOLS = (
     "cimq_module_forward_form",
     "cimq_wide_abi",
     "cimq_module_wide_plan",
+    "cimq_wide_bwd_abi",
+    "cimq_module_wide_bwd_plan",
     "cimq_module_shift_forward",
     "cimq_module_shift_backward",
     "cimq_module_forward_epilogue",
@@ -312,6 +316,11 @@ def _bind(lib):
     lib.cimq_net_forward.restype = ctypes.c_int
     lib.cimq_net_forward.argtypes = [ctypes.POINTER(NetDesc), _VP, ctypes.POINTER(_VP), ctypes.POINTER(_VP), _VP, _VP,
                                      _VP]
+    if hasattr(lib, "cimq_wide_bwd_abi"):
+        lib.cimq_wide_bwd_abi.restype = ctypes.c_int
+        lib.cimq_wide_bwd_abi.argtypes = []
+        lib.cimq_module_wide_bwd_plan.restype = ctypes.c_int
+        lib.cimq_module_wide_bwd_plan.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_int)]
     if hasattr(lib, "cimq_pool_abi"):
         lib.cimq_pool_abi.restype = ctypes.c_int
         lib.cimq_pool_abi.argtypes = []
@@ -488,6 +497,14 @@ def module_wide_plan(desc: ConvDesc):
     cimq_module_wide_plan (cimq_wide_abi() == 1)."""
     f = (ctypes.c_int * 4)()
     check(load().cimq_module_wide_plan(ctypes.byref(desc), f), "cimq_module_wide_plan")
+    return tuple(f)
+
+
+def module_wide_bwd_plan(desc: ConvDesc):
+    """(ok, channel chunks, bands per image, grad_w pixel chunks) of the wide layers' compact-state backward for
+    ``desc`` -- cimq_module_wide_bwd_plan (cimq_wide_bwd_abi() == 1); the option bit need not be set."""
+    f = (ctypes.c_int * 4)()
+    check(load().cimq_module_wide_bwd_plan(ctypes.byref(desc), f), "cimq_module_wide_bwd_plan")
     return tuple(f)
 
 

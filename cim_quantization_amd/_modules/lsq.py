@@ -85,6 +85,10 @@ class Conv2dLSQCiM(_Conv2dQCiM):
         # state words between forward and backward (33.5 MB less per 16-channel ResNet-20 layer at B = 256) and
         # recompute the partial sums in the backward -- slower on MI355X, so off by default
         self.recompute_psum = False
+        # CIMQ_OPT_WIDE_BWD: a wide layer (3x3 from 128 input channels up) whose plan the library accepts
+        # (cimq_module_wide_bwd_plan) trains from compact state words on the channel-chunked backward kernels
+        # instead of the general ones; a hint like recompute_psum, without effect on any other layer
+        self.wide_backward = False
         self._wprep = None        # functional.prepare_weights: the next forward's weight side, computed ahead
         self._inf_prep = None     # functional.inference_weights: the weight side the no-grad forwards share
         self._last_x_shape = None
@@ -171,7 +175,7 @@ class Conv2dLSQCiM(_Conv2dQCiM):
                                   self.binary_mask, self.signed_act, *self.layer_config(),
                                   self.accumulate_grads_in_place, bool(self.stochastic_quant),
                                   self.tail_stream if self.accumulate_grads_in_place else None, wprep,
-                                  self.recompute_psum)
+                                  self.recompute_psum, self.wide_backward)
             if self.bias is not None:
                 out = out + self.bias  # broadcasts over the last axis, as lsq.py:583
             return out

@@ -52,7 +52,7 @@ int prep_all(const Geo& g, const float* x, const float* w_q, const float* sa, co
     CIMQ_TRY(check_hip("prep_wgx"));
   }
   if (need_wgx && r.wcy) {
-    const int ncpbt = v7_plan(g).v.NCPBT;
+    const int ncpbt = wcy_blocks(g);
     const int tc = g.T * ncpbt * g.NKS * 64;
     hipLaunchKernelGGL(prep_wcy_kernel, dim3(cdiv(tc, blk)), dim3(blk), 0, s, g, w_q, sw, ncpbt,
                        reinterpret_cast<v4i*>(wreg(g, ctx) + L.wcy));
@@ -90,6 +90,7 @@ int dispatch_bwd_any(const Geo& g, const uint8_t* ctx, const float* sw, const fl
       if (g.nbw == 2) return launch_v7_n<2, 2>(g, v7_plan(g), ctx, sw, sa, gout, x, gx, ws, s, parts);
       if (g.nbw == 4) return launch_v7_n<4, 4>(g, v7_plan(g), ctx, sw, sa, gout, x, gx, ws, s, parts);
       return launch_v7_n<3, 3>(g, v7_plan(g), ctx, sw, sa, gout, x, gx, ws, s, parts);
+    case CIMQ_ROUTE_WIDE_BWD: return launch_wide_bwd(g, wide_bwd_plan(g), ctx, sw, sa, gout, x, gx, ws, s, parts);
     case CIMQ_ROUTE_DENSE: return launch_dense_bwd(g, ctx, sw, gout, gx, ws, s, r.lsq_fused ? x : nullptr, sa);
     case CIMQ_ROUTE_GENERAL: return launch_bwd_general(g, ctx, sw, sa, signed_act, gout, x, gx, ws, s);
     default: return fail(CIMQ_EINVAL, "internal: a forward-only descriptor has no backward");
@@ -506,7 +507,6 @@ static ModulePrep module_prep_args(const Geo& g, const float* x, const float* we
   CtxLayout L = ctx_layout(g);
   uint8_t* wr = wreg(g, c);
   const Route r = route_of(g);
-  const Plan7 p7 = v7_plan(g);
   ModulePrep a;
   memset(&a, 0, sizeof(a));
   a.x = x;
@@ -527,8 +527,8 @@ static ModulePrep module_prep_args(const Geo& g, const float* x, const float* we
   a.nwf = g.T * g.KS * g.NBLK * 64;
   // the backward's operands as the Route asks for them (none in a forward-only call)
   a.nwg = r.wgx ? g.T * g.FBT * g.NKS * 64 : 0;       // general / dense grad_x operand
-  a.ncpbt = p7.ok ? p7.v.NCPBT : 1;
-  a.nwc = r.wcy ? g.T * p7.v.NCPBT * g.NKS * 64 : 0;  // v8 grad_x operand
+  a.ncpbt = wcy_blocks(g);
+  a.nwc = r.wcy ? g.T * a.ncpbt * g.NKS * 64 : 0;  // v8 grad_x operand
   const Plan5 p5 = f5_plan(g);
   a.wf5 = reinterpret_cast<v4i*>(wr + L.wf5);
   a.f5 = f5w_of(p5.v);
@@ -780,6 +780,21 @@ int cimq_module_wide_plan(const cimq_conv_desc* d, int out[4]) {
   out[1] = ok ? p.w.nch : 0;
   out[2] = ok ? p.groups : 0;
   out[3] = ok ? g.T : 0;
+  return CIMQ_OK;
+}
+
+int cimq_wide_bwd_abi(void) { return 1; }
+
+int cimq_module_wide_bwd_plan(const cimq_conv_desc* d, int out[4]) {
+  Geo g;
+  CIMQ_TRY(make_geo(d, &g));
+  if (!out) return fail(CIMQ_EINVAL, "null out");
+  if (g.input_kind != CIMQ_INPUT_RAW_LSQ) return fail(CIMQ_EINVAL, "module entry points take the raw activation");
+  const PlanWB p = wide_bwd_plan(module_form(g));
+  out[0] = p.ok ? 1 : 0;
+  out[1] = p.ok ? p.w.ncc : 0;
+  out[2] = p.ok ? p.v.nbands : 0;
+  out[3] = p.ok ? p.v.nchunks : 0;
   return CIMQ_OK;
 }
 

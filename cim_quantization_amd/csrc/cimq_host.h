@@ -144,8 +144,10 @@ inline int make_geo(const cimq_conv_desc* d, Geo* out) {
   g.ps_int8 = (d->adc_variant & CIMQ_ADC_F_PS_INT8) ? 1 : 0;
   g.seed_lo = d->seed_lo;
   g.seed_hi = d->seed_hi;
-  if (d->options & ~(CIMQ_OPT_RECOMPUTE | CIMQ_OPT_INFERENCE))
+  if (d->options & ~(CIMQ_OPT_RECOMPUTE | CIMQ_OPT_INFERENCE | CIMQ_OPT_WIDE_BWD))
     return fail(CIMQ_EINVAL, "unknown options 0x%x", d->options);
+  // (a hint, like the recompute bit: wide_bwd_plan decides; with CIMQ_OPT_INFERENCE there is no backward to choose)
+  g.wide_bwd = (d->options & CIMQ_OPT_WIDE_BWD) ? 1 : 0;
   g.inference = (d->options & CIMQ_OPT_INFERENCE) ? 1 : 0;
   // (with CIMQ_OPT_INFERENCE the recompute bit changes nothing that runs: it only keeps the weight-side
   // layout, and so wprep_bytes, what it is without the inference bit)
@@ -699,6 +701,105 @@ inline bool wide_pool_ok(const Geo& g, const PlanW& p, const char** why = nullpt
   return r == nullptr;
 }
 
+// ---- the channel-chunked compact-state backward of a wide layer (cimq_wide_bwd.hip; CIMQ_OPT_WIDE_BWD) ----
+// grad_x: cim_bwd_gx_wide_kernel, a workgroup per (image, band of input rows, channel chunk) whose ring holds the
+// chunk's (c, kh) rows alone; grad_w: cim_bwd_gw_wide_kernel, a workgroup per (pixel chunk, 16-channel input block,
+// group of kWbOBG output blocks).  The V7 fields mean what they mean in v7_plan.
+constexpr int kWbOBX = 4;  // grad_x: 16-channel output blocks whose G a wave holds at a time
+constexpr int kWbOBG = 2;  // grad_w: output blocks sharing one staging of the activation planes
+struct PlanWB {
+  bool ok;
+  V7 v;
+  WideB w;
+  size_t lds_gx, lds_gw;
+  int pairs;  // grad_w grid y: input blocks x output groups
+};
+
+inline PlanWB wide_bwd_plan_compute(const Geo& g0) {
+  PlanWB p;
+  memset(&p, 0, sizeof(p));
+  if (tune("WIDE_BWD", 1) == 0) return p;
+  // the question is asked of the module's training form, whichever form and option bits the caller holds: the
+  // operands the prologue builds follow the answer, and both forms of a descriptor share them (routes_agree)
+  Geo g = g0;
+  g.onchw = 1;
+  g.wide_bwd = 0;
+  if (g.inference || !wide_plan(g).ok) return p;
+  if (g.mode != ADC_TERNARY || wide_cst(g) == 0) return p;  // the ternary library ADC, w2a2 / w3a3 / w4a4 in 1-bit slices
+  if (g.KH != 3 || g.KW != 3 || g.SH != 1 || g.SW != 1 || g.PH != 1 || g.PW != 1) return p;
+  if ((g.W & (g.W - 1)) != 0 || (g.Wo & (g.Wo - 1)) != 0 || g.Wo % 8 != 0 || g.M % 128 != 0) return p;
+  if (g.Wo > 32) return p;  // (64 wide -- one row a step, four ring segments -- is served by no test: refused)
+  if (g.OB16 % 2 != 0) return p;  // the wcy operand's K-steps hold two output blocks of one weight slice
+  V7& v = p.v;
+  if (g.P % 128 == 0) v.whole = 0;
+  else if (128 % g.P == 0) v.whole = 1;
+  else return p;
+  v.lw = 0;
+  while ((1 << v.lw) < g.Wo) ++v.lw;
+  v.lwin = 0;
+  while ((1 << v.lwin) < g.W) ++v.lwin;
+  v.lcin = -1;
+  // grad_x: bands as v7_plan's stride-1 layers, the ring of one channel chunk
+  int rb = 8;
+  while (rb > 1 && (long long)g.B * cdiv(g.H, rb) < 256) rb /= 2;
+  v.RB = std::min(g.H, tune("WGX_RB", rb));
+  v.nbands = (g.H + v.RB - 1) / v.RB;
+  v.FBX = g.FBT;
+  v.NCPBT = 0;
+  for (int i = 0; i < g.T; ++i) {
+    const int cplo = (i * g.xbar) / 3, cphi = (std::min(g.K, (i + 1) * g.xbar) - 1) / 3;
+    v.NCPBT = std::max(v.NCPBT, (cphi >> 2) - (cplo >> 2) + 1);
+  }
+  if (v.NCPBT > 12) return p;  // (CtxLayout::wcy holds 12 blocks a tile)
+  v.SWD = std::min(16, g.Wo);
+  v.NSEG = g.Wo / v.SWD;
+  v.NRS = 64 / g.Wo;
+  v.RSLOT = v.NRS + 2;
+  v.NPART = 1;
+  // the chunk: the most channels (a multiple of 4, so that no (c, kh) block of four straddles two chunks) whose ring
+  // leaves two workgroups a CU, then the chunks evened out
+  const size_t per_c = (size_t)v.RSLOT * v.NSEG * 3 * (v.SWD + 2) * 4;
+  const int cmax = (int)(((size_t)tune("WGX_LDS_KB", 80) * 1024 - 512 - 512) / per_c) & ~3;
+  if (cmax < 4) return p;
+  p.w.ncc = cdiv(g.C, cmax);
+  p.w.cch = (cdiv(g.C, p.w.ncc) + 3) & ~3;
+  p.w.ncc = cdiv(g.C, p.w.cch);
+  p.lds_gx = a16((size_t)p.w.cch * per_c) + 64 * 4 + 64 * 4;
+  // one act-LSQ partial per workgroup, in the region every route has (WsLayout::lsq_part)
+  if ((long long)g.B * v.nbands * p.w.ncc > std::max(kLsqParts, g.B * g.H)) return p;
+  // grad_w: v7_plan's stages and planes
+  v.NSLOT = v.whole ? (128 / g.P) * g.H : (128 / g.Wo) - 1 + g.KH;
+  v.CPL = 16;
+  gw_pitches(g, v);
+  v.NTL = 1;
+  for (int cb = 0; cb * 16 < g.C; ++cb) {
+    const int ilo = (cb * 16 * g.KHW) / g.xbar, ihi = (std::min(g.C, cb * 16 + 16) * g.KHW - 1) / g.xbar;
+    v.NTL = std::max(v.NTL, ihi - ilo + 1);
+  }
+  if (v.NTL > 3) return p;
+  if (v.CPL * v.NSLOT * (g.Wo / 8) > 512) return p;  // staging: <= 2 items per thread
+  const size_t planes = (size_t)g.nba * g.KW * v.KWP * 2;
+  p.lds_gw = std::max(a16(planes), (size_t)4 * 9 * 256 * 4) + 64 * 4 +
+             (size_t)kWbOBG * 4 * v.NTL * g.nbw * g.nba * 16 * 4;
+  p.pairs = (g.C / 16) * cdiv(g.OB16, kWbOBG);
+  // pixel chunks (slabs): never more than the general backward's, whose count sized the workspace
+  int gen_rows, gen_chunks;
+  gw_chunks(g, &gen_rows, &gen_chunks);
+  const int stages = g.M / 128;
+  const int want = std::min({std::max(1, tune("WGW_BLOCKS", 512) / p.pairs), gen_chunks, stages});
+  v.nstage = cdiv(stages, want);
+  v.nchunks = cdiv(stages, v.nstage);
+  const size_t lim = kLdsMax - 512;
+  p.ok = p.lds_gx <= lim && p.lds_gw <= lim;
+  return p;
+}
+inline PlanWB wide_bwd_plan(const Geo& g) { return memo_geo<PlanWB, wide_bwd_plan_compute>(g); }
+// the (c, kh)-row blocks per tile of the wcy operand the prologue builds: the v7 plan's, or the wide backward's
+inline int wcy_blocks(const Geo& g) {
+  const Plan7 p7 = v7_plan(g);
+  return p7.ok ? p7.v.NCPBT : wide_bwd_plan(g).ok ? wide_bwd_plan(g).v.NCPBT : 1;
+}
+
 // the shift ADC's statistics kernel (cimq_part_shift.hip) applies: interleaved 3-bit state words of
 // w2a2 / w3a3 on a v7 shape (other shift layers take the general backward)
 inline bool shift_stats_ok(const Geo& g) {
@@ -1002,6 +1103,7 @@ inline Route route_compute(const Geo& g) {
   // (a wide layer's forward-only call quantises in its row staging too; its training call keeps the prologue's
   // pass, whose backward words the general backward reads)
   const bool wide = wide_plan(g).ok;
+  const bool wb = g.wide_bwd && !g.inference && wide_bwd_plan(g).ok;  // (asked of the module form, either form here)
   r.actq = (fwd_actq_ok(g) && (g.onchw || g.inference)) || (wide && g.inference);
   r.fwd = v3_plan(g).ok ? ((g.onchw && r.actq && f5_plan(g).ok) ? CIMQ_ROUTE_FWD5 : CIMQ_ROUTE_V3)
         : dense         ? CIMQ_ROUTE_DENSE
@@ -1039,6 +1141,15 @@ inline Route route_compute(const Geo& g) {
     r.lsq_fused = raw && dense_lsq_parts(g) > 0;
     if (r.lsq_fused) r.act_parts = dense_lsq_parts(g);
     r.nchunks_bwd = cdiv(g.M, dense_rows_per_chunk(g));
+  } else if (wb && g.onchw) {
+    // the caller's choice (CIMQ_OPT_WIDE_BWD) on a wide layer its plan takes: compact state words, grad_x with the
+    // act-LSQ backward fused (a partial per workgroup), grad_w a launch of its own
+    const PlanWB pb = wide_bwd_plan(g);
+    r.gx = r.gw = CIMQ_ROUTE_WIDE_BWD;
+    r.lsq_fused = raw;
+    r.act_parts = g.B * pb.v.nbands * pb.w.ncc;
+    r.nchunks_bwd = pb.v.nchunks;  // (<= nchunks: wide_bwd_plan)
+    r.gw_own = true;
   } else {
     r.gx = r.gw = CIMQ_ROUTE_GENERAL;
     r.nchunks_bwd = nchunks;
@@ -1052,7 +1163,7 @@ inline Route route_compute(const Geo& g) {
                      : g.NBP == 8            ? ST_PLANES
                      : g.nbw == 4            ? ST_V7X2
                                              : ST_V7;
-  r.state = r.gx == CIMQ_ROUTE_R6 ? ST_NONE : fam;
+  r.state = r.gx == CIMQ_ROUTE_R6 ? ST_NONE : r.gx == CIMQ_ROUTE_WIDE_BWD ? (g.nbw == 4 ? ST_V7X2 : ST_V7) : fam;
   r.cst = (fam == ST_V7 || fam == ST_V7X2) ? g.nbw : (fam == ST_PLANES || fam == ST_C1) ? 8 : 0;
   r.fst = fam == ST_C1 ? FwdState::RECOMPUTE : FwdState::WRITE;
   // (the region holds any format of the shape: the v7 words are never larger than the per-k ones for nbw >= 2 --
@@ -1064,8 +1175,10 @@ inline Route route_compute(const Geo& g) {
   // ctx codes: the forward is cim_fwd5_kernel (it quantises the activation itself) and grad_w is
   // cim_bwd_gw5_kernel, the ctx's only reader
   r.codes = r.fwd == CIMQ_ROUTE_FWD5 && r.gw == CIMQ_ROUTE_GW5;
-  r.wgx = !v7b;  // the general / dense grad_x operand
-  r.wcy = v7b;   // the v8 grad_x operand (cim_bwd_gx_v8_kernel, the fused and first-conv kernels)
+  r.wgx = !v7b;      // the general / dense grad_x operand
+  r.wcy = v7b || wb;  // the v8 grad_x operand (cim_bwd_gx_v8_kernel, the fused and first-conv kernels), which
+                      // cim_bwd_gx_wide_kernel reads too: under CIMQ_OPT_WIDE_BWD both forms of the descriptor build
+                      // both operands, into regions every layout has (routes_agree)
   r.wg5 = x5_plan(g).ok;
   r.wx6 = r6_plan(g).ok;
   if (g.inference) {
@@ -1238,7 +1351,8 @@ inline WsLayout ws_layout_compute(const Geo& g) {
   // (a w4a4 layer on the v7 pair keeps the region, unused: cimq_query_sizes answered one size for the forward and
   // the backward workspace of such a descriptor before the v7 pair took it, and callers that sized their buffers
   // from that answer -- the forward's among them -- find it unchanged)
-  W.gxu = o; o = align256(o + ((r.gx != CIMQ_ROUTE_GENERAL && !(r.gx == CIMQ_ROUTE_V7 && v7_w44(g))) ? 0 : sizeof(float) * (size_t)g.M * g.K));
+  // (and a wide layer on the compact-state backward, CIMQ_OPT_WIDE_BWD: the option moves no size)
+  W.gxu = o; o = align256(o + ((r.gx != CIMQ_ROUTE_GENERAL && r.gx != CIMQ_ROUTE_WIDE_BWD && !(r.gx == CIMQ_ROUTE_V7 && v7_w44(g))) ? 0 : sizeof(float) * (size_t)g.M * g.K));
   W.total = o;
   return W;
 }
@@ -1264,7 +1378,9 @@ inline bool routes_agree(const Geo& g) {
   const size_t wc[] = {w1.gw_slab, w1.ga_slab, w1.gb_slab, w1.ss_slab, w1.qtab, w1.lsq_part, w1.gaq, w1.gapart, w1.wpart,
                        w1.bpo, w1.gxu, w1.total};
   return std::equal(std::begin(ca), std::end(ca), cc) && c.total <= a.total &&
-         std::equal(std::begin(wa), std::end(wa), wc) && (r1.state == r0.state || r1.state == ST_NONE) &&
+         std::equal(std::begin(wa), std::end(wa), wc) &&
+         // (the wide backward's compact words live in the region the Function form's per-k words size)
+         (r1.state == r0.state || r1.state == ST_NONE || r1.gx == CIMQ_ROUTE_WIDE_BWD) &&
          r0.wgx == r1.wgx && r0.wcy == r1.wcy && r0.wg5 == r1.wg5 && r0.wx6 == r1.wx6;
 }
 
@@ -1382,6 +1498,12 @@ int launch_fwd8_staged(const Geo& g, uint8_t* ctx, const float* sw, const float*
 // pool: the 2x2 max-pooled store of an epilogue call (wide_pool_ok), out [B, O, Ho/2, Wo/2]
 int launch_wide(const Geo& g, const PlanW& p, uint8_t* ctx, const float* sw, const float* sa, float* out,
                 hipStream_t s, const ActQ* aq, const Epi* ep = nullptr, bool pool = false);
+// cimq_part_wide_bwd.hip: the wide layers' state-writing training forward, cim_fwd_wide_state_kernel (Route::state
+// ST_V7 / ST_V7X2 on CIMQ_ROUTE_WIDE), and the channel-chunked backward from their words; parts: bit 0 grad_x, bit 1 grad_w
+int launch_wide_state(const Geo& g, const PlanW& p, uint8_t* ctx, const float* sw, const float* sa, float* out,
+                      hipStream_t s);
+int launch_wide_bwd(const Geo& g, const PlanWB& p, const uint8_t* ctx, const float* sw, const float* sa,
+                    const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, int parts);
 // cimq_part_fwd5.hip: the w3a3 module forward on the slice-planar patch (f5_plan)
 int launch_fwd5(const Geo& g, const Plan5& p, uint8_t* ctx, const float* sw, const float* sa, float* out,
                 hipStream_t s, const ActQ* aq, const Epi* ep = nullptr);

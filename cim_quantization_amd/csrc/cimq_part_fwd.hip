@@ -152,6 +152,10 @@ int launch_fwd_any(const Geo& g, uint8_t* ctx, const float* sw, const float* sa,
   if (ep && (ps_dbg || !g.inference)) return fail(CIMQ_EINVAL, "internal: output epilogue off the forward-only path");
   if (r.fwd == CIMQ_ROUTE_WIDE) {
     if (ps_dbg) return fail(CIMQ_EINVAL, "internal: the debug hook on the wide forward");
+    if (r.state == ST_V7 || r.state == ST_V7X2) {  // a training call on the compact-state backward (CIMQ_OPT_WIDE_BWD)
+      if (aq || ep) return fail(CIMQ_EINVAL, "internal: the wide state forward off the training call");
+      return launch_wide_state(g, wide_plan(g), ctx, sw, sa, out, s);
+    }
     return launch_wide(g, wide_plan(g), ctx, sw, sa, out, s, aq, ep);
   }
   if (r.fwd == CIMQ_ROUTE_DENSE) {

@@ -38,7 +38,8 @@ struct Geo {
   // host side, cimq_conv_desc.options (two halves of what was one int, so that the struct every kernel takes by
   // value keeps its size and its offsets): CIMQ_OPT_RECOMPUTE -- the module backward recomputes partial sums --
   // and CIMQ_OPT_INFERENCE -- forward only, nothing written that a backward would read
-  short recompute, inference;
+  signed char recompute, wide_bwd;  // (wide_bwd: CIMQ_OPT_WIDE_BWD, in what was recompute's upper byte)
+  short inference;
   uint32_t seed_lo, seed_hi;  // VAR_STOCHASTIC: Philox key
   const unsigned char* wbase;  // host side: the weight-side ctx regions (cimq_lsq_desc.wprep); null: inside ctx
 };
@@ -329,6 +330,11 @@ struct WideP {
   int ncx;  // channels the LDS patch holds: the widest chunk's span
   int nch;  // channel chunks: ceil(T / tr)
   int pf;   // compile-time slice counts: the next tile's weight fragments prefetched in registers
+};
+// ... of the wide layers' compact-state backward (cimq_wide_bwd.hip; wide_bwd_plan) beside its V7
+struct WideB {
+  int cch;  // grad_x: input channels per chunk (a multiple of 4; the last chunk may hold fewer)
+  int ncc;  // grad_x: channel chunks
 };
 constexpr int kWideOBM = 4;  // 16-channel output blocks per workgroup (tables sized for four, zero past the last)
 

@@ -520,17 +520,30 @@ def _take_wprep(wprep, desc, lsq, x_shape, params, stochastic):
     return wprep.buf
 
 
+_TRAIN_OPTS = _lib.CIMQ_OPT_RECOMPUTE | _lib.CIMQ_OPT_WIDE_BWD
+
+
+def _train_options(recompute, wide_backward=False):
+    """cimq_conv_desc.options of a training call, in the library's own values: ``recompute`` is a bool (True is
+    CIMQ_OPT_RECOMPUTE, 1) or such an options word already; ``wide_backward`` adds CIMQ_OPT_WIDE_BWD.  _CimModuleConv
+    keeps its pinned argument list, so cim_module_conv hands it this word where it took the recompute bool."""
+    return (int(recompute) & _TRAIN_OPTS) | (_lib.CIMQ_OPT_WIDE_BWD if wide_backward else 0)
+
+
 def _module_descs(x_shape, weight, stride, padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits,
-                  xbar, nbits_alpha, has_alpha, stochastic, recompute=False, inference=False):
+                  xbar, nbits_alpha, has_alpha, stochastic, recompute=False, inference=False, wide_backward=False):
     B, C, H, W = x_shape
     O, _, KH, KW = weight.shape
+    opts = _train_options(recompute, wide_backward)
+    if inference:
+        opts &= ~_lib.CIMQ_OPT_WIDE_BWD  # (no effect forward only: one descriptor, one prepared weight side)
     qp_a = float(2 ** nbits_a - 1)
     qn_w, qp_w = -(2 ** (nbits_w - 1)), 2 ** (nbits_w - 1) - 1
     desc = _lib.make_desc(B, C, H, W, O, KH, KW, _pair(stride), _pair(padding), xbar, nbits_w, nbits_a, wbitslice,
                           abitslice, adcbits, _lib.CIMQ_INPUT_RAW_LSQ, qp_a,
                           _lib.CIMQ_ADC_STOCHASTIC if stochastic else _lib.CIMQ_ADC_LIBRARY,
                           stochastic_seed() if stochastic else 0,
-                          (_lib.CIMQ_OPT_RECOMPUTE if recompute else 0) | (_lib.CIMQ_OPT_INFERENCE if inference else 0))
+                          opts | (_lib.CIMQ_OPT_INFERENCE if inference else 0))
     lsq = _lib.make_lsq_desc(qn_w, qp_w, 1.0 / math.sqrt(B * C * H * W * qp_a),
                              1.0 / math.sqrt(weight.numel() * qp_w), nbits_alpha if has_alpha else 0)
     return desc, lsq
@@ -544,16 +557,17 @@ def _shift_module_descs(x_shape, weight, stride, padding, dilation, nbits_a, abi
     return desc, lsq
 
 
-def _layer_descs(x_shape, weight, cfg, has_alpha, shift, stochastic=False, recompute=False, inference=False):
+def _layer_descs(x_shape, weight, cfg, has_alpha, shift, stochastic=False, recompute=False, inference=False,
+                 wide_backward=False):
     """The descriptor pair of one module-entry-point call.  ``cfg``: (stride, padding, dilation, nbits_a, abitslice,
     nbits_w, wbitslice, adcbits, xbar, nbits_alpha), Conv2dLSQCiM.layer_config's order; ``shift``: the fused shift
-    path's pair (adc 1.5, never stochastic, no recompute form)."""
+    path's pair (adc 1.5, never stochastic, no recompute form); ``wide_backward``: CIMQ_OPT_WIDE_BWD."""
     if shift:
         desc, lsq = _shift_module_descs(x_shape, weight, *cfg[:7], *cfg[8:])
         if inference:
             desc.options |= _lib.CIMQ_OPT_INFERENCE
         return desc, lsq
-    return _module_descs(x_shape, weight, *cfg, has_alpha, stochastic, recompute, inference)
+    return _module_descs(x_shape, weight, *cfg, has_alpha, stochastic, recompute, inference, wide_backward)
 
 
 def module_descs(m, x_shape, inference=False):
@@ -562,7 +576,7 @@ def module_descs(m, x_shape, inference=False):
     (``m.adc_shift``): the fused shift path's pair.  Never the stochastic form, which would draw a seed."""
     return _layer_descs(x_shape, m.weight, m.layer_config(), m.alpha_cim is not None,
                         bool(getattr(m, "adc_shift", False)), False, bool(getattr(m, "recompute_psum", False)),
-                        inference)
+                        inference, bool(getattr(m, "wide_backward", False)))
 
 
 _prepare_descs = module_descs  # the name it had while it was private: kept for callers written against it
@@ -659,7 +673,8 @@ class _LayerCall:
 
 
 def _layer_call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_mask, signed_act, cfg,
-                stochastic=False, wprep=None, recompute=False, inference=False, x_codes=False, want_out=True):
+                stochastic=False, wprep=None, recompute=False, inference=False, x_codes=False, want_out=True,
+                wide_backward=False):
     """What cimq_module_forward, cimq_module_shift_forward (``beta_cim`` given), cimq_module_forward_epilogue and
     cimq_module_forward_codes have in common, for a layer of configuration ``cfg`` (_layer_descs).  ``wprep``: a
     WeightPrep, used only if it matches this call; a shift call that can be differentiated never reads one (the
@@ -671,7 +686,7 @@ def _layer_call(x, weight, alpha_act, alpha_weight, alpha_cim, beta_cim, binary_
     shift = beta_cim is not None
     c = _LayerCall()
     c.desc, c.lsq = _layer_descs(tuple(x.shape), weight, (st, pd) + cfg[2:], alpha_cim is not None, shift,
-                                 stochastic, recompute, inference)
+                                 stochastic, recompute, inference, wide_backward)
     c.keep = None
     if inference or not shift:
         c.keep = _take_wprep(wprep, c.desc, c.lsq, x.shape,
@@ -816,21 +831,25 @@ class _CimModuleConv(torch.autograd.Function):
 
 def cim_module_conv(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride, padding,
                     dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar, nbits_alpha,
-                    accumulate=False, stochastic=False, tail_stream=None, wprep=None, recompute=False):
+                    accumulate=False, stochastic=False, tail_stream=None, wprep=None, recompute=False,
+                    wide_backward=False):
     """NCHW output of a Conv2dLSQCiM layer (quantisers fused); differentiable in x, weight and
     the three step-size parameters (alpha_act and alpha_weight are 1-element tensors).
     ``accumulate`` / ``tail_stream``: see _CimModuleConv; ``stochastic``: the stochastic 1.5-bit ADC;
     ``wprep``: a WeightPrep from prepare_weights (used only if it matches this call); ``recompute``:
-    CIMQ_OPT_RECOMPUTE (no state words in the ctx where a recompute backward exists; slower).
+    CIMQ_OPT_RECOMPUTE (no state words in the ctx where a recompute backward exists; slower); ``wide_backward``:
+    CIMQ_OPT_WIDE_BWD (a wide layer trains on the channel-chunked compact-state backward where its plan applies).
     A call nothing can differentiate (inference_call) runs forward only (CIMQ_OPT_INFERENCE): out, the small
     ctx and the forward workspace are allocated, nothing is saved; ``wprep`` then comes from inference_weights."""
+    # (the Function keeps its argument list: the descriptor's options word travels where the recompute bool did)
+    opts = _train_options(recompute, wide_backward)
     if inference_call(x, weight, alpha_act, alpha_weight, alpha_cim):
         return _CimModuleConv._call(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride,
                                     padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar,
-                                    nbits_alpha, stochastic, wprep, recompute, inference=True).out
+                                    nbits_alpha, stochastic, wprep, opts, inference=True).out
     return _CimModuleConv.apply(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, signed_act, stride,
                                 padding, dilation, nbits_a, abitslice, nbits_w, wbitslice, adcbits, xbar,
-                                nbits_alpha, accumulate, stochastic, tail_stream, wprep, recompute)
+                                nbits_alpha, accumulate, stochastic, tail_stream, wprep, opts)
 
 
 def module_shift_supported(x_shape, weight, stride, padding, dilation, nbits_a, abitslice, nbits_w, wbitslice,

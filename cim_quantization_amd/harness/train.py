@@ -56,6 +56,9 @@ def get_base_parser():
     p.add_argument("--adc-shift", action="store_true",
                    help="Conv2dLSQCiM(adc_shift=True): the per-tile scale + shift ADC with a learnable beta_cim "
                         "(adcbits 1 / 1.5; a launcher flag, not a prototxt field: the schema stays the reference's)")
+    p.add_argument("--wide-backward", action="store_true",
+                   help="Conv2dLSQCiM.wide_backward on every CiM conv: the wide layers (3x3 from 128 input channels "
+                        "up) train on the channel-chunked compact-state backward where the library's plan takes them")
     return p
 
 
@@ -267,6 +270,10 @@ def main(argv=None):
         backend = hp.multi_gpu.dist_backend if hp.HasField("multi_gpu") else "nccl"
         dist.init_process_group(backend=backend, init_method="env://", world_size=world, rank=rank)
     model, arch = build_model(hp, device, adc_shift=args.adc_shift)
+    if args.wide_backward:
+        for m in model.modules():
+            if hasattr(m, "wide_backward"):
+                m.wide_backward = True
     batch = hp.batch_size // world if distributed else hp.batch_size
     if distributed:
         model = nn.parallel.DistributedDataParallel(model, device_ids=[local])

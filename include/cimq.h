@@ -88,6 +88,15 @@ extern "C" {
                                 reports CIMQ_ROUTE_NONE for both backward roles.  Every other entry point that takes
                                 a cimq_conv_desc refuses the bit with CIMQ_EINVAL.  CIMQ_OPT_RECOMPUTE may be set
                                 with it and then has no effect.  Since ABI 15 */
+/* (bit value 8 is not an option either) */
+#define CIMQ_OPT_WIDE_BWD 16 /* module entry points, a hint as CIMQ_OPT_RECOMPUTE is: where cimq_module_wide_bwd_plan
+                                accepts the layer (a CIMQ_ROUTE_WIDE training layer: library ternary ADC, w2a2 / w3a3 /
+                                w4a4 in 1-bit slices, 3x3 / stride 1 / pad 1, power-of-two width) the training forward
+                                (cim_fwd_wide_state_kernel) writes compact state words into the ctx's state region and the backward runs
+                                cim_bwd_gx_wide_kernel + cim_bwd_gw_wide_kernel from them (CIMQ_ROUTE_WIDE_BWD for
+                                both roles) instead of the general kernels.  No size moves with the bit, for any
+                                descriptor; everywhere else, and together with CIMQ_OPT_INFERENCE, it changes
+                                nothing.  cimq_wide_bwd_abi() == 1 */
 
 /* cimq_lsq_desc.flags */
 #define CIMQ_LSQ_ACCUMULATE_GRADS 1 /* cimq_module_backward adds the parameter gradients into
@@ -248,8 +257,12 @@ enum {
   CIMQ_ROUTE_R6 = 9,       /* grad_x and grad_w in cim_bwd_r6_kernel from RECOMPUTED partial sums (the forward
                               writes no state words; round 6, ABI 13; only under CIMQ_OPT_RECOMPUTE since ABI 14) */
   CIMQ_ROUTE_NONE = 10,    /* route[1] / route[2] under CIMQ_OPT_INFERENCE: there is no backward.  Since ABI 15 */
-  CIMQ_ROUTE_WIDE = 11     /* forward: cim_fwd_wide_kernel, the channel-chunked forward of 3x3 module layers from 128
-                              input channels up (cimq_wide_abi() == 1); their backward stays CIMQ_ROUTE_GENERAL */
+  CIMQ_ROUTE_WIDE = 11,    /* forward: cim_fwd_wide_kernel, the channel-chunked forward of 3x3 module layers from 128
+                              input channels up (cimq_wide_abi() == 1); their backward stays CIMQ_ROUTE_GENERAL
+                              unless CIMQ_OPT_WIDE_BWD is set */
+  CIMQ_ROUTE_WIDE_BWD = 12 /* grad_x: cim_bwd_gx_wide_kernel / grad_w: cim_bwd_gw_wide_kernel, the channel-chunked
+                              compact-state backward of a CIMQ_ROUTE_WIDE layer under CIMQ_OPT_WIDE_BWD
+                              (cimq_wide_bwd_abi() == 1) */
 };
 int cimq_module_route(const cimq_conv_desc* d, int* route);
 
@@ -283,6 +296,14 @@ int cimq_wide_abi(void);
  * 16-channel blocks (the grid's y), out[3] the crossbar tiles.  Returns 0, CIMQ_EINVAL for a NULL argument, or the
  * status of a descriptor the module entry points refuse. */
 int cimq_module_wide_plan(const cimq_conv_desc* d, int out[4]);
+
+/* 1 where CIMQ_OPT_WIDE_BWD and CIMQ_ROUTE_WIDE_BWD exist.  CIMQ_ABI_VERSION / _MINOR and the other availability
+ * numbers are unchanged: no struct, call or size moved. */
+int cimq_wide_bwd_abi(void);
+/* The plan of that backward for `d` (the option bit need not be set: the question is whether it would take the
+ * layer), without device work: out[0] 1 where it applies (else 0, and the rest 0), out[1] the channel chunks of the
+ * grad_x grid, out[2] its bands of input rows per image, out[3] the pixel chunks (slabs) of grad_w. */
+int cimq_module_wide_bwd_plan(const cimq_conv_desc* d, int out[4]);
 int cimq_module_shift_forward(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* x, const float* weight,
                               const float* alpha_act, const float* alpha_weight, const float* alpha_cim,
                               const float* beta_cim, const int8_t* binary_mask, const float* signed_act, float* out,
