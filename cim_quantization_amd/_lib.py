@@ -23,11 +23,12 @@ CIMQ_INPUT_XQ = 0
 CIMQ_INPUT_RAW_LSQ = 1
 # cimq_module_route codes (include/cimq.h CIMQ_ROUTE_*)
 ROUTE_NAMES = {0: "general", 1: "v3", 2: "fwd5", 3: "v7", 4: "fused", 5: "c1", 6: "gx5", 7: "gw5", 8: "dense", 9: "r6",
-               10: "none", 11: "wide", 12: "wide_bwd"}
+               10: "none", 11: "wide", 12: "wide_bwd", 13: "c1w"}
 CIMQ_ROUTE_R6 = 9
 CIMQ_ROUTE_NONE = 10  # route[1] / route[2] under CIMQ_OPT_INFERENCE (ABI 15)
 CIMQ_ROUTE_WIDE = 11  # route[0]: cim_fwd_wide_kernel (cimq_wide_abi() == 1)
 CIMQ_ROUTE_WIDE_BWD = 12  # route[1] / route[2] of such a layer under CIMQ_OPT_WIDE_BWD (cimq_wide_bwd_abi() == 1)
+CIMQ_ROUTE_C1W = 13  # route[1] / route[2] of a w8a8 first conv of 32 .. 512 channels under the bit (cimq_c1w_abi() == 1)
 CIMQ_LSQ_ACCUMULATE_GRADS = 1
 CIMQ_LSQ_SKIP_TAIL = 2
 CIMQ_LSQ_DEFER_GW = 4
@@ -39,7 +40,9 @@ CIMQ_ADC_SHIFT_SIGN = 3
 CIMQ_ADC_F_PS_INT8 = 0x100
 CIMQ_ADC_F_SHIFT_RANGE = 0x200
 CIMQ_OPT_RECOMPUTE = 1  # cimq_conv_desc.options (ABI 14)
-CIMQ_OPT_WIDE_BWD = 16  # a wide layer trains on the compact-state backward where its plan applies (bit 8 is refused)
+# a wide layer trains on the compact-state backward, a w8a8 first conv of 32 .. 512 output channels on the multi-block
+# recompute backward, where the layer's plan applies (bit 8 is refused)
+CIMQ_OPT_WIDE_BWD = 16
 CIMQ_OPT_INFERENCE = 4  # forward only: nothing written that a backward would read (ABI 15; bit 2 is refused)
 CIMQ_EPI_RELU = 1  # cimq_epilogue.flags (ABI 16)
 CIMQ_CODES_NO_FLOAT = 1  # cimq_act_codes.flags (ABI 16, minor 1)
@@ -72,6 +75,8 @@ EXPORTED_SYMBOLS = (
     "cimq_module_wide_plan",
     "cimq_wide_bwd_abi",
     "cimq_module_wide_bwd_plan",
+    "cimq_c1w_abi",
+    "cimq_module_c1w_plan",
     "cimq_module_shift_forward",
     "cimq_module_shift_backward",
     "cimq_module_forward_epilogue",
@@ -321,6 +326,11 @@ def _bind(lib):
         lib.cimq_wide_bwd_abi.argtypes = []
         lib.cimq_module_wide_bwd_plan.restype = ctypes.c_int
         lib.cimq_module_wide_bwd_plan.argtypes = [ctypes.POINTER(ConvDesc), ctypes.POINTER(ctypes.c_int)]
+    if hasattr(lib, "cimq_c1w_abi"):
+        lib.cimq_c1w_abi.restype = ctypes.c_int
+        lib.cimq_c1w_abi.argtypes = []
+        lib.cimq_module_c1w_plan.restype = ctypes.c_int
+        lib.cimq_module_c1w_plan.argtypes = [ctypes.POINTER(ConvDesc)] + [ctypes.POINTER(ctypes.c_int)] * 4
     if hasattr(lib, "cimq_pool_abi"):
         lib.cimq_pool_abi.restype = ctypes.c_int
         lib.cimq_pool_abi.argtypes = []
@@ -506,6 +516,14 @@ def module_wide_bwd_plan(desc: ConvDesc):
     f = (ctypes.c_int * 4)()
     check(load().cimq_module_wide_bwd_plan(ctypes.byref(desc), f), "cimq_module_wide_bwd_plan")
     return tuple(f)
+
+
+def module_c1w_plan(desc: ConvDesc):
+    """(ok, workgroups per image, output blocks per workgroup, 128-pixel steps per image) of the wide first conv's
+    recompute backward for ``desc`` -- cimq_module_c1w_plan (cimq_c1w_abi() == 1); the option bit need not be set."""
+    f = [ctypes.c_int() for _ in range(4)]
+    check(load().cimq_module_c1w_plan(ctypes.byref(desc), *[ctypes.byref(v) for v in f]), "cimq_module_c1w_plan")
+    return tuple(v.value for v in f)
 
 
 def pool_abi() -> int:

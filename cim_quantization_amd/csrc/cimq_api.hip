@@ -91,6 +91,7 @@ int dispatch_bwd_any(const Geo& g, const uint8_t* ctx, const float* sw, const fl
       if (g.nbw == 4) return launch_v7_n<4, 4>(g, v7_plan(g), ctx, sw, sa, gout, x, gx, ws, s, parts);
       return launch_v7_n<3, 3>(g, v7_plan(g), ctx, sw, sa, gout, x, gx, ws, s, parts);
     case CIMQ_ROUTE_WIDE_BWD: return launch_wide_bwd(g, wide_bwd_plan(g), ctx, sw, sa, gout, x, gx, ws, s, parts);
+    case CIMQ_ROUTE_C1W: return launch_c1w(g, c1w_plan(g), ctx, sw, sa, gout, x, gx, ws, s);
     case CIMQ_ROUTE_DENSE: return launch_dense_bwd(g, ctx, sw, gout, gx, ws, s, r.lsq_fused ? x : nullptr, sa);
     case CIMQ_ROUTE_GENERAL: return launch_bwd_general(g, ctx, sw, sa, signed_act, gout, x, gx, ws, s);
     default: return fail(CIMQ_EINVAL, "internal: a forward-only descriptor has no backward");
@@ -798,6 +799,21 @@ int cimq_module_wide_bwd_plan(const cimq_conv_desc* d, int out[4]) {
   return CIMQ_OK;
 }
 
+int cimq_c1w_abi(void) { return 1; }
+
+int cimq_module_c1w_plan(const cimq_conv_desc* d, int* ok, int* groups, int* blocks_per_group, int* steps) {
+  Geo g;
+  CIMQ_TRY(make_geo(d, &g));
+  if (!ok || !groups || !blocks_per_group || !steps) return fail(CIMQ_EINVAL, "null out");
+  if (g.input_kind != CIMQ_INPUT_RAW_LSQ) return fail(CIMQ_EINVAL, "module entry points take the raw activation");
+  const PlanC1W p = c1w_plan(module_form(g));
+  *ok = p.ok ? 1 : 0;
+  *groups = p.ok ? p.v.groups : 0;
+  *blocks_per_group = p.ok ? p.v.obg : 0;
+  *steps = p.ok ? p.v.c.nsteps : 0;
+  return CIMQ_OK;
+}
+
 int cimq_module_forward_form(const cimq_conv_desc* d, int form[2]) {
   Geo g;
   CIMQ_TRY(make_geo(d, &g));
@@ -1258,8 +1274,9 @@ static int module_backward_impl(const cimq_conv_desc* d, const cimq_lsq_desc* q,
   const float* sw = scal + 1;
   const float* gsrc = grad_out;
   // the general backward reads [B, P, O] grad_out, also behind the fast forward (a v3 layer off the v7 plan, e.g.
-  // w4a4); the fast kernels read NCHW (g.onchw), and the dense path's P = 1
-  if (r.gx == CIMQ_ROUTE_GENERAL) {
+  // w4a4); the fast kernels read NCHW (g.onchw), and the dense path's P = 1.  (cim_bwd_c1w_kernel behind the general
+  // forward -- 256 % O != 0 -- reads [B, P, O] as well: it follows g.onchw)
+  if (r.gx == CIMQ_ROUTE_GENERAL || (r.gx == CIMQ_ROUTE_C1W && !g.onchw)) {
     float* bpo = reinterpret_cast<float*>(w + ws_layout(g).bpo);
     hipLaunchKernelGGL(nchw_to_bpo_kernel, dim3(std::min(cdiv((long long)g.M * g.O, 256), 8192)), dim3(256), 0, s,
                        g, grad_out, bpo);

@@ -589,6 +589,78 @@ inline PlanC1 c1_plan(const Geo& g) {
   return p;
 }
 
+// ---- the first conv's backward beyond 16 output channels (cimq_c1w.hip; CIMQ_OPT_WIDE_BWD) ----
+// c1_plan's conditions with O = 16 n, 2 <= n <= 32, and none of v7_plan's (which fails for these layers).  A
+// workgroup per (image, group of obg output blocks); several groups leave grad_x partials in the workspace's
+// unfolded-grad_x region (M * K floats = 9 partials of C * M) for c1w_fold_kernel.
+constexpr int kC1wOBG = 4;     // output blocks a workgroup walks (more only where 9 groups would not cover O)
+constexpr int kC1wGroups = 9;  // K / C: the group partials the region holds
+struct PlanC1W {
+  bool ok;
+  VC1W v;
+};
+
+inline PlanC1W c1w_plan_compute(const Geo& g0) {
+  PlanC1W p;
+  memset(&p, 0, sizeof(p));
+  if (tune("C1W", 1) == 0) return p;
+  // one answer for both forms and any option bits of a descriptor: the operands the prologue builds follow it, and
+  // the forms share them (routes_agree).  The forward is whichever the layer has (cim_fwd_v3_kernel where 256 % O == 0,
+  // else the general kernel): the backward reads the ctx's slice words and weight fragments, which both leave alike
+  Geo g = g0;
+  g.onchw = 1;
+  g.wide_bwd = 0;
+  if (g.inference || g.variant != VAR_LIBRARY || g.input_kind != CIMQ_INPUT_RAW_LSQ) return p;
+  if (g.NBP != 8 || g.nbw != 8 || g.nba != 8 || g.bsw != 1 || g.bsa != 1 || g.K > 32) return p;
+  if (g.O % 16 != 0 || g.O < 32 || g.O > 512) return p;
+  if (g.SH != 1 || g.SW != 1 || g.KH != 3 || g.KW != 3 || g.PH != 1 || g.PW != 1 || g.T != 1) return p;
+  if (g.W < 8 || g.W > 64 || (g.W & (g.W - 1)) != 0 || g.Wo != g.W || g.Ho != g.H) return p;
+  // a grad_w / grad_alpha slab per image, in the slabs the general backward's chunk count sized: a batch beyond
+  // that count is refused (the workspace keeps its size, CIMQ_LSQ_SKIP_TAIL / _DEFER_GW and the chained backward
+  // find the slabs where the tail reads them)
+  int gen_rows, gen_chunks;
+  gw_chunks(g, &gen_rows, &gen_chunks);
+  if (g.B > gen_chunks) return p;
+  VC1& v = p.v.c;
+  v.lw = 0;
+  while ((1 << v.lw) < g.W) ++v.lw;
+  v.R = 128 / g.W;
+  if (g.H % v.R != 0) return p;
+  v.nsteps = g.H / v.R;
+  v.RH = (v.R - 1) + 3;
+  v.WP = g.W + 2;
+  v.SWD = std::min(16, g.W);
+  v.NSEG = g.W / v.SWD;
+  v.RSLOT = v.nsteps == 1 ? g.H : v.R + 2;
+  v.NCPBT = ((g.K - 1) / 3 >> 2) + 1;  // (c, kh)-blocks of 4 (one tile): at most 3
+  v.lcin = 0;
+  while ((1 << v.lcin) < g.C) ++v.lcin;
+  if ((1 << v.lcin) != g.C) v.lcin = -1;
+  p.v.obg = std::max(tune("C1W_OBG", kC1wOBG), cdiv(g.OB16, kC1wGroups));
+  p.v.groups = cdiv(g.OB16, p.v.obg);
+  size_t o = 0;
+  const size_t patch = a16((size_t)g.C * v.RH * v.WP * 8);
+  v.o_xp = (unsigned)o; o += patch;
+  v.o_hp = (unsigned)o; o += patch;
+  v.o_ptab = (unsigned)o; o += 64 * 4;
+  v.o_prm = (unsigned)o; o += 64 * 16 * 16;
+  v.o_cel = (unsigned)o; o += a16(3 * 64 * 4);
+  v.o_g = (unsigned)o; o += 16 * 132 * 4;
+  v.o_ring = (unsigned)o; o += a16((size_t)v.RSLOT * v.NSEG * 3 * g.C * (v.SWD + 2) * 4);
+  v.o_gal = (unsigned)o; o += 8 * 64 * 16 * 4;
+  v.o_red = (unsigned)o; o += a16((2 * 16 * 16 + 8) * 4);
+  v.o_e = (unsigned)o; o += 8 * 2 * 256 * 4;
+  v.o_wk = (unsigned)o; o += 8 * 64 * 16;
+  v.o_wc = (unsigned)o; o += (size_t)3 * 4 * 64 * 16;
+  v.lds = (unsigned)o;
+  // the kernel's one-step-ahead staging: at most three 16-byte items per thread of 512
+  if (2 * g.C * v.RH * (g.W / 2) + 512 > 3 * 512 || v.NCPBT > 3) return p;
+  // (c1w_fold_kernel's LDS is 16 static bytes)
+  p.ok = p.v.obg >= 1 && p.v.groups <= kC1wGroups && o <= kLdsMax - 512;
+  return p;
+}
+inline PlanC1W c1w_plan(const Geo& g) { return memo_geo<PlanC1W, c1w_plan_compute>(g); }
+
 // ---- the dense path (cimq_part_dense.hip): 1x1 kernels on 1x1 images, a [B][C] x [C][O] GEMM ----
 // (BASELINE cfg5, QuantLinear as Conv2dLSQCiM(k=1) on [B, C, 1, 1]); the library ternary ADC, equal
 // weight / activation slice counts up to 4 (the uint2 state word holds 16 slice pairs per plane)
@@ -794,10 +866,11 @@ inline PlanWB wide_bwd_plan_compute(const Geo& g0) {
   return p;
 }
 inline PlanWB wide_bwd_plan(const Geo& g) { return memo_geo<PlanWB, wide_bwd_plan_compute>(g); }
-// the (c, kh)-row blocks per tile of the wcy operand the prologue builds: the v7 plan's, or the wide backward's
+// the (c, kh)-row blocks per tile of the wcy operand the prologue builds: the v7 plan's, the wide backward's, or the
+// wide first conv's
 inline int wcy_blocks(const Geo& g) {
   const Plan7 p7 = v7_plan(g);
-  return p7.ok ? p7.v.NCPBT : wide_bwd_plan(g).ok ? wide_bwd_plan(g).v.NCPBT : 1;
+  return p7.ok ? p7.v.NCPBT : wide_bwd_plan(g).ok ? wide_bwd_plan(g).v.NCPBT : c1w_plan(g).ok ? c1w_plan(g).v.c.NCPBT : 1;
 }
 
 // the shift ADC's statistics kernel (cimq_part_shift.hip) applies: interleaved 3-bit state words of
@@ -1104,6 +1177,7 @@ inline Route route_compute(const Geo& g) {
   // pass, whose backward words the general backward reads)
   const bool wide = wide_plan(g).ok;
   const bool wb = g.wide_bwd && !g.inference && wide_bwd_plan(g).ok;  // (asked of the module form, either form here)
+  const bool c1w = g.wide_bwd && !g.inference && !v7b && c1w_plan(g).ok;  // (likewise; the wide first conv)
   r.actq = (fwd_actq_ok(g) && (g.onchw || g.inference)) || (wide && g.inference);
   r.fwd = v3_plan(g).ok ? ((g.onchw && r.actq && f5_plan(g).ok) ? CIMQ_ROUTE_FWD5 : CIMQ_ROUTE_V3)
         : dense         ? CIMQ_ROUTE_DENSE
@@ -1150,6 +1224,13 @@ inline Route route_compute(const Geo& g) {
     r.act_parts = g.B * pb.v.nbands * pb.w.ncc;
     r.nchunks_bwd = pb.v.nchunks;  // (<= nchunks: wide_bwd_plan)
     r.gw_own = true;
+  } else if (c1w) {
+    // the same choice on a w8a8 first conv of 32 .. 512 output channels (c1w_plan): one recompute kernel per
+    // (image, output-block group) with the act-LSQ backward fused, a slab and a partial per image as on c1; like c1
+    // it reads grad_out in either layout (g.onchw)
+    r.gx = r.gw = CIMQ_ROUTE_C1W;
+    r.lsq_fused = raw;
+    r.nchunks_bwd = r.act_parts = g.B;  // (<= nchunks: c1w_plan)
   } else {
     r.gx = r.gw = CIMQ_ROUTE_GENERAL;
     r.nchunks_bwd = nchunks;
@@ -1176,7 +1257,7 @@ inline Route route_compute(const Geo& g) {
   // cim_bwd_gw5_kernel, the ctx's only reader
   r.codes = r.fwd == CIMQ_ROUTE_FWD5 && r.gw == CIMQ_ROUTE_GW5;
   r.wgx = !v7b;      // the general / dense grad_x operand
-  r.wcy = v7b || wb;  // the v8 grad_x operand (cim_bwd_gx_v8_kernel, the fused and first-conv kernels), which
+  r.wcy = v7b || wb || c1w;  // the v8 grad_x operand (cim_bwd_gx_v8_kernel, the fused and first-conv kernels), which
                       // cim_bwd_gx_wide_kernel reads too: under CIMQ_OPT_WIDE_BWD both forms of the descriptor build
                       // both operands, into regions every layout has (routes_agree)
   r.wg5 = x5_plan(g).ok;
@@ -1351,8 +1432,9 @@ inline WsLayout ws_layout_compute(const Geo& g) {
   // (a w4a4 layer on the v7 pair keeps the region, unused: cimq_query_sizes answered one size for the forward and
   // the backward workspace of such a descriptor before the v7 pair took it, and callers that sized their buffers
   // from that answer -- the forward's among them -- find it unchanged)
-  // (and a wide layer on the compact-state backward, CIMQ_OPT_WIDE_BWD: the option moves no size)
-  W.gxu = o; o = align256(o + ((r.gx != CIMQ_ROUTE_GENERAL && r.gx != CIMQ_ROUTE_WIDE_BWD && !(r.gx == CIMQ_ROUTE_V7 && v7_w44(g))) ? 0 : sizeof(float) * (size_t)g.M * g.K));
+  // (and a wide layer on the compact-state backward, CIMQ_OPT_WIDE_BWD: the option moves no size; the wide first
+  // conv's kernel, cim_bwd_c1w_kernel, keeps its output-block groups' grad_x partials here)
+  W.gxu = o; o = align256(o + ((r.gx != CIMQ_ROUTE_GENERAL && r.gx != CIMQ_ROUTE_WIDE_BWD && r.gx != CIMQ_ROUTE_C1W && !(r.gx == CIMQ_ROUTE_V7 && v7_w44(g))) ? 0 : sizeof(float) * (size_t)g.M * g.K));
   W.total = o;
   return W;
 }
@@ -1547,6 +1629,9 @@ int launch_fused(const Geo& g, const Plan9& p, const uint8_t* ctx, const float* 
                  const float* x, float* gx, uint8_t* ws, hipStream_t s, bool lsq);
 int launch_c1(const Geo& g, const PlanC1& p, const uint8_t* ctx, const float* sw, const float* sa, const float* gout,
               const float* x, float* gx, uint8_t* ws, hipStream_t s, bool lsq);
+// cimq_part_c1w.hip: the wide first conv's recompute backward (c1w_plan, CIMQ_ROUTE_C1W) and its group fold
+int launch_c1w(const Geo& g, const PlanC1W& p, const uint8_t* ctx, const float* sw, const float* sa, const float* gout,
+               const float* x, float* gx, uint8_t* ws, hipStream_t s);
 // cimq_part_r6.hip: the recompute backward (CIMQ_ROUTE_R6); dbg: the parity hook's state words into st_dbg instead
 int launch_r6(const Geo& g, const PlanR6& p, const uint8_t* ctx, const float* sw, const float* sa, const float* sgn,
               const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, uint32_t* st_dbg = nullptr);

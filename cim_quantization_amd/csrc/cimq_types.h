@@ -200,7 +200,15 @@ struct VC1 {
   unsigned o_xp, o_hp, o_ptab, o_prm, o_cel, o_g, o_ring, o_gal, o_red, o_e, o_wk, o_wc, lds;
 };
 
-constexpr int kF5MaxTc = 8;   // (tile, channel-block) pairs: 2 / 4 / 8 for C = 16 / 32 / 64 at xbar 128
+// ... of its multi-output-block sibling (cimq_c1w.hip; c1w_plan): c1's step geometry and LDS layout, and the split of
+// the 16-channel output blocks over grid y
+struct VC1W {
+  VC1 c;
+  int obg;      // output blocks a workgroup walks
+  int groups;   // workgroups per image: ceil(OB16 / obg), at most 9 (the group partials of grad_x)
+};
+
+constexpr int kF5MaxTc = 8;  // (tile, channel-block) pairs: 2 / 4 / 8 for C = 16 / 32 / 64 at xbar 128
 constexpr int kF5MaxGrp = 4;  // tile groups
 
 // ... of the w3a3 module forward (cimq_fwd5.hip; f5_plan)

@@ -838,7 +838,8 @@ def cim_module_conv(x, weight, alpha_act, alpha_weight, alpha_cim, binary_mask, 
     ``accumulate`` / ``tail_stream``: see _CimModuleConv; ``stochastic``: the stochastic 1.5-bit ADC;
     ``wprep``: a WeightPrep from prepare_weights (used only if it matches this call); ``recompute``:
     CIMQ_OPT_RECOMPUTE (no state words in the ctx where a recompute backward exists; slower); ``wide_backward``:
-    CIMQ_OPT_WIDE_BWD (a wide layer trains on the channel-chunked compact-state backward where its plan applies).
+    CIMQ_OPT_WIDE_BWD (a wide layer trains on the channel-chunked compact-state backward, a w8a8 first conv of 32 ..
+    512 output channels on the multi-block recompute backward, where its plan applies).
     A call nothing can differentiate (inference_call) runs forward only (CIMQ_OPT_INFERENCE): out, the small
     ctx and the forward workspace are allocated, nothing is saved; ``wprep`` then comes from inference_weights."""
     # (the Function keeps its argument list: the descriptor's options word travels where the recompute bool did)

@@ -58,7 +58,8 @@ def get_base_parser():
                         "(adcbits 1 / 1.5; a launcher flag, not a prototxt field: the schema stays the reference's)")
     p.add_argument("--wide-backward", action="store_true",
                    help="Conv2dLSQCiM.wide_backward on every CiM conv: the wide layers (3x3 from 128 input channels "
-                        "up) train on the channel-chunked compact-state backward where the library's plan takes them")
+                        "up) train on the channel-chunked compact-state backward, and a w8a8 first conv of 32 .. 512 "
+                        "output channels on the multi-block recompute backward, where the library's plan takes them")
     return p
 
 

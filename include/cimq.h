@@ -96,7 +96,13 @@ extern "C" {
                                 cim_bwd_gx_wide_kernel + cim_bwd_gw_wide_kernel from them (CIMQ_ROUTE_WIDE_BWD for
                                 both roles) instead of the general kernels.  No size moves with the bit, for any
                                 descriptor; everywhere else, and together with CIMQ_OPT_INFERENCE, it changes
-                                nothing.  cimq_wide_bwd_abi() == 1 */
+                                nothing.  cimq_wide_bwd_abi() == 1.
+                                The same hint on a w8a8 first conv of 32 .. 512 output channels that
+                                cimq_module_c1w_plan accepts (1-bit slices, K <= 32, one crossbar tile, 3x3 / stride 1
+                                / pad 1, a power-of-two width in 8 .. 64, the library ADC, batch within the general
+                                backward's slab count): the backward runs cim_bwd_c1w_kernel (CIMQ_ROUTE_C1W for both
+                                roles), which recomputes the partial sums from the ctx's slice words; the forward and
+                                every size stay.  cimq_c1w_abi() == 1 */
 
 /* cimq_lsq_desc.flags */
 #define CIMQ_LSQ_ACCUMULATE_GRADS 1 /* cimq_module_backward adds the parameter gradients into
@@ -260,9 +266,12 @@ enum {
   CIMQ_ROUTE_WIDE = 11,    /* forward: cim_fwd_wide_kernel, the channel-chunked forward of 3x3 module layers from 128
                               input channels up (cimq_wide_abi() == 1); their backward stays CIMQ_ROUTE_GENERAL
                               unless CIMQ_OPT_WIDE_BWD is set */
-  CIMQ_ROUTE_WIDE_BWD = 12 /* grad_x: cim_bwd_gx_wide_kernel / grad_w: cim_bwd_gw_wide_kernel, the channel-chunked
+  CIMQ_ROUTE_WIDE_BWD = 12, /* grad_x: cim_bwd_gx_wide_kernel / grad_w: cim_bwd_gw_wide_kernel, the channel-chunked
                               compact-state backward of a CIMQ_ROUTE_WIDE layer under CIMQ_OPT_WIDE_BWD
                               (cimq_wide_bwd_abi() == 1) */
+  CIMQ_ROUTE_C1W = 13      /* the w8a8 first conv of 32 .. 512 output channels under CIMQ_OPT_WIDE_BWD:
+                              cim_bwd_c1w_kernel (both roles; + c1w_fold_kernel where an image's output blocks are
+                              split over several workgroups) (cimq_c1w_abi() == 1) */
 };
 int cimq_module_route(const cimq_conv_desc* d, int* route);
 
@@ -304,6 +313,14 @@ int cimq_wide_bwd_abi(void);
  * layer), without device work: out[0] 1 where it applies (else 0, and the rest 0), out[1] the channel chunks of the
  * grad_x grid, out[2] its bands of input rows per image, out[3] the pixel chunks (slabs) of grad_w. */
 int cimq_module_wide_bwd_plan(const cimq_conv_desc* d, int out[4]);
+
+/* 1 where CIMQ_ROUTE_C1W exists.  CIMQ_ABI_VERSION / _MINOR and the other availability numbers are unchanged: no
+ * struct, call or size moved. */
+int cimq_c1w_abi(void);
+/* The plan of that backward for `d` (the option bit need not be set), without device work: *ok 1 where it applies
+ * (else 0, and the rest 0), *groups the workgroups per image (the grid's y; above 1, c1w_fold_kernel adds their grad_x
+ * partials), *blocks_per_group the 16-channel output blocks each walks, *steps the 128-pixel steps per image. */
+int cimq_module_c1w_plan(const cimq_conv_desc* d, int* ok, int* groups, int* blocks_per_group, int* steps);
 int cimq_module_shift_forward(const cimq_conv_desc* d, const cimq_lsq_desc* q, const float* x, const float* weight,
                               const float* alpha_act, const float* alpha_weight, const float* alpha_cim,
                               const float* beta_cim, const int8_t* binary_mask, const float* signed_act, float* out,
