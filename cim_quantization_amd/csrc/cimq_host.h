@@ -546,28 +546,24 @@ struct PlanC1 {
   VC1 v;
 };
 
-inline PlanC1 c1_plan(const Geo& g) {
-  PlanC1 p;
-  memset(&p, 0, sizeof(p));
-  if (tune("C1", 1) == 0) return p;
-  const Plan7 p7 = v7_plan(g);
-  if (!p7.ok || g.variant != VAR_LIBRARY) return p;
-  if (g.NBP != 8 || g.nbw != 8 || g.nba != 8 || g.bsw != 1 || g.bsa != 1 || g.O != 16 || g.K > 32) return p;
-  if (g.SH != 1 || g.SW != 1 || g.KHW != 9 || g.T != 1) return p;
-  if (g.W < 8 || g.W > 64 || (g.W & (g.W - 1)) != 0 || g.Wo != g.W || g.Ho != g.H) return p;
-  VC1& v = p.v;
+// The recompute body's step geometry and LDS layout (cim_bwd_c1_kernel; shared by c1_plan and c1w_plan, which keep only
+// their own gates), for a 3x3 stride-1 same-size layer of one tile with W a power of two in 8 .. 64.  False where the
+// image is no whole number of 128-pixel steps, or a step's staging exceeds three 16-byte items per thread of 512.
+inline bool c1_fill(const Geo& g, VC1& v) {
   v.lw = 0;
   while ((1 << v.lw) < g.W) ++v.lw;
   v.R = 128 / g.W;
-  if (g.H % v.R != 0) return p;
+  if (g.H % v.R != 0) return false;
   v.nsteps = g.H / v.R;
   v.RH = (v.R - 1) + 3;
   v.WP = g.W + 2;
   v.SWD = std::min(16, g.W);
   v.NSEG = g.W / v.SWD;
   v.RSLOT = v.nsteps == 1 ? g.H : v.R + 2;
-  v.NCPBT = p7.v.NCPBT;
-  v.lcin = p7.v.lcin;
+  v.NCPBT = ((g.K - 1) / 3 >> 2) + 1;  // (c, kh)-blocks of 4 (one tile; v7_plan's count where it plans): at most 3
+  v.lcin = 0;
+  while ((1 << v.lcin) < g.C) ++v.lcin;
+  if ((1 << v.lcin) != g.C) v.lcin = -1;
   size_t o = 0;
   const size_t patch = a16((size_t)g.C * v.RH * v.WP * 8);
   v.o_xp = (unsigned)o; o += patch;
@@ -584,8 +580,19 @@ inline PlanC1 c1_plan(const Geo& g) {
   v.o_wc = (unsigned)o; o += (size_t)3 * 4 * 64 * 16;
   v.lds = (unsigned)o;
   // the kernel's one-step-ahead staging: at most three 16-byte items per thread of 512
-  if (2 * g.C * v.RH * (g.W / 2) + 512 > 3 * 512 || (g.K - 1) / 3 / 4 + 1 > 3) return p;
-  p.ok = o <= kLdsMax - 512;
+  return 2 * g.C * v.RH * (g.W / 2) + 512 <= 3 * 512 && v.NCPBT <= 3;
+}
+
+inline PlanC1 c1_plan(const Geo& g) {
+  PlanC1 p;
+  memset(&p, 0, sizeof(p));
+  if (tune("C1", 1) == 0) return p;
+  if (!v7_plan(g).ok || g.variant != VAR_LIBRARY) return p;
+  if (g.NBP != 8 || g.nbw != 8 || g.nba != 8 || g.bsw != 1 || g.bsa != 1 || g.O != 16 || g.K > 32) return p;
+  if (g.SH != 1 || g.SW != 1 || g.KHW != 9 || g.T != 1) return p;
+  if (g.W < 8 || g.W > 64 || (g.W & (g.W - 1)) != 0 || g.Wo != g.W || g.Ho != g.H) return p;
+  if (!c1_fill(g, p.v)) return p;
+  p.ok = p.v.lds <= kLdsMax - 512;
   return p;
 }
 
@@ -621,42 +628,11 @@ inline PlanC1W c1w_plan_compute(const Geo& g0) {
   int gen_rows, gen_chunks;
   gw_chunks(g, &gen_rows, &gen_chunks);
   if (g.B > gen_chunks) return p;
-  VC1& v = p.v.c;
-  v.lw = 0;
-  while ((1 << v.lw) < g.W) ++v.lw;
-  v.R = 128 / g.W;
-  if (g.H % v.R != 0) return p;
-  v.nsteps = g.H / v.R;
-  v.RH = (v.R - 1) + 3;
-  v.WP = g.W + 2;
-  v.SWD = std::min(16, g.W);
-  v.NSEG = g.W / v.SWD;
-  v.RSLOT = v.nsteps == 1 ? g.H : v.R + 2;
-  v.NCPBT = ((g.K - 1) / 3 >> 2) + 1;  // (c, kh)-blocks of 4 (one tile): at most 3
-  v.lcin = 0;
-  while ((1 << v.lcin) < g.C) ++v.lcin;
-  if ((1 << v.lcin) != g.C) v.lcin = -1;
   p.v.obg = std::max(tune("C1W_OBG", kC1wOBG), cdiv(g.OB16, kC1wGroups));
   p.v.groups = cdiv(g.OB16, p.v.obg);
-  size_t o = 0;
-  const size_t patch = a16((size_t)g.C * v.RH * v.WP * 8);
-  v.o_xp = (unsigned)o; o += patch;
-  v.o_hp = (unsigned)o; o += patch;
-  v.o_ptab = (unsigned)o; o += 64 * 4;
-  v.o_prm = (unsigned)o; o += 64 * 16 * 16;
-  v.o_cel = (unsigned)o; o += a16(3 * 64 * 4);
-  v.o_g = (unsigned)o; o += 16 * 132 * 4;
-  v.o_ring = (unsigned)o; o += a16((size_t)v.RSLOT * v.NSEG * 3 * g.C * (v.SWD + 2) * 4);
-  v.o_gal = (unsigned)o; o += 8 * 64 * 16 * 4;
-  v.o_red = (unsigned)o; o += a16((2 * 16 * 16 + 8) * 4);
-  v.o_e = (unsigned)o; o += 8 * 2 * 256 * 4;
-  v.o_wk = (unsigned)o; o += 8 * 64 * 16;
-  v.o_wc = (unsigned)o; o += (size_t)3 * 4 * 64 * 16;
-  v.lds = (unsigned)o;
-  // the kernel's one-step-ahead staging: at most three 16-byte items per thread of 512
-  if (2 * g.C * v.RH * (g.W / 2) + 512 > 3 * 512 || v.NCPBT > 3) return p;
+  if (!c1_fill(g, p.v.c)) return p;
   // (c1w_fold_kernel's LDS is 16 static bytes)
-  p.ok = p.v.obg >= 1 && p.v.groups <= kC1wGroups && o <= kLdsMax - 512;
+  p.ok = p.v.obg >= 1 && p.v.groups <= kC1wGroups && p.v.c.lds <= kLdsMax - 512;
   return p;
 }
 inline PlanC1W c1w_plan(const Geo& g) { return memo_geo<PlanC1W, c1w_plan_compute>(g); }

@@ -1,7 +1,7 @@
 // cimq_part_c1w.hip -- launch of the wide first conv's recompute backward under CIMQ_OPT_WIDE_BWD (c1w_plan,
-// CIMQ_ROUTE_C1W): cim_bwd_c1w_kernel over (image, output-block group) and, where an image has several groups,
-// c1w_fold_kernel over the images.  Own translation unit of libcimq.so, compiled without packed fp32 instructions
-// (build.py); cimq_part_fused.hip, its flags and cim_bwd_c1_kernel stay what they were.
+// CIMQ_ROUTE_C1W): cim_bwd_c1w_kernel (= cim_bwd_c1_kernel<true, true>) over (image, output-block group) and, where an image has several
+// groups, c1w_fold_kernel over the images.  Own translation unit of libcimq.so, compiled without packed fp32
+// instructions (build.py); cimq_part_fused.hip, with its own flags, holds the one-block instances of the same kernel.
 #include "cimq_host.h"
 #include "cimq_c1w.hip"
 

@@ -188,7 +188,7 @@ struct V9 {
   unsigned o_ring, o_cel, o_red, o_plane, o_gwl, o_gal, o_st, o_g, lds;  // LDS layout (bytes)
 };
 
-// ... of the first conv's backward (cimq_c1.hip; c1_plan)
+// ... of the first conv's recompute backward (cim_bwd_c1_kernel, cimq_c1.hip; c1_fill for c1_plan and c1w_plan)
 struct VC1 {
   int lw;       // log2(W)
   int R;        // output rows per step (128 / W)
@@ -200,7 +200,7 @@ struct VC1 {
   unsigned o_xp, o_hp, o_ptab, o_prm, o_cel, o_g, o_ring, o_gal, o_red, o_e, o_wk, o_wc, lds;
 };
 
-// ... of its multi-output-block sibling (cimq_c1w.hip; c1w_plan): c1's step geometry and LDS layout, and the split of
+// ... of its multi-output-block instance (cimq_c1w.hip; c1w_plan): the same step geometry and LDS layout, and the split of
 // the 16-channel output blocks over grid y
 struct VC1W {
   VC1 c;

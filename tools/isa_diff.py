@@ -4,7 +4,9 @@
     python tools/isa_diff.py PARENT_TREE NEW_TREE [-o OUT.md] [-j N] [UNIT ...]
 
 UNIT names a translation unit under cim_quantization_amd/csrc (default: cimq_part_fwd.hip).  Each unit of
-each tree is compiled device-only with build.py's flags, unbundled and disassembled; per kernel the table
+each tree is compiled device-only with the flags it ships with -- build.py's FLAGS, and for the units build.py names
+in NO_PK_F32_UNITS its NO_PK_F32 flags as well, all read from this tree's cim_quantization_amd/build.py (the one
+source of truth; the same flags go to both trees) -- unbundled and disassembled; per kernel the table
 holds the resource figures of both trees (the code object's metadata notes) and whether the instruction
 streams are equal once addresses, symbol names and the file-name line are dropped.  Exit status 1 if the
 kernel lists differ, or any kernel's resources or stream.
@@ -13,6 +15,7 @@ from __future__ import annotations
 
 import argparse
 import concurrent.futures
+import importlib.util
 import os
 import re
 import subprocess
@@ -22,10 +25,12 @@ import tempfile
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.environ.get("HIPCC", os.path.join(ROCM, "bin", "hipcc"))
 LLVM = os.path.join(ROCM, "lib", "llvm", "bin")
-ARCH = os.environ.get("CIMQ_OFFLOAD_ARCH", "gfx950")
-# cim_quantization_amd/build.py's flags
-FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-pass-failed",
-         "-mllvm", "-amdgpu-mfma-vgpr-form"]
+# cim_quantization_amd/build.py: every unit's flags, the units compiled without packed fp32 and the flags that do it
+_spec = importlib.util.spec_from_file_location(
+    "cimq_build", os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "cim_quantization_amd", "build.py"))
+_build = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(_build)
+ARCH, FLAGS = _build.ARCH, _build.FLAGS
 COLS = [("vgpr", ".vgpr_count"), ("agpr", ".agpr_count"), ("sgpr", ".sgpr_count"),
         ("sspill", ".sgpr_spill_count"), ("vspill", ".vgpr_spill_count"),
         ("scratch", ".private_segment_fixed_size"), ("lds", ".group_segment_fixed_size")]
@@ -35,7 +40,8 @@ def device_object(tree: str, unit: str, work: str) -> str:
     src = os.path.join(tree, "cim_quantization_amd", "csrc", unit)
     bundle = os.path.join(work, unit + ".bundle.o")
     obj = os.path.join(work, unit + ".gfx.o")
-    subprocess.run([HIPCC] + FLAGS + ["--cuda-device-only", "-c", "-o", bundle, src], check=True)
+    extra = _build.NO_PK_F32 if unit in _build.NO_PK_F32_UNITS else []
+    subprocess.run([HIPCC] + FLAGS + extra + ["--cuda-device-only", "-c", "-o", bundle, src], check=True)
     subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o",
                     f"--targets=hip-amdgcn-amd-amdhsa--{ARCH}", f"--input={bundle}", f"--output={obj}"], check=True)
     return obj
