@@ -114,7 +114,9 @@ class OracleConv2dLSQCiM(torch.nn.Conv2d):
             self.alpha_act.data.copy_(2 * x.abs().mean() / math.sqrt(qp_a))
             self.alpha_weight.data.copy_(2 * self.weight.abs().mean() / math.sqrt(qp_w))
             self.init_state.fill_(1)
-        sa = _gs(self.alpha_act, 1.0 / math.sqrt(x.numel() * qp_a))
+        # (tests: ``act_numel`` is the element count of the batch that x is a subset of -- grad_scale's factor, and
+        # through it the fp32 value of sa, are then that batch's)
+        sa = _gs(self.alpha_act, 1.0 / math.sqrt((getattr(self, "act_numel", None) or x.numel()) * qp_a))
         x_q = _rp((x / sa).clamp(qn_a, qp_a)) * sa
         sw = _gs(self.alpha_weight, 1.0 / math.sqrt(self.weight.numel() * qp_w))
         w_q = _rp((self.weight / sw).clamp(qn_w, qp_w)) * sw

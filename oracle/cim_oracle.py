@@ -354,7 +354,8 @@ def cim_backward(ctx: CimCtx, grad_out: np.ndarray, absolute: bool = False):
     lesser = ps <= thr_lo                                                        # :311
     Gm = np.where(greater | lesser, dt(0), G).astype(dt)                         # :313
     grad_alpha = grad_beta = None
-    numel = ps.size
+    # (tests: ``ps_numel`` in the meta is the partial-sum count of the batch that this ctx's images are a subset of)
+    numel = m.get("ps_numel") or ps.size
     c = F32(1.0 / math.sqrt(numel * m["qp"])) if adc_bits in (1, 1.5) else None
     if adc_bits == 1 and ctx.beta is None:                                       # :321-325
         q = np.sign(ps).astype(dt)

@@ -19,6 +19,10 @@ CASES = [
     case(2, 1, 32, 16, 16, bits=8),            # K = 9: one (c, kh) block
     case(2, 3, 32, 16, 8, bits=8, adc=4),      # a multi-bit ADC: the literal path
     case(2, 3, 80, 16, 8, bits=8, signed=1),   # five blocks: a last group of one
+    # the widths and step counts c1_fill accepts beyond those above (W <= 32, at most two steps)
+    case(2, 3, 32, 32, 32, bits=8, signed=1),  # VGG-small's image: eight steps, the ring reused four times
+    case(2, 3, 32, 4, 64, bits=8),             # W = 64: R = 2, four ring segments a row, two steps
+    case(2, 3, 32, 8, 64, bits=8, signed=1),   # W = 64, four steps
 ]
 GROUPS = 3    # the case that must report >= 2 groups
 LITERAL = 0   # ... that also runs with an all-equal alpha_cim (the literal flag)

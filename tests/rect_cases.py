@@ -62,6 +62,8 @@ FUNCTION_CASES = [
     case(2, 3, 16, 8, 32, bits=8, signed=1),
     case(2, 3, 16, 16, 8, bits=8, signed=1),
     case(2, 3, 16, 16, 8, bits=8, adc=4),        # ... a multi-bit ADC: the literal path without the act-LSQ fold
+    case(2, 3, 16, 4, 64, bits=8, signed=1),     # ... W = 64: two rows a step, four ring segments a row
+    case(2, 3, 16, 32, 32, bits=8, signed=1),    # ... eight steps: the ring reused four times
 ]
 
 # ---- the module path (Conv2dLSQCiM, steady state) with the (forward, grad_x, grad_w) kernels cimq_module_route
@@ -90,6 +92,8 @@ MODULE_CASES = [
     case(2, 3, 16, 16, 8, bits=8, signed=1, route=("v3", "c1", "c1")),     # ... one step of 16 rows
     case(2, 3, 16, 16, 8, bits=8, adc=4, route=("v3", "c1", "c1")),        # ... a multi-bit ADC: the literal path
     case(2, 1, 16, 16, 16, bits=8, route=("v3", "c1", "c1")),              # ... K = 9: one (c, kh) block
+    case(2, 3, 16, 4, 64, bits=8, signed=1, route=("v3", "c1", "c1")),     # ... W = 64: R = 2, four ring segments
+    case(2, 3, 16, 32, 32, bits=8, signed=1, route=("v3", "c1", "c1")),    # ... VGG-small's image: eight steps
 ]
 
 # 8-row grad_x bands at stride 1 need B * ceil(H / 8) >= 256: H = 12 gives an 8-row and a partial 4-row band

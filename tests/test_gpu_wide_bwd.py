@@ -171,7 +171,8 @@ def test_harness_step_with_wide_backward(cuda_device, tmp_path, capsys, monkeypa
     test_gpu_wide), so one update at lr 1e-4 leaves the two runs' weights at most ~1e-9 of a quantiser step apart: among
     4.6 M weights no code is expected to flip, and the losses differ by fp32 rounding of one forward -- bound 1e-4 of
     the loss.  (At the prototxt's lr 0.01 this B = 2 run has diverged to a loss near 80 by step three and is no
-    yardstick.)  On the model that trained: the five wide layers' routes and every parameter's gradient."""
+    yardstick.)  On the model that trained: the five wide layers' routes, the first conv's (general without the flag,
+    c1w with it) and every parameter's gradient."""
     import cim_quantization_amd._lib as L
     from cim_quantization_amd import functional as F
     from cim_quantization_amd._modules.lsq import Conv2dLSQCiM
@@ -190,11 +191,16 @@ def test_harness_step_with_wide_backward(cuda_device, tmp_path, capsys, monkeypa
         train.main(["--hp", str(hp), "--max-steps", "3", "--max-val-steps", "1"] + flags)
         out = capsys.readouterr().out
         losses.append([float(ln.split("loss ")[1].split()[0]) for ln in out.splitlines() if ln.startswith("Epoch [")])
-    for (model, _), want in zip(built, (WIDE, WIDE_BWD)):
+    # (the w8a8 first conv, 3 -> 128 on 32 x 32, trains on cim_bwd_c1w_kernel with the flag: test_gpu_c1w)
+    for (model, _), want, want1 in zip(built, (WIDE, WIDE_BWD), (("v3", "general", "general"), ("v3", "c1w", "c1w"))):
         wide = [m for m in model.modules() if isinstance(m, Conv2dLSQCiM) and m.in_channels >= 128]
         assert len(wide) == 5
         for m in wide:
             assert route_names(L, F.module_descs(m, m._last_x_shape)[0]) == want
+        first = [m for m in model.modules() if isinstance(m, Conv2dLSQCiM) and m.in_channels == 3]
+        assert len(first) == 1 and (first[0].out_channels, first[0].nbits_w, first[0].nbits_a) == (128, 8, 8)
+        assert first[0]._last_x_shape == (2, 3, 32, 32)
+        assert route_names(L, F.module_descs(first[0], first[0]._last_x_shape)[0]) == want1
         for n, p in model.named_parameters():
             assert p.grad is not None and torch.isfinite(p.grad).all(), n
     off, on = losses
