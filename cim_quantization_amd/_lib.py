@@ -106,6 +106,11 @@ EXPORTED_SYMBOLS = (
     "cimq_profile_stop",
     "cimq_profile_read",
     "cimq_flat_sgd",
+    "cimq_ideal_abi",
+    "cimq_ideal_plan",
+    "cimq_ideal_sizes",
+    "cimq_ideal_forward",
+    "cimq_ideal_backward",
 )
 
 KERNEL_IDS = {"fwd": 1, "bwd_gx": 2, "bwd_gw": 3, "prep_act": 4, "fwd_v7": 5, "gx_v8": 6, "gw_v7": 7, "bwd_fused": 8}
@@ -210,6 +215,20 @@ class QConvDesc(ctypes.Structure):
         ("dilation_h", ctypes.c_int32), ("dilation_w", ctypes.c_int32), ("groups", ctypes.c_int32),
         ("code_min", ctypes.c_int32), ("code_max", ctypes.c_int32),
         ("has_bias", ctypes.c_int32), ("reserved", ctypes.c_int32),
+    ]
+
+
+class IdealDesc(ctypes.Structure):
+    """Mirror of ``cimq_ideal_desc`` (cimq_ideal_abi() == 1)."""
+
+    _fields_ = [
+        ("batch", ctypes.c_int32), ("in_channels", ctypes.c_int32),
+        ("in_h", ctypes.c_int32), ("in_w", ctypes.c_int32),
+        ("out_channels", ctypes.c_int32), ("kernel_h", ctypes.c_int32), ("kernel_w", ctypes.c_int32),
+        ("stride_h", ctypes.c_int32), ("stride_w", ctypes.c_int32),
+        ("pad_h", ctypes.c_int32), ("pad_w", ctypes.c_int32),
+        ("bits_w", ctypes.c_int32), ("bits_a", ctypes.c_int32),
+        ("options", ctypes.c_int32), ("reserved", ctypes.c_int32),
     ]
 
 
@@ -374,6 +393,17 @@ def _bind(lib):
     lib.cimq_flat_sgd.restype = ctypes.c_int
     lib.cimq_flat_sgd.argtypes = [ctypes.c_longlong, _VP, _VP, _VP, _VP, ctypes.c_float, ctypes.c_float, ctypes.c_int,
                                   ctypes.c_int, _VP]
+    if hasattr(lib, "cimq_ideal_abi"):
+        lib.cimq_ideal_abi.restype = ctypes.c_int
+        lib.cimq_ideal_abi.argtypes = []
+        lib.cimq_ideal_plan.restype = ctypes.c_int
+        lib.cimq_ideal_plan.argtypes = [ctypes.POINTER(IdealDesc), ctypes.POINTER(ctypes.c_int)]
+        lib.cimq_ideal_sizes.restype = ctypes.c_int
+        lib.cimq_ideal_sizes.argtypes = [ctypes.POINTER(IdealDesc)] + [ctypes.POINTER(ctypes.c_size_t)] * 2
+        lib.cimq_ideal_forward.restype = ctypes.c_int
+        lib.cimq_ideal_forward.argtypes = [ctypes.POINTER(IdealDesc)] + [_VP] * 8
+        lib.cimq_ideal_backward.restype = ctypes.c_int
+        lib.cimq_ideal_backward.argtypes = [ctypes.POINTER(IdealDesc)] + [_VP] * 12
     lib.cimq_profile_start.restype = ctypes.c_int
     lib.cimq_profile_start.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.cimq_profile_read.restype = ctypes.c_int
@@ -485,6 +515,34 @@ def qconv_sizes(desc: QConvDesc):
     f, b = ctypes.c_size_t(), ctypes.c_size_t()
     check(load().cimq_qconv_sizes(ctypes.byref(desc), ctypes.byref(f), ctypes.byref(b)), "cimq_qconv_sizes")
     return f.value, b.value
+
+
+def make_ideal_desc(B, C, H, W, O, KH, KW, stride, padding, bits_w, bits_a, options=0, reserved=0) -> IdealDesc:
+    d = IdealDesc()
+    d.batch, d.in_channels, d.in_h, d.in_w = int(B), int(C), int(H), int(W)
+    d.out_channels, d.kernel_h, d.kernel_w = int(O), int(KH), int(KW)
+    d.stride_h, d.stride_w = int(stride[0]), int(stride[1])
+    d.pad_h, d.pad_w = int(padding[0]), int(padding[1])
+    d.bits_w, d.bits_a = int(bits_w), int(bits_a)
+    d.options, d.reserved = int(options), int(reserved)
+    return d
+
+
+def ideal_plan(desc: IdealDesc):
+    """(ok, m-tiles per image, forward channel chunks, grad_x bands per image, grad_w slabs) of the ideal-ADC conv
+    for ``desc`` -- cimq_ideal_plan; a descriptor off the plan answers ok = 0 (the reason in cimq_last_error()), a
+    malformed one raises."""
+    f = (ctypes.c_int * 5)()
+    rc = load().cimq_ideal_plan(ctypes.byref(desc), f)
+    if rc not in (0, CIMQ_EUNSUPPORTED):
+        check(rc, "cimq_ideal_plan")
+    return tuple(f)
+
+
+def ideal_sizes(desc: IdealDesc):
+    c, w = ctypes.c_size_t(), ctypes.c_size_t()
+    check(load().cimq_ideal_sizes(ctypes.byref(desc), ctypes.byref(c), ctypes.byref(w)), "cimq_ideal_sizes")
+    return c.value, w.value
 
 
 def module_route(desc: ConvDesc):

@@ -17,7 +17,8 @@ import math
 import torch
 import torch.nn.functional as F
 
-from ..functional import (alpha_cim_init, cim_conv2d_lsq, cim_conv2d_lsq_shift, cim_module_conv,  # noqa: F401
+from ..functional import (alpha_cim_init, cim_conv2d_lsq, cim_conv2d_lsq_shift, cim_ideal_conv, cim_module_conv,  # noqa: F401
+                          ideal_conv_plan,
                           act_codes_of, cim_module_conv_codes, cim_module_conv_epilogue, cim_module_conv_pool,
                           cim_module_shift_conv, get_adcless_cim_output, get_analog_partial_sums_autograd_ver2,
                           conv_out_hw, get_cim_output_signed, inference_call, inference_weights, lsq_quantize,
@@ -56,7 +57,11 @@ class Conv2dLSQCiM(_Conv2dQCiM):
     On the fused library-ADC path, and on the fused shift path (beta_cim then counts among the parameters), the
     layer then keeps the weight side it prepared (``_inf_prep``) and
     reuses it while the input shape and the parameters' versions and addresses are unchanged, so a whole
-    evaluation quantises the weights once per input shape.  ``train(True)`` and ``load_state_dict`` drop
+    evaluation quantises the weights once per input shape.
+
+    ``adcbits=0`` (the ideal ADC: no partial-sum quantisation) runs in steady state on the library's fused int8
+    forward and bf16 backward (``ideal_ready``; functional.cim_ideal_conv), the first step and any refused shape on
+    torch.  That path's contract excludes non-finite activations and weights.  ``train(True)`` and ``load_state_dict`` drop
     it, a call made with grad enabled never reads it, and stochastic-ADC layers keep none.  An edit
     through ``p.data`` bumps no version counter (functional._versions): after one, call ``train()`` /
     ``eval()`` again or torch.autograd.graph.increment_version(p) before the next evaluation."""
@@ -140,7 +145,8 @@ class Conv2dLSQCiM(_Conv2dQCiM):
         qp_adc = _adc_qp(self.adcbits)
         qn_a, qp_a = _act_range(self.nbits_a)
         flags = self._init_flags()
-        if self.training and not flags[0]:
+        first_step = self.training and not flags[0]
+        if first_step:
             # lsq.py:532-542: sign detection and LSQ step-size init on the first training step
             if x.min() < -1e-5:
                 self.signed_act.data.fill_(1)
@@ -180,6 +186,11 @@ class Conv2dLSQCiM(_Conv2dQCiM):
             if self.bias is not None:
                 out = out + self.bias  # broadcasts over the last axis, as lsq.py:583
             return out
+        if self.adcbits == 0 and not first_step and self.ideal_ready(x):
+            # the ideal ADC in steady state: both quantisers, the conv and its backward in the library
+            out = cim_ideal_conv(x, self.weight, self.alpha_act, self.alpha_weight, self.stride, self.padding,
+                                 self.nbits_a, self.nbits_w)
+            return out if self.bias is None else out + self.bias.view(1, -1, 1, 1)  # F.conv2d's per-channel bias
         sa = grad_scale(self.alpha_act, 1.0 / math.sqrt(x.numel() * qp_a))            # lsq.py:547-548
         sw = grad_scale(self.alpha_weight, 1.0 / math.sqrt(self.weight.numel() * qp_w))  # lsq.py:553-554
         w_q = round_pass((self.weight / sw).clamp(qn_w, qp_w)) * sw                   # lsq.py:555
@@ -211,6 +222,25 @@ class Conv2dLSQCiM(_Conv2dQCiM):
         if self.bias is not None:
             out = out + self.bias  # broadcasts over the last axis, as lsq.py:583
         return out
+
+    def ideal_ready(self, x):
+        """Whether ``forward`` runs this ``adcbits == 0`` layer for input ``x`` on libcimq's ideal-ADC kernels
+        (functional.cim_ideal_conv): ``fused`` set, the first-step initialisation done, ROCm fp32 tensors, groups 1,
+        dilation 1 and a shape cimq_ideal_plan accepts for this kind of call -- differentiable, or forward only, as
+        grad mode and the tensors say now (cached per shape).  Everything else runs the torch branch.
+        Non-finite activations or weights are outside that path's contract: an int8 code cannot carry a NaN."""
+        if not (self.adcbits == 0 and self.fused and self._init_flags()[0] and torch.is_tensor(x) and x.is_cuda
+                and x.dtype == torch.float32 and x.dim() == 4 and self.weight.is_cuda
+                and self.weight.dtype == torch.float32 and self.groups == 1 and tuple(self.dilation) == (1, 1)):
+            return False
+        key = tuple(x.shape)
+        hit = getattr(self, "_ideal_ok", None)
+        if hit is None or hit[0] != key:
+            hit = self._ideal_ok = (key, ideal_conv_plan(*key, self.out_channels, *self.weight.shape[-2:],
+                                                         tuple(self.stride), tuple(self.padding), self.nbits_a,
+                                                         self.nbits_w)[0])
+        # (training answer, forward-only answer): a large layer trains on torch and evaluates in the library
+        return hit[1][1 if inference_call(x, self.weight, self.alpha_act, self.alpha_weight) else 0]
 
     def fused_epilogue_ready(self, x):
         """Whether ``forward_fused`` takes this layer for input ``x``: the steady-state library path (both

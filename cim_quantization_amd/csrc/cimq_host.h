@@ -1442,6 +1442,130 @@ inline bool routes_agree(const Geo& g) {
          r0.wgx == r1.wgx && r0.wcy == r1.wcy && r0.wg5 == r1.wg5 && r0.wx6 == r1.wx6;
 }
 
+// ---------------------------------------------------------------------------------------
+// ideal_plan: the ideal-ADC conv (cimq_ideal.hip).  Validates the descriptor and fills the geometry and the launch
+// plans of its three kernels; every refusal leaves its reason in cimq_last_error().
+// ---------------------------------------------------------------------------------------
+constexpr size_t kIdealLdsAim = 80 * 1024;  // two workgroups a CU (wide_plan's rule)
+constexpr long long kIdealTrainMacs = 1LL << 30;  // padded MACs B * P * OP * Cp * KH * KW a training descriptor may have
+inline int pitch16_odd(int n) { return (n & 1) ? n : n + 1; }  // a pitch in 16-byte units: odd, so 16 lanes' b128 reads tile the banks
+
+inline size_t ideal_fwd_lds(const IdealG& g, int ncx) {
+  const size_t tab = (size_t)cdiv((long long)g.ntap * ncx, 64) * 4 * 4;
+  return ((tab + 15) & ~(size_t)15) + (size_t)g.frows * g.fwp * 16 * pitch16_odd(ncx / 16);
+}
+inline size_t ideal_gx_lds(const IdealG& g, int noc) {
+  const size_t tab = (size_t)cdiv((long long)g.ntap * noc, 32) * 4 * 4;
+  return ((tab + 15) & ~(size_t)15) + (size_t)3 * g.xrows * g.Wo * 16 * pitch16_odd(noc / 8);
+}
+// the largest multiple of 16 (at most n16 * 16) whose LDS meets the aim, 16 where none does
+template <class F>
+inline int ideal_chunk(int n16, F bytes) {
+  int c = n16;
+  while (c > 1 && bytes(c * 16) > kIdealLdsAim) --c;
+  return c * 16;
+}
+
+inline int ideal_plan(const cimq_ideal_desc* d, IdealG* out) {
+  if (!d) return fail(CIMQ_EINVAL, "ideal: null descriptor");
+  if (d->reserved != 0) return fail(CIMQ_EINVAL, "ideal: reserved must be 0");
+  if (d->options & ~CIMQ_OPT_INFERENCE) return fail(CIMQ_EINVAL, "ideal: unknown option bits 0x%x", d->options);
+  IdealG g;
+  memset(&g, 0, sizeof(g));
+  g.B = d->batch; g.C = d->in_channels; g.H = d->in_h; g.W = d->in_w; g.O = d->out_channels;
+  g.KH = d->kernel_h; g.KW = d->kernel_w; g.SH = d->stride_h; g.SW = d->stride_w; g.PH = d->pad_h; g.PW = d->pad_w;
+  if (g.B < 1 || g.C < 1 || g.H < 1 || g.W < 1 || g.O < 1 || g.KH < 1 || g.KW < 1 || g.SH < 1 || g.SW < 1 ||
+      g.PH < 0 || g.PW < 0)
+    return fail(CIMQ_EINVAL, "ideal: bad geometry");
+  if (g.KH > 7 || g.KW > 7) return fail(CIMQ_EUNSUPPORTED, "ideal: kernel larger than 7 (%d x %d)", g.KH, g.KW);
+  if (g.SH > 2 || g.SW > 2) return fail(CIMQ_EUNSUPPORTED, "ideal: stride above 2");
+  if (d->bits_a < 2 || d->bits_a > 8 || d->bits_w < 2 || d->bits_w > 8)
+    return fail(CIMQ_EUNSUPPORTED, "ideal: bits outside [2, 8] (w%d a%d)", d->bits_w, d->bits_a);
+  g.Ho = (g.H + 2 * g.PH - g.KH) / g.SH + 1;
+  g.Wo = (g.W + 2 * g.PW - g.KW) / g.SW + 1;
+  if (g.H + 2 * g.PH < g.KH || g.W + 2 * g.PW < g.KW) return fail(CIMQ_EINVAL, "ideal: empty output");
+  g.ntap = g.KH * g.KW;
+  // |code_a| <= 255, |code_w| <= 128: 65536 products of at most 32640 stay below 2^31
+  if ((long long)g.C * g.ntap > 65536)
+    return fail(CIMQ_EUNSUPPORTED, "ideal: contraction C * KH * KW above 65536 (the int32 accumulator)");
+  g.P = g.Ho * g.Wo;
+  g.Cp = (g.C + 15) / 16 * 16; g.ncb = g.Cp / 16;
+  g.OP = (g.O + 15) / 16 * 16; g.nob = g.OP / 16;
+  const long long lim = 1LL << 31;
+  if (g.nob > 65535) return fail(CIMQ_EUNSUPPORTED, "ideal: more than 65535 output blocks");
+  if ((long long)g.B * g.C * g.H * g.W >= lim || (long long)g.B * g.OP * g.Ho * g.Wo >= lim ||
+      (long long)g.OP * g.Cp * g.ntap >= lim)
+    return fail(CIMQ_EUNSUPPORTED, "ideal: a tensor beyond 32-bit indexing");
+  g.qp_a = (float)((1 << d->bits_a) - 1);
+  g.qn_w = -(float)(1 << (d->bits_w - 1));
+  g.qp_w = (float)((1 << (d->bits_w - 1)) - 1);
+  g.ga = (float)(1.0 / sqrt((double)g.B * g.C * g.H * g.W * (double)g.qp_a));
+  g.gw = (float)(1.0 / sqrt((double)g.O * g.C * g.ntap * (double)g.qp_w));
+  g.split = d->bits_a == 8;
+  g.inference = (d->options & CIMQ_OPT_INFERENCE) ? 1 : 0;
+  const size_t ldsmax = kLdsMax - 512;
+  // the measured gate: forward + backward beat the torch branch on every ResNet-20 shape
+  // (0.6 G padded MACs at B = 256) and lost to it on every VGG-small shape (4.8 G and up); the forward alone won on all
+  const long long macs = (long long)g.B * g.P * g.OP * g.Cp * g.ntap;
+  if (!g.inference && macs > kIdealTrainMacs)
+    return fail(CIMQ_EUNSUPPORTED, "ideal: a training call of %lld M MACs stays on the vendor conv (above %lld M)",
+                macs >> 20, kIdealTrainMacs >> 20);
+
+  // forward
+  g.mt = cdiv(g.P, 64);
+  const int nor = std::min(g.Ho, (64 % g.Wo == 0) ? 64 / g.Wo : 63 / g.Wo + 2);
+  g.frows = (nor - 1) * g.SH + g.KH;
+  g.fwp = g.W + 2 * g.PW;
+  const int ncx0 = ideal_chunk(g.ncb, [&](int n) { return ideal_fwd_lds(g, n); });
+  g.nch = cdiv(g.Cp, ncx0);
+  g.ncx = cdiv(cdiv(g.Cp, g.nch), 16) * 16;
+  g.fpitch = 16 * pitch16_odd(g.ncx / 16);
+  g.fks = cdiv((long long)g.ntap * g.ncx, 64);
+  g.nobw = g.nob >= 4 ? 4 : (g.nob >= 2 ? 2 : 1);
+  g.flds = (int)ideal_fwd_lds(g, g.ncx);
+  if ((size_t)g.flds > ldsmax) return fail(CIMQ_EUNSUPPORTED, "ideal: the forward patch needs %d bytes of LDS", g.flds);
+
+  // grad_x
+  g.xwb = std::min(g.W, 16 * 4 * kIdealPGX);
+  g.xrb = std::max(1, std::min(g.H, 16 * 4 * kIdealPGX / g.xwb));
+  g.xnrb = cdiv(g.H, g.xrb);
+  g.xncol = cdiv(g.W, g.xwb);
+  g.xrows = std::min(g.Ho, cdiv(g.xrb + g.KH - 1, g.SH));
+  const int noc0 = ideal_chunk(g.nob, [&](int n) { return ideal_gx_lds(g, n); });
+  g.xnoch = cdiv(g.OP, noc0);
+  g.noc = cdiv(cdiv(g.OP, g.xnoch), 16) * 16;
+  g.xopitch = 8 * pitch16_odd(g.noc / 8);
+  g.xks = cdiv((long long)g.ntap * g.noc, 32);
+  g.xlds = (int)ideal_gx_lds(g, g.noc);
+  if ((size_t)g.xlds > ldsmax) return fail(CIMQ_EUNSUPPORTED, "ideal: grad_x's planes need %d bytes of LDS", g.xlds);
+
+  // grad_w
+  g.wspr = cdiv(g.Wo, 8);
+  g.wrb = std::max(1, std::min(g.Ho, cdiv(16, g.wspr)));
+  g.wnb = cdiv(g.Ho, g.wrb);
+  g.wntg = cdiv(g.ntap, kIdealTG);
+  const long long units = (long long)g.B * g.wnb;
+  const long long wgs = (long long)g.ncb * g.wntg * cdiv(g.nob, kIdealOBG);
+  const long long want = std::max(1LL, std::min(256LL, 1024 / wgs));
+  g.wupc = cdiv(units, std::min(units, want));
+  g.wslabs = cdiv(units, g.wupc);
+  g.wxrows = (g.wrb - 1) * g.SH + g.KH;
+  g.wxw = (g.wspr * 8 - 1) * g.SW + g.KW;
+  g.wxplane = (g.wxrows * g.wxw) | 1;
+  g.wgpitch = 8 * pitch16_odd(g.wrb * g.wspr);
+  const size_t wstage = (((size_t)16 * g.wxplane * 2 + 15) & ~(size_t)15) + (size_t)3 * 16 * kIdealOBG * g.wgpitch * 2;
+  const size_t wred = (size_t)kIdealTG * kIdealOBG * 4 * 64 * 16;
+  g.wlds = (int)std::max(wstage, wred);
+  if ((size_t)g.wlds > ldsmax) return fail(CIMQ_EUNSUPPORTED, "ideal: grad_w's rows need %d bytes of LDS", g.wlds);
+  if ((long long)g.wslabs * g.OP * g.ntap * g.Cp >= lim)
+    return fail(CIMQ_EUNSUPPORTED, "ideal: grad_w's slabs beyond 32-bit indexing");
+  *out = g;
+  return CIMQ_OK;
+}
+inline size_t ideal_wf_bytes(const IdealG& g) { return align256((size_t)g.nch * g.fks * g.nob * 64 * 16); }
+inline size_t ideal_wx_bytes(const IdealG& g) { return align256((size_t)g.ncb * g.xnoch * g.xks * 64 * 16); }
+inline int ideal_gx_blocks(const IdealG& g) { return g.B * g.xnrb * g.xncol * cdiv(g.ncb, kIdealCBX); }
+
 template <typename K>
 inline int set_lds(K kernel, size_t bytes) {
   if (bytes > 64 * 1024) {

@@ -356,4 +356,25 @@ constexpr int kWideOBM = 4;  // 16-channel output blocks per workgroup (tables s
   X(cfl, (size_t)nkj * kWideOBM * 16 * 4)          /* coef, same order */                                  \
   X(ckl, a16((size_t)3 * g.nbw * g.nba * 4))       /* [3][nkj] (Params::ckj) */
 
+// The ideal-ADC conv (cimq_ideal.hip; ideal_plan): LSQ codes on both sides, no partial-sum quantisation.  Geometry,
+// quantiser constants and the three kernels' launch plans, filled by the host and passed by value.
+constexpr int kIdealTG = 9;     // grad_w: taps a workgroup accumulates at a time
+constexpr int kIdealOBG = 2;    // grad_w: 16-channel output blocks per workgroup
+constexpr int kIdealCBX = 4;    // grad_x: 16-channel input blocks per workgroup
+constexpr int kIdealPGX = 2;    // grad_x: 16-pixel groups per wave
+constexpr int kIdealTailBlocks = 1024;
+struct IdealG {
+  int B, C, H, W, O, KH, KW, SH, SW, PH, PW, Ho, Wo, P;
+  int Cp, ncb, OP, nob, ntap;  // channels padded to 16 and their blocks, both sides; KH * KW
+  float qp_a, qn_w, qp_w;      // clamp ranges (activations from 0)
+  float ga, gw;                // grad_scale factors 1 / sqrt(numel * Qp)
+  int split, inference;
+  // forward: 64-pixel m-tiles of one image, the patch [frows][fwp][fpitch] bytes of ncx channels at a time
+  int mt, frows, fwp, ncx, nch, fpitch, fks, nobw, flds;
+  // grad_x: bands of xrb rows x xwb columns (at most 128 pixels), grad_out staged noc channels at a time
+  int xrb, xwb, xnrb, xncol, xrows, noc, xnoch, xopitch, xks, xlds;
+  // grad_w: units of wrb output rows of one image, wupc units per slab
+  int wrb, wspr, wnb, wupc, wslabs, wntg, wxrows, wxw, wxplane, wgpitch, wlds;
+};
+
 }  // namespace cimq

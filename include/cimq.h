@@ -750,6 +750,56 @@ int cimq_profile_read(int cap, double* ms, double* algo_bytes, double* algo_flop
 int cimq_flat_sgd(long long n, float* param, float* grad, float* buf, const float* wd, float lr, float momentum,
                   int first, int zero_grad, void* stream);
 
+/* The ideal-ADC conv: Conv2dLSQCiM(adcbits = 0), LSQ codes on both sides and no partial-sum quantisation
+ * (lsq.py:584-585), forward and backward in the library.  cimq_ideal_abi() == 1 where the calls below exist.
+ *   sa = grad_scale(alpha_act, ga), code_a = rint(clamp(x / sa, 0, 2^bits_a - 1))        (one IEEE division)
+ *   sw = grad_scale(alpha_weight, gw), code_w = rint(clamp(weight / sw, -2^(bits_w-1), 2^(bits_w-1) - 1))
+ *   out = conv(code_a, code_w) * sa * sw
+ * with ga = 1 / sqrt(numel(x) * Qp_a), gw = 1 / sqrt(numel(weight) * Qp_w) derived from the descriptor.  The conv is
+ * one int32 accumulation over all of C * KH * KW (exact; C * KH * KW <= 65536 keeps it inside int32).  The backward is
+ * the autograd of round_pass(clamp(v / s)) * s around the conv: the clamp passes the gradient where
+ * qn <= v / s <= qp (bounds inclusive), each step size collects rint(clamp(v / s)) - [inside] * v / s times the
+ * incoming gradient, and grad_scale's factor is applied on the way to the parameter.  Every sum has a fixed order:
+ * two calls give the same bits.
+ * A non-finite x or weight element is outside this path's contract: an int8 code cannot carry a NaN.
+ * No call allocates, synchronises or reads device memory on the host. */
+int cimq_ideal_abi(void);
+
+typedef struct cimq_ideal_desc {
+  int32_t batch, in_channels, in_h, in_w;
+  int32_t out_channels, kernel_h, kernel_w;
+  int32_t stride_h, stride_w, pad_h, pad_w;
+  int32_t bits_w, bits_a;
+  int32_t options;  /* 0 or CIMQ_OPT_INFERENCE */
+  int32_t reserved; /* must be 0 */
+} cimq_ideal_desc;
+
+/* Host query, no device work.  out[0] = 1 where the calls take d (0 with CIMQ_EUNSUPPORTED and the reason in
+ * cimq_last_error() otherwise), out[1] = 64-pixel m-tiles per image of the forward, out[2] = channel chunks of its
+ * LDS patch, out[3] = grad_x bands per image, out[4] = grad_w pixel chunks (slabs).  Admitted: groups 1 and
+ * dilation 1 (neither can be expressed), KH, KW <= 7, stride 1 or 2 per axis, bits_a, bits_w in [2, 8],
+ * C * KH * KW <= 65536, every tensor below 2^31 elements, every kernel's LDS within the device's, and without
+ * CIMQ_OPT_INFERENCE at most 2^30 padded multiply-accumulates B * Ho * Wo * O16 * C16 * KH * KW (above, the vendor
+ * conv's backward measured faster; the forward-only descriptor has no such bound).  CIMQ_EINVAL for a
+ * NULL pointer, a non-positive extent, a non-zero reserved or an unknown option bit. */
+int cimq_ideal_plan(const cimq_ideal_desc* d, int out[5]);
+
+/* ctx: the weight codes as MFMA fragments, all the forward leaves for the backward (which re-reads x); under
+ * CIMQ_OPT_INFERENCE the forward's fragments alone, so ctx_bytes is smaller.  ws: the backward's partial sums and
+ * grad_w slabs, the same number with and without the bit; the forward does not touch ws. */
+int cimq_ideal_sizes(const cimq_ideal_desc* d, size_t* ctx_bytes, size_t* ws_bytes);
+
+/* x [B, C, H, W] and weight [O, C, KH, KW] raw fp32, alpha_act / alpha_weight device pointers to one float,
+ * out [B, O, Ho, Wo] fp32.  Two launches: the weight quantiser into ctx, the conv. */
+int cimq_ideal_forward(const cimq_ideal_desc* d, const float* x, const float* weight, const float* alpha_act,
+                       const float* alpha_weight, float* out, void* ctx, void* ws, void* stream);
+
+/* grad_x, grad_w in the shapes of x, weight; grad_alpha_act / grad_alpha_weight one float each, written (not added
+ * to).  ctx as the forward of the same descriptor and parameters left it.  CIMQ_EINVAL on an inference descriptor. */
+int cimq_ideal_backward(const cimq_ideal_desc* d, const float* x, const float* weight, const float* alpha_act,
+                        const float* alpha_weight, const float* grad_out, const void* ctx, float* grad_x,
+                        float* grad_w, float* grad_alpha_act, float* grad_alpha_weight, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

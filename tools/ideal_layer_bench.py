@@ -1,0 +1,115 @@
+"""Time of one Conv2dLSQCiM(adcbits=0) layer -- the ideal ADC -- on the library path (functional.cim_ideal_conv:
+cimq_ideal_forward / cimq_ideal_backward) and on the torch branch (``fused = False``: torch quantisers, the vendor
+conv, autograd), per distinct ResNet-20 conv shape (bench.RESNET20, at w3a3 and w4a4; its first conv at w8a8) and per
+VGG-small conv shape (the first conv and tools/wide_layer_bench.py's SHAPES, w3a3 and w4a4), B = 256.
+
+For each shape: forward + backward, and the no-grad forward, each captured as one HIP graph and timed over
+``--steps`` replays between two HIP events after a warm-up (w4a4_layer_bench._graph_ms); the two sides alternate over
+``--runs`` runs in one session.  Per row the runs, their medians and spreads (max - min) and ``faster_*``: the
+library's median is below torch's by more than the larger of the two spreads -- the gate a shape has to pass to stay
+in ideal_plan.
+
+    python tools/ideal_layer_bench.py --out profiles/ideal/summary.json
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from wide_layer_bench import SHAPES as VGG_WIDE  # noqa: E402
+
+
+def shapes(bits):
+    """(net, C, O, H, stride, bits), each once"""
+    import bench
+    out = []
+    for _, c, o, h, s, nb in bench.RESNET20:
+        for b in ([8] if nb == 8 else bits):
+            row = ("resnet20", c, o, h, s, b)
+            if row not in out:
+                out.append(row)
+    for c, o, h in [(3, 128, 32)] + list(VGG_WIDE):
+        for b in ([8] if c == 3 else bits):
+            out.append(("vggsmall", c, o, h, 1, b))
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--bits", type=int, nargs="+", default=[3, 4])
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args(argv)
+    import torch
+
+    import cim_quantization_amd._modules as my_nn
+    from w4a4_layer_bench import _graph_ms
+    if not torch.cuda.is_available():
+        raise SystemExit("ideal_layer_bench measures on a GPU; none found")
+    dev = torch.device("cuda", 0)
+    rows = []
+    for net, c, o, h, s, bits in shapes(args.bits):
+        torch.manual_seed(11)
+        m = my_nn.Conv2dLSQCiM(c, o, 3, s, 1, bias=False, nbits_w=bits, nbits_a=bits, adcbits=0)
+        torch.nn.init.kaiming_normal_(m.weight)
+        m = m.to(dev).train()
+        x = torch.randn(args.batch, c, h, h, device=dev).relu()
+        ho = (h + 2 - 3) // s + 1
+        g = torch.randn(args.batch, o, ho, ho, device=dev) / math.sqrt(args.batch * o * ho * ho)
+        m(x[:2].contiguous()).backward(g[:2].contiguous())  # the initialising step, on two images (torch path)
+        xg = x.clone().requires_grad_(True)
+
+        def step():
+            xg.grad = None
+            m(xg).backward(g)
+
+        def evalf():
+            with torch.no_grad():
+                m(x)
+
+        us = {(k, on): [] for k in ("step", "eval") for on in (False, True)}
+        ready = None
+        for _ in range(args.runs):
+            for on in (False, True):
+                m.fused = on
+                if on:
+                    ready = bool(m.ideal_ready(x))
+                us[("step", on)].append(1e3 * _graph_ms(step, args.steps, args.warmup))
+                us[("eval", on)].append(1e3 * _graph_ms(evalf, args.steps, args.warmup))
+        med = {k: statistics.median(v) for k, v in us.items()}
+        spread = {k: max(v) - min(v) for k, v in us.items()}
+        row = {"net": net, "bits": bits, "C": c, "O": o, "H": h, "stride": s, "ideal_ready": ready}
+        for k in ("step", "eval"):
+            row.update({f"us_{k}_torch": us[(k, False)], f"us_{k}_lib": us[(k, True)],
+                        f"median_{k}_torch": med[(k, False)], f"median_{k}_lib": med[(k, True)],
+                        f"spread_{k}_torch": spread[(k, False)], f"spread_{k}_lib": spread[(k, True)],
+                        f"faster_{k}": med[(k, True)] < med[(k, False)] - max(spread[(k, False)], spread[(k, True)])})
+        rows.append(row)
+        print(f"{net} w{bits}a{bits} {c:3d}->{o:3d} {h:2d}x{h:<2d} s{s} ready {ready}  fwd+bwd torch "
+              f"{med[('step', False)]:8.1f} us (+-{spread[('step', False)]:.1f}) lib {med[('step', True)]:8.1f} us "
+              f"(+-{spread[('step', True)]:.1f}) faster {row['faster_step']}  eval torch {med[('eval', False)]:8.1f} us "
+              f"lib {med[('eval', True)]:8.1f} us faster {row['faster_eval']}", flush=True)
+        del m, x, xg, g
+        torch.cuda.empty_cache()
+    out = {"batch": args.batch, "adc": 0, "steps": args.steps, "warmup": args.warmup, "runs": args.runs,
+           "launch": "hip_graph", "device": torch.cuda.get_device_name(dev), "rows": rows}
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+    return out
+
+
+if __name__ == "__main__":
+    main()
