@@ -111,6 +111,8 @@ EXPORTED_SYMBOLS = (
     "cimq_ideal_sizes",
     "cimq_ideal_forward",
     "cimq_ideal_backward",
+    "cimq_ideal_wide_abi",
+    "cimq_ideal_wide_plan",
 )
 
 KERNEL_IDS = {"fwd": 1, "bwd_gx": 2, "bwd_gw": 3, "prep_act": 4, "fwd_v7": 5, "gx_v8": 6, "gw_v7": 7, "bwd_fused": 8}
@@ -404,6 +406,11 @@ def _bind(lib):
         lib.cimq_ideal_forward.argtypes = [ctypes.POINTER(IdealDesc)] + [_VP] * 8
         lib.cimq_ideal_backward.restype = ctypes.c_int
         lib.cimq_ideal_backward.argtypes = [ctypes.POINTER(IdealDesc)] + [_VP] * 12
+    if hasattr(lib, "cimq_ideal_wide_abi"):
+        lib.cimq_ideal_wide_abi.restype = ctypes.c_int
+        lib.cimq_ideal_wide_abi.argtypes = []
+        lib.cimq_ideal_wide_plan.restype = ctypes.c_int
+        lib.cimq_ideal_wide_plan.argtypes = [ctypes.POINTER(IdealDesc), ctypes.POINTER(ctypes.c_int)]
     lib.cimq_profile_start.restype = ctypes.c_int
     lib.cimq_profile_start.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.cimq_profile_read.restype = ctypes.c_int
@@ -536,6 +543,17 @@ def ideal_plan(desc: IdealDesc):
     rc = load().cimq_ideal_plan(ctypes.byref(desc), f)
     if rc not in (0, CIMQ_EUNSUPPORTED):
         check(rc, "cimq_ideal_plan")
+    return tuple(f)
+
+
+def ideal_wide_plan(desc: IdealDesc):
+    """(ok, grad_x workgroups per image, grad_x output-channel chunks, grad_w stages per slab, grad_w slabs, LDS bytes)
+    of the large-layer backward pair for ``desc`` -- cimq_ideal_wide_plan; off its plan ok = 0 (the reason in
+    cimq_last_error()), a malformed descriptor raises."""
+    f = (ctypes.c_int * 6)()
+    rc = load().cimq_ideal_wide_plan(ctypes.byref(desc), f)
+    if rc not in (0, CIMQ_EUNSUPPORTED):
+        check(rc, "cimq_ideal_wide_plan")
     return tuple(f)
 
 

@@ -189,7 +189,7 @@ class Conv2dLSQCiM(_Conv2dQCiM):
         if self.adcbits == 0 and not first_step and self.ideal_ready(x):
             # the ideal ADC in steady state: both quantisers, the conv and its backward in the library
             out = cim_ideal_conv(x, self.weight, self.alpha_act, self.alpha_weight, self.stride, self.padding,
-                                 self.nbits_a, self.nbits_w)
+                                 self.nbits_a, self.nbits_w, self.wide_backward)
             return out if self.bias is None else out + self.bias.view(1, -1, 1, 1)  # F.conv2d's per-channel bias
         sa = grad_scale(self.alpha_act, 1.0 / math.sqrt(x.numel() * qp_a))            # lsq.py:547-548
         sw = grad_scale(self.alpha_weight, 1.0 / math.sqrt(self.weight.numel() * qp_w))  # lsq.py:553-554
@@ -233,12 +233,12 @@ class Conv2dLSQCiM(_Conv2dQCiM):
                 and x.dtype == torch.float32 and x.dim() == 4 and self.weight.is_cuda
                 and self.weight.dtype == torch.float32 and self.groups == 1 and tuple(self.dilation) == (1, 1)):
             return False
-        key = tuple(x.shape)
+        key = tuple(x.shape) + (bool(self.wide_backward),)
         hit = getattr(self, "_ideal_ok", None)
         if hit is None or hit[0] != key:
-            hit = self._ideal_ok = (key, ideal_conv_plan(*key, self.out_channels, *self.weight.shape[-2:],
+            hit = self._ideal_ok = (key, ideal_conv_plan(*x.shape, self.out_channels, *self.weight.shape[-2:],
                                                          tuple(self.stride), tuple(self.padding), self.nbits_a,
-                                                         self.nbits_w)[0])
+                                                         self.nbits_w, key[-1])[0])
         # (training answer, forward-only answer): a large layer trains on torch and evaluates in the library
         return hit[1][1 if inference_call(x, self.weight, self.alpha_act, self.alpha_weight) else 0]
 

@@ -35,7 +35,8 @@ FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 # MI355X, with no error raised.  Units written since are compiled with the feature off, so the compiler emits none; the
 # older units keep the flags their pinned instruction streams (tools/isa_diff.py) were taken with.  DESIGN.md section 1.
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-NO_PK_F32_UNITS = {"cimq_part_wide_bwd.hip", "cimq_part_c1w.hip", "cimq_part_ideal.hip"}
+NO_PK_F32_UNITS = {"cimq_part_wide_bwd.hip", "cimq_part_c1w.hip", "cimq_part_ideal.hip",
+                   "cimq_part_ideal_wide.hip"}
 
 
 def sources():

@@ -1466,10 +1466,13 @@ inline int ideal_chunk(int n16, F bytes) {
   return c * 16;
 }
 
-inline int ideal_plan(const cimq_ideal_desc* d, IdealG* out) {
+// (CIMQ_OPT_WIDE_BWD is a hint and moves nothing here; mac_gate = false is ideal_wide_plan's, whose pair the gate's
+// measurement does not describe)
+inline int ideal_plan(const cimq_ideal_desc* d, IdealG* out, bool mac_gate = true) {
   if (!d) return fail(CIMQ_EINVAL, "ideal: null descriptor");
   if (d->reserved != 0) return fail(CIMQ_EINVAL, "ideal: reserved must be 0");
-  if (d->options & ~CIMQ_OPT_INFERENCE) return fail(CIMQ_EINVAL, "ideal: unknown option bits 0x%x", d->options);
+  if (d->options & ~(CIMQ_OPT_INFERENCE | CIMQ_OPT_WIDE_BWD))
+    return fail(CIMQ_EINVAL, "ideal: unknown option bits 0x%x", d->options);
   IdealG g;
   memset(&g, 0, sizeof(g));
   g.B = d->batch; g.C = d->in_channels; g.H = d->in_h; g.W = d->in_w; g.O = d->out_channels;
@@ -1507,7 +1510,8 @@ inline int ideal_plan(const cimq_ideal_desc* d, IdealG* out) {
   // the measured gate: forward + backward beat the torch branch on every ResNet-20 shape
   // (0.6 G padded MACs at B = 256) and lost to it on every VGG-small shape (4.8 G and up); the forward alone won on all
   const long long macs = (long long)g.B * g.P * g.OP * g.Cp * g.ntap;
-  if (!g.inference && macs > kIdealTrainMacs)
+  // (IDEAL_GATE = 0 in a tuning build: tools/ideal_layer_bench.py times the plain backward above the gate)
+  if (mac_gate && tune("IDEAL_GATE", 1) && !g.inference && macs > kIdealTrainMacs)
     return fail(CIMQ_EUNSUPPORTED, "ideal: a training call of %lld M MACs stays on the vendor conv (above %lld M)",
                 macs >> 20, kIdealTrainMacs >> 20);
 
@@ -1565,6 +1569,72 @@ inline int ideal_plan(const cimq_ideal_desc* d, IdealG* out) {
 inline size_t ideal_wf_bytes(const IdealG& g) { return align256((size_t)g.nch * g.fks * g.nob * 64 * 16); }
 inline size_t ideal_wx_bytes(const IdealG& g) { return align256((size_t)g.ncb * g.xnoch * g.xks * 64 * 16); }
 inline int ideal_gx_blocks(const IdealG& g) { return g.B * g.xnrb * g.xncol * cdiv(g.ncb, kIdealCBX); }
+
+// ---------------------------------------------------------------------------------------
+// ideal_wide_plan: the large-layer backward pair (cimq_ideal_wide.hip) for a training descriptor that carries
+// CIMQ_OPT_WIDE_BWD.  On success g is ideal_plan's answer without the MAC gate, with noc / xnoch / xopitch / xks (the
+// wx fragments ideal_prep_w_kernel writes) and wslabs set for the pair; the forward's fields are ideal_plan's own.
+// ---------------------------------------------------------------------------------------
+constexpr int kIdealWideMinStages = 4;  // grad_w: 64-pixel stages a slab holds at least (18 accumulators written once)
+inline int ideal_wide_plan(const cimq_ideal_desc* d, IdealG* out, IdealWideG* vout) {
+  IdealG g;
+  if (const int rc = ideal_plan(d, &g, false)) return rc;
+  if (!(d->options & CIMQ_OPT_WIDE_BWD)) return fail(CIMQ_EUNSUPPORTED, "ideal wide: CIMQ_OPT_WIDE_BWD is not set");
+  if (g.inference) return fail(CIMQ_EUNSUPPORTED, "ideal wide: an inference descriptor has no backward");
+  if (g.KH != 3 || g.KW != 3 || g.SH != 1 || g.SW != 1 || g.PH != 1 || g.PW != 1)
+    return fail(CIMQ_EUNSUPPORTED, "ideal wide: 3 x 3, stride 1, pad 1 only (%d x %d, stride %d %d, pad %d %d)", g.KH,
+                g.KW, g.SH, g.SW, g.PH, g.PW);
+  if (g.W != 8 && g.W != 16 && g.W != 32) return fail(CIMQ_EUNSUPPORTED, "ideal wide: width %d not 8, 16 or 32", g.W);
+  if ((g.H * g.W) % 64) return fail(CIMQ_EUNSUPPORTED, "ideal wide: H * W = %d no multiple of 64", g.H * g.W);
+  if (g.C < 128 || g.C % 16) return fail(CIMQ_EUNSUPPORTED, "ideal wide: C = %d below 128 or no multiple of 16", g.C);
+  if (g.O % 32) return fail(CIMQ_EUNSUPPORTED, "ideal wide: O = %d no multiple of 32", g.O);
+  IdealWideG v;
+  memset(&v, 0, sizeof(v));
+  v.rows = 64 / g.W;
+  v.mt = g.P / 64;
+  // grad_x: the largest chunk of output channels (a multiple of 32) whose three planes meet the aim
+  const int npix = (v.rows + 2) * (g.W + 2);
+  int noc = g.O;
+  while (noc > 32 && (size_t)3 * npix * 16 * pitch16_odd(noc / 8) > kIdealLdsAim) noc -= 32;
+  g.xnoch = cdiv(g.O, noc);
+  g.noc = cdiv(cdiv(g.O, g.xnoch), 32) * 32;
+  g.xopitch = 8 * pitch16_odd(g.noc / 8);
+  g.xks = 9 * g.noc / 32;
+  v.xpitch = 2 * g.xopitch;
+  v.xplane = npix * v.xpitch;
+  v.nog = g.noc / 32;
+  v.xsteps = g.xnoch * g.xks;
+  v.gxblocks = g.B * v.mt * cdiv(g.ncb, kIdealWideCB);
+  v.xlds = 3 * v.xplane;
+  // grad_w: slabs as ideal_plan cuts them (two waves of the machine, at most 256), but kIdealWideMinStages a slab
+  v.wcpitch = 16 * pitch16_odd((v.rows + 2) * g.W / 8);
+  v.wunits = g.B * v.mt;
+  const long long wgs = (long long)cdiv(g.ncb, 2) * cdiv(g.nob, 4);
+  const long long want = std::max(1LL, std::min(256LL, 1024 / wgs));
+  v.wspc = std::max(cdiv(v.wunits, std::min<long long>(v.wunits, want)), std::min(v.wunits, kIdealWideMinStages));
+  g.wslabs = cdiv(v.wunits, v.wspc);
+  v.wnxi = 32 * (v.rows + 2) * (g.W / 8);
+  v.wlds = 3 * 32 * v.wcpitch + 3 * 64 * kIdealWideGPitch;
+  const size_t ldsmax = kLdsMax - 512;
+  if ((size_t)v.xlds > ldsmax || (size_t)v.wlds > ldsmax)
+    return fail(CIMQ_EUNSUPPORTED, "ideal wide: %d / %d bytes of LDS", v.xlds, v.wlds);
+  if ((long long)g.wslabs * g.OP * g.ntap * g.Cp >= (1LL << 31))
+    return fail(CIMQ_EUNSUPPORTED, "ideal wide: grad_w's slabs beyond 32-bit indexing");
+  *out = g;
+  *vout = v;
+  return CIMQ_OK;
+}
+// the plan the ideal entry points run d on: the wide pair where the hint is set and its plan holds (*wide = 1),
+// otherwise exactly ideal_plan's answer (refusals and their messages included)
+inline int ideal_route(const cimq_ideal_desc* d, IdealG* g, IdealWideG* v, int* wide) {
+  *wide = 0;
+  if (d && (d->options & CIMQ_OPT_WIDE_BWD) && !(d->options & CIMQ_OPT_INFERENCE) &&
+      ideal_wide_plan(d, g, v) == CIMQ_OK) {
+    *wide = 1;
+    return CIMQ_OK;
+  }
+  return ideal_plan(d, g);
+}
 
 template <typename K>
 inline int set_lds(K kernel, size_t bytes) {
@@ -1732,6 +1802,10 @@ int launch_c1(const Geo& g, const PlanC1& p, const uint8_t* ctx, const float* sw
 // cimq_part_c1w.hip: the wide first conv's recompute backward (c1w_plan, CIMQ_ROUTE_C1W) and its group fold
 int launch_c1w(const Geo& g, const PlanC1W& p, const uint8_t* ctx, const float* sw, const float* sa, const float* gout,
                const float* x, float* gx, uint8_t* ws, hipStream_t s);
+// cimq_part_ideal_wide.hip: cimq_ideal_backward's kernels under ideal_wide_plan (grad_x, grad_w slabs)
+int launch_ideal_wide_bwd(const IdealG& g, const IdealWideG& v, const float* x, const float* gout, const v4i* wx,
+                          const float* alpha_a, const float* alpha_w, float* gx, float* part_a, float* slab,
+                          hipStream_t s);
 // cimq_part_r6.hip: the recompute backward (CIMQ_ROUTE_R6); dbg: the parity hook's state words into st_dbg instead
 int launch_r6(const Geo& g, const PlanR6& p, const uint8_t* ctx, const float* sw, const float* sa, const float* sgn,
               const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, uint32_t* st_dbg = nullptr);

@@ -8,25 +8,9 @@
 //             the activation codes requantised from x; the LSQ step-size sums ride on both epilogues.
 // No atomics: every sum has a fixed order.  Included by cimq_part_ideal.hip; plans in cimq_host.h (ideal_plan).
 #pragma once
-#include "cimq_device.h"
+#include "cimq_ideal_dev.h"
 
 namespace cimq {
-
-__device__ inline float ideal_code(float v, float s, float qn, float qp) {
-  return rintf(fminf(fmaxf(v / s, qn), qp));  // (a non-finite v is outside the contract)
-}
-
-// the block's sum in every thread: a wave butterfly, then the waves' sums added in wave order (red: one float a wave)
-__device__ inline float ideal_block_sum(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  float s = red[0];
-  for (int i = 1; i < nw; ++i) s += red[i];
-  return s;
-}
 
 // ---------------------------------------------------------------------------------------
 // weight side, once per forward: the codes as int8 A-fragments of the forward

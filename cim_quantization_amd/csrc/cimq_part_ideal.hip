@@ -12,14 +12,24 @@ int gw_tail_blocks(const IdealG& g) {
   return (int)std::max(1LL, std::min<long long>(((long long)g.O * g.C * g.ntap + 255) / 256, kIdealTailBlocks));
 }
 
+// what a descriptor runs on: ideal_plan's kernels, or under CIMQ_OPT_WIDE_BWD where ideal_wide_plan holds the wide
+// backward pair (cimq_part_ideal_wide.hip) behind the same forward
+struct IdealRoute {
+  IdealG g;
+  IdealWideG v;
+  int wide;
+  int gx_blocks() const { return wide ? v.gxblocks : ideal_gx_blocks(g); }
+};
+int route(const cimq_ideal_desc* d, IdealRoute* r) { return ideal_route(d, &r->g, &r->v, &r->wide); }
+
 // ws: act-LSQ partials | weight-LSQ partials | grad_w slabs
 struct IdealWs {
   size_t part_a, part_w, slab, total;
 };
-IdealWs ideal_ws(const IdealG& g) {
+IdealWs ideal_ws(const IdealG& g, int gx_blocks) {
   IdealWs w;
   w.part_a = 0;
-  w.part_w = align256((size_t)ideal_gx_blocks(g) * 4);
+  w.part_w = align256((size_t)gx_blocks * 4);
   w.slab = w.part_w + align256((size_t)kIdealTailBlocks * 4);
   w.total = w.slab + align256((size_t)g.wslabs * g.OP * g.ntap * g.Cp * 4);
   return w;
@@ -48,8 +58,9 @@ int cimq_ideal_abi(void) { return 1; }
 int cimq_ideal_plan(const cimq_ideal_desc* d, int out[5]) {
   if (!out) return fail(CIMQ_EINVAL, "ideal_plan: null out");
   for (int i = 0; i < 5; ++i) out[i] = 0;
-  IdealG g;
-  CIMQ_TRY(ideal_plan(d, &g));
+  IdealRoute r;
+  CIMQ_TRY(route(d, &r));
+  const IdealG& g = r.g;
   out[0] = 1;
   out[1] = g.mt;
   out[2] = g.nch;
@@ -59,18 +70,20 @@ int cimq_ideal_plan(const cimq_ideal_desc* d, int out[5]) {
 }
 
 int cimq_ideal_sizes(const cimq_ideal_desc* d, size_t* ctx_bytes, size_t* ws_bytes) {
-  IdealG g;
-  CIMQ_TRY(ideal_plan(d, &g));
+  IdealRoute r;
+  CIMQ_TRY(route(d, &r));
+  const IdealG& g = r.g;
   if (ctx_bytes) *ctx_bytes = ideal_wf_bytes(g) + (g.inference ? 0 : ideal_wx_bytes(g));
-  if (ws_bytes) *ws_bytes = ideal_ws(g).total;
+  if (ws_bytes) *ws_bytes = ideal_ws(g, r.gx_blocks()).total;
   return CIMQ_OK;
 }
 
 int cimq_ideal_forward(const cimq_ideal_desc* d, const float* x, const float* weight, const float* alpha_act,
                        const float* alpha_weight, float* out, void* ctx, void* ws, void* stream) {
   (void)ws;
-  IdealG g;
-  CIMQ_TRY(ideal_plan(d, &g));
+  IdealRoute r;
+  CIMQ_TRY(route(d, &r));
+  const IdealG& g = r.g;
   if (!x || !weight || !alpha_act || !alpha_weight || !out || !ctx)
     return fail(CIMQ_EINVAL, "ideal_forward: null pointer");
   hipStream_t st = (hipStream_t)stream;
@@ -88,36 +101,41 @@ int cimq_ideal_forward(const cimq_ideal_desc* d, const float* x, const float* we
 int cimq_ideal_backward(const cimq_ideal_desc* d, const float* x, const float* weight, const float* alpha_act,
                         const float* alpha_weight, const float* grad_out, const void* ctx, float* grad_x,
                         float* grad_w, float* grad_alpha_act, float* grad_alpha_weight, void* ws, void* stream) {
-  IdealG g;
-  CIMQ_TRY(ideal_plan(d, &g));
+  IdealRoute r;
+  CIMQ_TRY(route(d, &r));
+  const IdealG& g = r.g;
   if (g.inference) return fail(CIMQ_EINVAL, "ideal_backward: an inference descriptor has no backward");
   if (!x || !weight || !alpha_act || !alpha_weight || !grad_out || !ctx || !grad_x || !grad_w || !grad_alpha_act ||
       !grad_alpha_weight || !ws)
     return fail(CIMQ_EINVAL, "ideal_backward: null pointer");
   hipStream_t st = (hipStream_t)stream;
-  const IdealWs W = ideal_ws(g);
+  const IdealWs W = ideal_ws(g, r.gx_blocks());
   uint8_t* wsb = reinterpret_cast<uint8_t*>(ws);
   float* part_a = reinterpret_cast<float*>(wsb + W.part_a);
   float* part_w = reinterpret_cast<float*>(wsb + W.part_w);
   float* slab = reinterpret_cast<float*>(wsb + W.slab);
   const v4i* wx = reinterpret_cast<const v4i*>(reinterpret_cast<const uint8_t*>(ctx) + ideal_wf_bytes(g));
 
-  CIMQ_TRY(set_lds(cim_ideal_gx_kernel, g.xlds));
-  hipLaunchKernelGGL(cim_ideal_gx_kernel, dim3((unsigned)(g.B * g.xnrb * g.xncol), (unsigned)cdiv(g.ncb, kIdealCBX)),
-                     dim3(256), g.xlds, st, g, x, grad_out, wx, alpha_act, alpha_weight, grad_x, part_a);
-  CIMQ_TRY(check_hip("cim_ideal_gx"));
+  if (r.wide) {
+    CIMQ_TRY(launch_ideal_wide_bwd(g, r.v, x, grad_out, wx, alpha_act, alpha_weight, grad_x, part_a, slab, st));
+  } else {
+    CIMQ_TRY(set_lds(cim_ideal_gx_kernel, g.xlds));
+    hipLaunchKernelGGL(cim_ideal_gx_kernel, dim3((unsigned)(g.B * g.xnrb * g.xncol), (unsigned)cdiv(g.ncb, kIdealCBX)),
+                       dim3(256), g.xlds, st, g, x, grad_out, wx, alpha_act, alpha_weight, grad_x, part_a);
+    CIMQ_TRY(check_hip("cim_ideal_gx"));
 
-  CIMQ_TRY(set_lds(cim_ideal_gw_kernel, g.wlds));
-  hipLaunchKernelGGL(cim_ideal_gw_kernel,
-                     dim3((unsigned)g.wslabs, (unsigned)(g.ncb * g.wntg), (unsigned)cdiv(g.nob, kIdealOBG)), dim3(256),
-                     g.wlds, st, g, x, grad_out, alpha_act, slab);
-  CIMQ_TRY(check_hip("cim_ideal_gw"));
+    CIMQ_TRY(set_lds(cim_ideal_gw_kernel, g.wlds));
+    hipLaunchKernelGGL(cim_ideal_gw_kernel,
+                       dim3((unsigned)g.wslabs, (unsigned)(g.ncb * g.wntg), (unsigned)cdiv(g.nob, kIdealOBG)),
+                       dim3(256), g.wlds, st, g, x, grad_out, alpha_act, slab);
+    CIMQ_TRY(check_hip("cim_ideal_gw"));
+  }
 
   const int ntb = gw_tail_blocks(g);
   hipLaunchKernelGGL(ideal_gw_finish_kernel, dim3(ntb), dim3(256), 0, st, g, weight, slab, alpha_act, alpha_weight,
                      grad_w, part_w);
   CIMQ_TRY(check_hip("ideal_gw_finish"));
-  hipLaunchKernelGGL(ideal_alpha_finish_kernel, dim3(1), dim3(256), 0, st, g, ideal_gx_blocks(g), part_a, ntb, part_w,
+  hipLaunchKernelGGL(ideal_alpha_finish_kernel, dim3(1), dim3(256), 0, st, g, r.gx_blocks(), part_a, ntb, part_w,
                      grad_alpha_act, grad_alpha_weight);
   return check_hip("ideal_alpha_finish");
 }

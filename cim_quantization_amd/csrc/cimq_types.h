@@ -377,4 +377,17 @@ struct IdealG {
   int wrb, wspr, wnb, wupc, wslabs, wntg, wxrows, wxw, wxplane, wgpitch, wlds;
 };
 
+// The large-layer backward pair of the ideal-ADC conv (cimq_ideal_wide.hip; ideal_wide_plan, CIMQ_OPT_WIDE_BWD):
+// 3 x 3, stride 1, pad 1, W in {8, 16, 32}, whole-row 64-pixel tiles.  Passed beside IdealG, whose noc / xnoch / xks
+// (the wx fragments of ideal_prep_w_kernel) and wslabs the plan fills for this pair.
+constexpr int kIdealWideCB = 8;        // grad_x: 16-channel input blocks per workgroup
+constexpr int kIdealWideGPitch = 144;  // grad_w: bytes per output channel of a grad_out plane (64 bf16, odd in 16 B)
+struct IdealWideG {
+  int rows, mt;                       // rows of a 64-pixel tile (64 / W), tiles per image
+  // grad_x: the patch [rows + 2][W + 2][xpitch bytes] per plane, nog 32-deep k-steps per tap, xsteps k-steps in all
+  int xpitch, xplane, nog, xsteps, gxblocks, xlds;
+  // grad_w: code planes [3][32][wcpitch bytes], wspc 64-pixel stages per slab of wunits = B * mt, wnxi x items a stage
+  int wcpitch, wspc, wunits, wnxi, wlds;
+};
+
 }  // namespace cimq

@@ -1297,15 +1297,17 @@ def qconv2d(x_q, act_scale, w_q, w_scale, bias=None, stride=(1, 1), padding=(0, 
 _IDEAL_PLANS = {}
 
 
-def ideal_conv_plan(B, C, H, W, O, KH, KW, stride, padding, nbits_a, nbits_w):
+def ideal_conv_plan(B, C, H, W, O, KH, KW, stride, padding, nbits_a, nbits_w, wide_backward=False):
     """``((ok, ok under CIMQ_OPT_INFERENCE), training descriptor, inference descriptor, ctx bytes, ws bytes, inference
     ctx bytes)`` of the ideal-ADC conv for one shape, asked of the library once (cimq_ideal_plan / cimq_ideal_sizes).
-    The two answers differ on large layers: their training call stays on torch, their no-grad forward does not."""
-    key = (B, C, H, W, O, KH, KW, tuple(stride), tuple(padding), nbits_a, nbits_w)
+    The two answers differ on large layers: their training call stays on torch, their no-grad forward does not --
+    unless ``wide_backward`` (CIMQ_OPT_WIDE_BWD on the training descriptor) puts it on the large-layer backward pair."""
+    key = (B, C, H, W, O, KH, KW, tuple(stride), tuple(padding), nbits_a, nbits_w, bool(wide_backward))
     p = _IDEAL_PLANS.get(key)
     if p is None:
         args = (B, C, H, W, O, KH, KW, stride, padding, nbits_w, nbits_a)
-        d, di = _lib.make_ideal_desc(*args), _lib.make_ideal_desc(*args, options=_lib.CIMQ_OPT_INFERENCE)
+        d = _lib.make_ideal_desc(*args, options=_lib.CIMQ_OPT_WIDE_BWD if wide_backward else 0)
+        di = _lib.make_ideal_desc(*args, options=_lib.CIMQ_OPT_INFERENCE)
         ok, oki = bool(_lib.ideal_plan(d)[0]), bool(_lib.ideal_plan(di)[0])
         p = ((ok, oki), d, di) + (_lib.ideal_sizes(d) if ok else (0, 0)) + (_lib.ideal_sizes(di)[:1] if oki else (0,))
         _IDEAL_PLANS[key] = p
@@ -1316,7 +1318,7 @@ class _IdealConv(torch.autograd.Function):
     """Conv2dLSQCiM's adcbits = 0 branch in two library calls (cimq_ideal_forward / cimq_ideal_backward)."""
 
     @staticmethod
-    def forward(ctx, x, weight, alpha_act, alpha_weight, stride, padding, nbits_a, nbits_w, train):
+    def forward(ctx, x, weight, alpha_act, alpha_weight, stride, padding, nbits_a, nbits_w, train, wide):
         _require_device(x, weight, alpha_act, alpha_weight)
         dev = x.device
         xc, wc = _f32(x, dev), _f32(weight, dev)
@@ -1325,7 +1327,7 @@ class _IdealConv(torch.autograd.Function):
         O, C2, KH, KW = wc.shape
         if C2 != C:
             raise ValueError("cim_ideal_conv: weight does not match x's channels (groups must be 1)")
-        ok, d, di, cb, wsb, cbi = ideal_conv_plan(B, C, H, W, O, KH, KW, stride, padding, nbits_a, nbits_w)
+        ok, d, di, cb, wsb, cbi = ideal_conv_plan(B, C, H, W, O, KH, KW, stride, padding, nbits_a, nbits_w, wide)
         if not ok[0 if train else 1]:
             _lib.ideal_plan(d if train else di)  # (the reason, again)
             raise _lib.CimqError("cim_ideal_conv: the library does not take this shape (cimq_ideal_plan): " +
@@ -1353,16 +1355,19 @@ class _IdealConv(torch.autograd.Function):
                                                    gs.data_ptr(), gs.data_ptr() + 4, ws.data_ptr(), _stream()),
                    "cimq_ideal_backward")
         a_shape, s_shape = ctx.shapes
-        return gx, gw, gs[0:1].reshape(a_shape), gs[1:2].reshape(s_shape), None, None, None, None, None
+        return gx, gw, gs[0:1].reshape(a_shape), gs[1:2].reshape(s_shape), None, None, None, None, None, None
 
 
-def cim_ideal_conv(x, weight, alpha_act, alpha_weight, stride=(1, 1), padding=(0, 0), nbits_a=8, nbits_w=8):
+def cim_ideal_conv(x, weight, alpha_act, alpha_weight, stride=(1, 1), padding=(0, 0), nbits_a=8, nbits_w=8,
+                   wide_backward=False):
     """Conv2dLSQCiM(adcbits=0) on libcimq: ``conv(code_a, code_w) * sa * sw`` with both LSQ quantisers fused into the
     int8 MFMA forward, and its autograd (grad_x, grad_w and both step-size gradients) on the bf16 MFMA backward
     kernels.  ``x`` [B, C, H, W] and ``weight`` [O, C, KH, KW] are the raw fp32 tensors, ``alpha_act`` /
     ``alpha_weight`` the step-size parameters.  Under no-grad (or with no input requiring a gradient) the call is the
     forward-only descriptor and keeps nothing.  Non-finite inputs are outside its contract (an int8 code cannot carry
-    a NaN).  Raises where cimq_ideal_plan refuses the shape; gradients are returned, never accumulated in place."""
+    a NaN).  Raises where cimq_ideal_plan refuses the shape; gradients are returned, never accumulated in place.
+    ``wide_backward`` is CIMQ_OPT_WIDE_BWD on the training descriptor: a hint that moves the backward of a large 3 x 3
+    stride-1 layer (cimq_ideal_wide_plan) onto the whole-row-tile kernel pair and changes nothing elsewhere."""
     train = not inference_call(x, weight, alpha_act, alpha_weight)
     return _IdealConv.apply(x, weight, alpha_act, alpha_weight, _pair(stride), _pair(padding), int(nbits_a),
-                            int(nbits_w), train)
+                            int(nbits_w), train, bool(wide_backward))

@@ -59,7 +59,9 @@ def get_base_parser():
     p.add_argument("--wide-backward", action="store_true",
                    help="Conv2dLSQCiM.wide_backward on every CiM conv: the wide layers (3x3 from 128 input channels "
                         "up) train on the channel-chunked compact-state backward, and a w8a8 first conv of 32 .. 512 "
-                        "output channels on the multi-block recompute backward, where the library's plan takes them")
+                        "output channels on the multi-block recompute backward, where the library's plan takes them; "
+                        "with adcbits 0 (the ideal ADC) the 3x3 stride-1 layers from 128 input channels up train on "
+                        "the library's whole-row-tile backward pair instead of the vendor conv")
     return p
 
 

@@ -770,7 +770,7 @@ typedef struct cimq_ideal_desc {
   int32_t out_channels, kernel_h, kernel_w;
   int32_t stride_h, stride_w, pad_h, pad_w;
   int32_t bits_w, bits_a;
-  int32_t options;  /* 0 or CIMQ_OPT_INFERENCE */
+  int32_t options;  /* CIMQ_OPT_INFERENCE, CIMQ_OPT_WIDE_BWD (a hint, below) or 0 */
   int32_t reserved; /* must be 0 */
 } cimq_ideal_desc;
 
@@ -799,6 +799,24 @@ int cimq_ideal_forward(const cimq_ideal_desc* d, const float* x, const float* we
 int cimq_ideal_backward(const cimq_ideal_desc* d, const float* x, const float* weight, const float* alpha_act,
                         const float* alpha_weight, const float* grad_out, const void* ctx, float* grad_x,
                         float* grad_w, float* grad_alpha_act, float* grad_alpha_weight, void* ws, void* stream);
+
+/* The large-layer backward of the ideal-ADC conv.  cimq_ideal_wide_abi() == 1 where cimq_ideal_desc.options takes
+ * CIMQ_OPT_WIDE_BWD.  The bit is a hint, as on the module entry points: where cimq_ideal_wide_plan holds, the bound on
+ * multiply-accumulates of a training descriptor does not apply, cimq_ideal_forward runs what it runs without the bit
+ * and cimq_ideal_backward runs cim_ideal_gx_wide_kernel + cim_ideal_gw_wide_kernel (whole-row 64-pixel tiles, aligned
+ * 16-byte LDS operand reads, no per-lane predicate) before the same two finishing kernels; cimq_ideal_sizes answers for
+ * the descriptor as given (ctx and ws may differ from the plain descriptor's).  Everywhere else, and together with
+ * CIMQ_OPT_INFERENCE, the descriptor answers exactly as it does without the bit.  Same sums in a fixed order: two
+ * calls give the same bits; the order differs from the plain backward's, so the two agree to rounding only. */
+int cimq_ideal_wide_abi(void);
+
+/* Host query, no device work.  out[0] = 1 where d -- a training descriptor carrying CIMQ_OPT_WIDE_BWD -- runs the pair
+ * (0 with CIMQ_EUNSUPPORTED and the reason in cimq_last_error() otherwise), out[1] = grad_x workgroups per image,
+ * out[2] = grad_x output-channel chunks, out[3] = grad_w 64-pixel stages per slab, out[4] = grad_w slabs, out[5] = the
+ * wider of the two kernels' LDS bytes.  Admitted: all cimq_ideal_plan admits but for the multiply-accumulate bound,
+ * and 3 x 3, stride 1, pad 1, W in {8, 16, 32}, H * W a multiple of 64, C >= 128 and a multiple of 16, O a multiple
+ * of 32. */
+int cimq_ideal_wide_plan(const cimq_ideal_desc* d, int out[6]);
 
 #ifdef __cplusplus
 }

@@ -7,9 +7,12 @@ For each shape: forward + backward, and the no-grad forward, each captured as on
 ``--steps`` replays between two HIP events after a warm-up (w4a4_layer_bench._graph_ms); the two sides alternate over
 ``--runs`` runs in one session.  Per row the runs, their medians and spreads (max - min) and ``faster_*``: the
 library's median is below torch's by more than the larger of the two spreads -- the gate a shape has to pass to stay
-in ideal_plan.
+in ideal_plan.  ``--wide-backward`` adds a third side to the alternation, the library with ``m.wide_backward = True``
+(CIMQ_OPT_WIDE_BWD: the large-layer backward pair where cimq_ideal_wide_plan holds), and ``faster_step_wide_vs_torch``
+/ ``faster_step_wide_vs_lib`` by the same rule; ``--nets`` keeps the rows of the named networks.
 
     python tools/ideal_layer_bench.py --out profiles/ideal/summary.json
+    python tools/ideal_layer_bench.py --wide-backward --nets vggsmall --out profiles/ideal_wide/summary.json
 """
 from __future__ import annotations
 
@@ -49,6 +52,8 @@ def main(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--wide-backward", action="store_true", help="time wide_backward = True as a third side")
+    ap.add_argument("--nets", nargs="+", default=["resnet20", "vggsmall"])
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
     import torch
@@ -59,7 +64,8 @@ def main(argv=None):
         raise SystemExit("ideal_layer_bench measures on a GPU; none found")
     dev = torch.device("cuda", 0)
     rows = []
-    for net, c, o, h, s, bits in shapes(args.bits):
+    sides = [("torch", False, False), ("lib", True, False)] + ([("wide", True, True)] if args.wide_backward else [])
+    for net, c, o, h, s, bits in [r for r in shapes(args.bits) if r[0] in args.nets]:
         torch.manual_seed(11)
         m = my_nn.Conv2dLSQCiM(c, o, 3, s, 1, bias=False, nbits_w=bits, nbits_a=bits, adcbits=0)
         torch.nn.init.kaiming_normal_(m.weight)
@@ -79,17 +85,30 @@ def main(argv=None):
                 m(x)
 
         us = {(k, on): [] for k in ("step", "eval") for on in (False, True)}
-        ready = None
+        us[("step", "wide")] = []
+        ready = ready_wide = None
         for _ in range(args.runs):
-            for on in (False, True):
-                m.fused = on
+            for side, on, wide in sides:
+                m.fused, m.wide_backward = on, wide
+                if side == "wide":  # (the hint moves the backward alone: the no-grad forward is the lib side's)
+                    ready_wide = bool(m.ideal_ready(xg))
+                    us[("step", "wide")].append(1e3 * _graph_ms(step, args.steps, args.warmup))
+                    continue
                 if on:
                     ready = bool(m.ideal_ready(x))
                 us[("step", on)].append(1e3 * _graph_ms(step, args.steps, args.warmup))
                 us[("eval", on)].append(1e3 * _graph_ms(evalf, args.steps, args.warmup))
+        us = {k: v for k, v in us.items() if v}
         med = {k: statistics.median(v) for k, v in us.items()}
         spread = {k: max(v) - min(v) for k, v in us.items()}
         row = {"net": net, "bits": bits, "C": c, "O": o, "H": h, "stride": s, "ideal_ready": ready}
+        if args.wide_backward:
+            k = ("step", "wide")
+            row.update({"ideal_ready_wide": ready_wide, "us_step_wide": us[k], "median_step_wide": med[k],
+                        "spread_step_wide": spread[k]})
+            for other, name in ((False, "torch"), (True, "lib")):
+                row[f"faster_step_wide_vs_{name}"] = med[k] < med[("step", other)] - max(spread[k],
+                                                                                         spread[("step", other)])
         for k in ("step", "eval"):
             row.update({f"us_{k}_torch": us[(k, False)], f"us_{k}_lib": us[(k, True)],
                         f"median_{k}_torch": med[(k, False)], f"median_{k}_lib": med[(k, True)],
@@ -99,7 +118,10 @@ def main(argv=None):
         print(f"{net} w{bits}a{bits} {c:3d}->{o:3d} {h:2d}x{h:<2d} s{s} ready {ready}  fwd+bwd torch "
               f"{med[('step', False)]:8.1f} us (+-{spread[('step', False)]:.1f}) lib {med[('step', True)]:8.1f} us "
               f"(+-{spread[('step', True)]:.1f}) faster {row['faster_step']}  eval torch {med[('eval', False)]:8.1f} us "
-              f"lib {med[('eval', True)]:8.1f} us faster {row['faster_eval']}", flush=True)
+              f"lib {med[('eval', True)]:8.1f} us faster {row['faster_eval']}" +
+              (f"  fwd+bwd wide {med[('step', 'wide')]:8.1f} us (+-{spread[('step', 'wide')]:.1f}) ready {ready_wide} "
+               f"faster than torch {row['faster_step_wide_vs_torch']} lib {row['faster_step_wide_vs_lib']}"
+               if args.wide_backward else ""), flush=True)
         del m, x, xg, g
         torch.cuda.empty_cache()
     out = {"batch": args.batch, "adc": 0, "steps": args.steps, "warmup": args.warmup, "runs": args.runs,
