@@ -113,6 +113,8 @@ EXPORTED_SYMBOLS = (
     "cimq_ideal_backward",
     "cimq_ideal_wide_abi",
     "cimq_ideal_wide_plan",
+    "cimq_ideal_wide_fwd_abi",
+    "cimq_ideal_wide_fwd_plan",
 )
 
 KERNEL_IDS = {"fwd": 1, "bwd_gx": 2, "bwd_gw": 3, "prep_act": 4, "fwd_v7": 5, "gx_v8": 6, "gw_v7": 7, "bwd_fused": 8}
@@ -411,6 +413,11 @@ def _bind(lib):
         lib.cimq_ideal_wide_abi.argtypes = []
         lib.cimq_ideal_wide_plan.restype = ctypes.c_int
         lib.cimq_ideal_wide_plan.argtypes = [ctypes.POINTER(IdealDesc), ctypes.POINTER(ctypes.c_int)]
+    if hasattr(lib, "cimq_ideal_wide_fwd_abi"):
+        lib.cimq_ideal_wide_fwd_abi.restype = ctypes.c_int
+        lib.cimq_ideal_wide_fwd_abi.argtypes = []
+        lib.cimq_ideal_wide_fwd_plan.restype = ctypes.c_int
+        lib.cimq_ideal_wide_fwd_plan.argtypes = [ctypes.POINTER(IdealDesc), ctypes.POINTER(ctypes.c_int)]
     lib.cimq_profile_start.restype = ctypes.c_int
     lib.cimq_profile_start.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.cimq_profile_read.restype = ctypes.c_int
@@ -554,6 +561,17 @@ def ideal_wide_plan(desc: IdealDesc):
     rc = load().cimq_ideal_wide_plan(ctypes.byref(desc), f)
     if rc not in (0, CIMQ_EUNSUPPORTED):
         check(rc, "cimq_ideal_wide_plan")
+    return tuple(f)
+
+
+def ideal_wide_fwd_plan(desc: IdealDesc):
+    """(ok, 64-pixel tiles per image, channel chunks, output groups per workgroup, workgroups in blockIdx.y, LDS bytes)
+    of the large-layer forward for ``desc`` -- cimq_ideal_wide_fwd_plan; off its plan ok = 0 (the reason in
+    cimq_last_error(), starting "ideal wide fwd:"), a malformed descriptor raises."""
+    f = (ctypes.c_int * 6)()
+    rc = load().cimq_ideal_wide_fwd_plan(ctypes.byref(desc), f)
+    if rc not in (0, CIMQ_EUNSUPPORTED):
+        check(rc, "cimq_ideal_wide_fwd_plan")
     return tuple(f)
 
 

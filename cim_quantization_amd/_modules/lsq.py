@@ -93,7 +93,9 @@ class Conv2dLSQCiM(_Conv2dQCiM):
         # CIMQ_OPT_WIDE_BWD: a wide layer (3x3 from 128 input channels up) whose plan the library accepts
         # (cimq_module_wide_bwd_plan) trains from compact state words on the channel-chunked backward kernels
         # instead of the general ones, and a w8a8 first conv of 32 .. 512 output channels (cimq_module_c1w_plan) on
-        # the multi-block recompute backward; a hint like recompute_psum, without effect on any other layer
+        # the multi-block recompute backward; a hint like recompute_psum, without effect on any other layer.  With
+        # adcbits 0 it is the hint for the ideal-ADC path's large-layer kernels: the backward pair
+        # (cimq_ideal_wide_plan) and, in training and no-grad calls alike, the forward (cimq_ideal_wide_fwd_plan)
         self.wide_backward = False
         self._wprep = None        # functional.prepare_weights: the next forward's weight side, computed ahead
         self._inf_prep = None     # functional.inference_weights: the weight side the no-grad forwards share

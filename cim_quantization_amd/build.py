@@ -36,7 +36,7 @@ FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=
 # older units keep the flags their pinned instruction streams (tools/isa_diff.py) were taken with.  DESIGN.md section 1.
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 NO_PK_F32_UNITS = {"cimq_part_wide_bwd.hip", "cimq_part_c1w.hip", "cimq_part_ideal.hip",
-                   "cimq_part_ideal_wide.hip"}
+                   "cimq_part_ideal_wide.hip", "cimq_part_ideal_wide_fwd.hip"}
 
 
 def sources():

@@ -1636,6 +1636,46 @@ inline int ideal_route(const cimq_ideal_desc* d, IdealG* g, IdealWideG* v, int* 
   return ideal_plan(d, g);
 }
 
+// ---------------------------------------------------------------------------------------
+// ideal_wide_fwd_plan: the large-layer forward (cimq_ideal_wide_fwd.hip) for a descriptor -- training or inference --
+// that carries CIMQ_OPT_WIDE_BWD.  g is what ideal_route answered for d and is not changed: the kernel runs on
+// ideal_plan's patch (frows x fwp x fpitch, nch chunks of ncx channels) and on the wf fragments as they are.
+// ---------------------------------------------------------------------------------------
+inline int ideal_wide_fwd_plan(const cimq_ideal_desc* d, const IdealG& g, IdealWideFwdG* vout) {
+  if (!(d->options & CIMQ_OPT_WIDE_BWD))
+    return fail(CIMQ_EUNSUPPORTED, "ideal wide fwd: CIMQ_OPT_WIDE_BWD is not set");
+  if (g.KH != 3 || g.KW != 3 || g.SH != 1 || g.SW != 1 || g.PH != 1 || g.PW != 1)
+    return fail(CIMQ_EUNSUPPORTED, "ideal wide fwd: 3 x 3, stride 1, pad 1 only (%d x %d, stride %d %d, pad %d %d)",
+                g.KH, g.KW, g.SH, g.SW, g.PH, g.PW);
+  if (g.W != 8 && g.W != 16 && g.W != 32)
+    return fail(CIMQ_EUNSUPPORTED, "ideal wide fwd: width %d not 8, 16 or 32", g.W);
+  if ((g.H * g.W) % 64) return fail(CIMQ_EUNSUPPORTED, "ideal wide fwd: H * W = %d no multiple of 64", g.H * g.W);
+  if (g.C < 128 || g.C % 16)
+    return fail(CIMQ_EUNSUPPORTED, "ideal wide fwd: C = %d below 128 or no multiple of 16", g.C);
+  if (g.O % 32) return fail(CIMQ_EUNSUPPORTED, "ideal wide fwd: O = %d no multiple of 32", g.O);
+  // (no harness network has an a8 layer in this class; it stays on cim_ideal_fwd_kernel)
+  if (g.split) return fail(CIMQ_EUNSUPPORTED, "ideal wide fwd: bits_a = 8 needs the two-nibble accumulation");
+  IdealWideFwdG v;
+  memset(&v, 0, sizeof(v));
+  v.rows = 64 / g.W;
+  v.mt = g.P / 64;
+  if (g.frows != v.rows + 2 || g.fwp != g.W + 2 || g.mt != v.mt)
+    return fail(CIMQ_EUNSUPPORTED, "ideal wide fwd: the patch is not a whole-row tile's (%d x %d)", g.frows, g.fwp);
+  // 16 output blocks a group where O has them (a wave: all 64 pixels x 4 blocks), 8 below (a wave: 32 pixels x 4 blocks)
+  v.pb = g.nob >= 16 ? 4 : 2;
+  v.span = v.pb * kIdealWideFwdOB;
+  v.ngroups = cdiv(g.nob, v.span);
+  // blockIdx.y splits the groups only to fill the machine (about 1024 workgroups, ideal_plan's rule for its slabs), and
+  // never below kIdealWideFwdMinGroups a workgroup: each one stages -- reads and divides -- the tile's whole patch
+  const long long tiles = (long long)g.B * v.mt;
+  const long long want = std::max(1LL, 1024 / tiles);
+  v.gpw = std::max(cdiv(v.ngroups, (int)std::min<long long>(v.ngroups, want)),
+                   std::min(v.ngroups, kIdealWideFwdMinGroups));
+  v.ny = cdiv(v.ngroups, v.gpw);
+  *vout = v;
+  return CIMQ_OK;
+}
+
 template <typename K>
 inline int set_lds(K kernel, size_t bytes) {
   if (bytes > 64 * 1024) {
@@ -1806,6 +1846,9 @@ int launch_c1w(const Geo& g, const PlanC1W& p, const uint8_t* ctx, const float* 
 int launch_ideal_wide_bwd(const IdealG& g, const IdealWideG& v, const float* x, const float* gout, const v4i* wx,
                           const float* alpha_a, const float* alpha_w, float* gx, float* part_a, float* slab,
                           hipStream_t s);
+// cimq_part_ideal_wide_fwd.hip: cimq_ideal_forward's conv under ideal_wide_fwd_plan
+int launch_ideal_wide_fwd(const IdealG& g, const IdealWideFwdG& v, const float* x, const v4i* wf, const float* alpha_a,
+                          const float* alpha_w, float* out, hipStream_t s);
 // cimq_part_r6.hip: the recompute backward (CIMQ_ROUTE_R6); dbg: the parity hook's state words into st_dbg instead
 int launch_r6(const Geo& g, const PlanR6& p, const uint8_t* ctx, const float* sw, const float* sa, const float* sgn,
               const float* gout, const float* x, float* gx, uint8_t* ws, hipStream_t s, uint32_t* st_dbg = nullptr);

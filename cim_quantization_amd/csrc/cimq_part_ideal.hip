@@ -13,7 +13,8 @@ int gw_tail_blocks(const IdealG& g) {
 }
 
 // what a descriptor runs on: ideal_plan's kernels, or under CIMQ_OPT_WIDE_BWD where ideal_wide_plan holds the wide
-// backward pair (cimq_part_ideal_wide.hip) behind the same forward
+// backward pair (cimq_part_ideal_wide.hip); the forward of either is cim_ideal_fwd_kernel, or under the same hint where
+// ideal_wide_fwd_plan holds the large-layer forward (cimq_part_ideal_wide_fwd.hip) on the same plan and fragments
 struct IdealRoute {
   IdealG g;
   IdealWideG v;
@@ -93,6 +94,10 @@ int cimq_ideal_forward(const cimq_ideal_desc* d, const float* x, const float* we
   hipLaunchKernelGGL(ideal_prep_w_kernel, dim3((unsigned)std::min<long long>((nfrag + 255) / 256, 4096)), dim3(256), 0,
                      st, g, weight, alpha_weight, wf, wx);
   CIMQ_TRY(check_hip("ideal_prep_w"));
+  // the hint, in training and in inference descriptors alike: the large-layer forward where its plan holds
+  IdealWideFwdG fv;
+  if ((d->options & CIMQ_OPT_WIDE_BWD) && ideal_wide_fwd_plan(d, g, &fv) == CIMQ_OK)
+    return launch_ideal_wide_fwd(g, fv, x, wf, alpha_act, alpha_weight, out, st);
   if (g.nobw == 4) return launch_fwd<4>(g, x, wf, alpha_act, alpha_weight, out, st);
   if (g.nobw == 2) return launch_fwd<2>(g, x, wf, alpha_act, alpha_weight, out, st);
   return launch_fwd<1>(g, x, wf, alpha_act, alpha_weight, out, st);

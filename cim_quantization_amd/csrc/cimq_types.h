@@ -390,4 +390,16 @@ struct IdealWideG {
   int wcpitch, wspc, wunits, wnxi, wlds;
 };
 
+// The large-layer forward of the ideal-ADC conv (cimq_ideal_wide_fwd.hip; ideal_wide_fwd_plan, CIMQ_OPT_WIDE_BWD): the
+// same shape class, bits_a <= 7.  Passed beside IdealG, whose forward fields (the patch, the chunks, the wf fragments)
+// it reads as ideal_plan fills them.  A wave owns pb pixel blocks x kIdealWideFwdOB output blocks; the four waves of a
+// workgroup cover 64 pixels x span output blocks, one output group.
+constexpr int kIdealWideFwdOB = 4;         // 16-channel output blocks per wave
+constexpr int kIdealWideFwdMinGroups = 2;  // output groups a workgroup keeps its staged patch for, where O has them
+struct IdealWideFwdG {
+  int rows, mt;                  // rows of a 64-pixel tile (64 / W), tiles per image
+  int pb, span, ngroups;         // pixel blocks per wave (2 or 4), output blocks per group (4 pb), groups in O
+  int gpw, ny;                   // groups per workgroup, workgroups in blockIdx.y
+};
+
 }  // namespace cimq

@@ -1301,13 +1301,16 @@ def ideal_conv_plan(B, C, H, W, O, KH, KW, stride, padding, nbits_a, nbits_w, wi
     """``((ok, ok under CIMQ_OPT_INFERENCE), training descriptor, inference descriptor, ctx bytes, ws bytes, inference
     ctx bytes)`` of the ideal-ADC conv for one shape, asked of the library once (cimq_ideal_plan / cimq_ideal_sizes).
     The two answers differ on large layers: their training call stays on torch, their no-grad forward does not --
-    unless ``wide_backward`` (CIMQ_OPT_WIDE_BWD on the training descriptor) puts it on the large-layer backward pair."""
+    unless ``wide_backward`` (CIMQ_OPT_WIDE_BWD) puts it on the large-layer backward pair.  The hint goes on both
+    descriptors: it changes neither answer for the inference one, and moves the forward of either onto the
+    large-layer forward kernel where cimq_ideal_wide_fwd_plan holds."""
     key = (B, C, H, W, O, KH, KW, tuple(stride), tuple(padding), nbits_a, nbits_w, bool(wide_backward))
     p = _IDEAL_PLANS.get(key)
     if p is None:
         args = (B, C, H, W, O, KH, KW, stride, padding, nbits_w, nbits_a)
-        d = _lib.make_ideal_desc(*args, options=_lib.CIMQ_OPT_WIDE_BWD if wide_backward else 0)
-        di = _lib.make_ideal_desc(*args, options=_lib.CIMQ_OPT_INFERENCE)
+        hint = _lib.CIMQ_OPT_WIDE_BWD if wide_backward else 0
+        d = _lib.make_ideal_desc(*args, options=hint)
+        di = _lib.make_ideal_desc(*args, options=_lib.CIMQ_OPT_INFERENCE | hint)
         ok, oki = bool(_lib.ideal_plan(d)[0]), bool(_lib.ideal_plan(di)[0])
         p = ((ok, oki), d, di) + (_lib.ideal_sizes(d) if ok else (0, 0)) + (_lib.ideal_sizes(di)[:1] if oki else (0,))
         _IDEAL_PLANS[key] = p
@@ -1366,8 +1369,10 @@ def cim_ideal_conv(x, weight, alpha_act, alpha_weight, stride=(1, 1), padding=(0
     ``alpha_weight`` the step-size parameters.  Under no-grad (or with no input requiring a gradient) the call is the
     forward-only descriptor and keeps nothing.  Non-finite inputs are outside its contract (an int8 code cannot carry
     a NaN).  Raises where cimq_ideal_plan refuses the shape; gradients are returned, never accumulated in place.
-    ``wide_backward`` is CIMQ_OPT_WIDE_BWD on the training descriptor: a hint that moves the backward of a large 3 x 3
-    stride-1 layer (cimq_ideal_wide_plan) onto the whole-row-tile kernel pair and changes nothing elsewhere."""
+    ``wide_backward`` is CIMQ_OPT_WIDE_BWD on the descriptor of either kind of call: a hint that moves a large 3 x 3
+    stride-1 layer onto the whole-row-tile kernels -- the backward pair (cimq_ideal_wide_plan) and, in training and
+    no-grad calls alike, the register-blocked forward (cimq_ideal_wide_fwd_plan; the same ``out`` bit for bit) -- and
+    changes nothing elsewhere."""
     train = not inference_call(x, weight, alpha_act, alpha_weight)
     return _IdealConv.apply(x, weight, alpha_act, alpha_weight, _pair(stride), _pair(padding), int(nbits_a),
                             int(nbits_w), train, bool(wide_backward))

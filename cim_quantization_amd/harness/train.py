@@ -61,7 +61,8 @@ def get_base_parser():
                         "up) train on the channel-chunked compact-state backward, and a w8a8 first conv of 32 .. 512 "
                         "output channels on the multi-block recompute backward, where the library's plan takes them; "
                         "with adcbits 0 (the ideal ADC) the 3x3 stride-1 layers from 128 input channels up train on "
-                        "the library's whole-row-tile backward pair instead of the vendor conv")
+                        "the library's whole-row-tile backward pair instead of the vendor conv, and run their forward, "
+                        "in training and in validate(), on the library's register-blocked large-layer kernel")
     return p
 
 

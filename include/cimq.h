@@ -802,11 +802,11 @@ int cimq_ideal_backward(const cimq_ideal_desc* d, const float* x, const float* w
 
 /* The large-layer backward of the ideal-ADC conv.  cimq_ideal_wide_abi() == 1 where cimq_ideal_desc.options takes
  * CIMQ_OPT_WIDE_BWD.  The bit is a hint, as on the module entry points: where cimq_ideal_wide_plan holds, the bound on
- * multiply-accumulates of a training descriptor does not apply, cimq_ideal_forward runs what it runs without the bit
- * and cimq_ideal_backward runs cim_ideal_gx_wide_kernel + cim_ideal_gw_wide_kernel (whole-row 64-pixel tiles, aligned
+ * multiply-accumulates of a training descriptor does not apply, cimq_ideal_forward writes the out it writes without the
+ * bit (on the large-layer forward where cimq_ideal_wide_fwd_plan holds, below) and cimq_ideal_backward runs cim_ideal_gx_wide_kernel + cim_ideal_gw_wide_kernel (whole-row 64-pixel tiles, aligned
  * 16-byte LDS operand reads, no per-lane predicate) before the same two finishing kernels; cimq_ideal_sizes answers for
  * the descriptor as given (ctx and ws may differ from the plain descriptor's).  Everywhere else, and together with
- * CIMQ_OPT_INFERENCE, the descriptor answers exactly as it does without the bit.  Same sums in a fixed order: two
+ * CIMQ_OPT_INFERENCE, the descriptor's plans, sizes and results are exactly those it has without the bit.  Same sums in a fixed order: two
  * calls give the same bits; the order differs from the plain backward's, so the two agree to rounding only. */
 int cimq_ideal_wide_abi(void);
 
@@ -817,6 +817,22 @@ int cimq_ideal_wide_abi(void);
  * and 3 x 3, stride 1, pad 1, W in {8, 16, 32}, H * W a multiple of 64, C >= 128 and a multiple of 16, O a multiple
  * of 32. */
 int cimq_ideal_wide_plan(const cimq_ideal_desc* d, int out[6]);
+
+/* The large-layer forward of the ideal-ADC conv.  cimq_ideal_wide_fwd_abi() == 1 where CIMQ_OPT_WIDE_BWD is the hint
+ * for the large-layer kernels of this path, forward included: where cimq_ideal_wide_fwd_plan holds for a descriptor
+ * that carries the bit -- a training one or, here alone, one that also carries CIMQ_OPT_INFERENCE --
+ * cimq_ideal_forward runs cim_ideal_fwd_wide_kernel after the weight quantiser (whole-row 64-pixel tiles, a patch
+ * with a zero halo staged once per workgroup and kept for its output groups, 8 or 16 int8 MFMAs a wave per k-step,
+ * float4 stores).  out is bit for bit what the descriptor gives without the bit; ctx, ws, cimq_ideal_plan,
+ * cimq_ideal_sizes and cimq_ideal_wide_plan answer as before. */
+int cimq_ideal_wide_fwd_abi(void);
+
+/* Host query, no device work.  out[0] = 1 where cimq_ideal_forward runs d on the large-layer forward (0 with
+ * CIMQ_EUNSUPPORTED and the reason, starting "ideal wide fwd:", in cimq_last_error() otherwise), out[1] = 64-pixel
+ * tiles per image, out[2] = channel chunks of the LDS patch, out[3] = output groups per workgroup, out[4] =
+ * workgroups in blockIdx.y, out[5] = LDS bytes.  Admitted: all cimq_ideal_forward takes d with, and 3 x 3, stride 1,
+ * pad 1, W in {8, 16, 32}, H * W a multiple of 64, C >= 128 and a multiple of 16, O a multiple of 32, bits_a <= 7. */
+int cimq_ideal_wide_fwd_plan(const cimq_ideal_desc* d, int out[6]);
 
 #ifdef __cplusplus
 }
